@@ -2,7 +2,7 @@
 """Headline benchmark: clips/s for encode + greedy decode of the Cnn14Rnn-Trm captioner on synthetic
 10 s @ 32 kHz clips (BASELINE.json metric, configs[1]: batch 64 per GPU, max_length 20).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One process per GPU (torch.distributed / RCCL when N > 1): launched under ``torch.distributed.run`` the ranks are read
 from the environment; launched plainly with ``--gpus N > 1`` the script re-executes itself under
@@ -25,6 +25,8 @@ decoding, token ids back on the host) over one resident batch.  Rank 0 prints ON
   15-30 s clips, zero-padded: with / without dead-row skipping);
 * ``cpu_baseline``: the oracle (CPU restatement of the reference) on all physical host cores, median of 5 passes over a
   bounded 32-clip sample.
+``--dump-outputs DIR`` writes the arrays the last timed step returned (token ids, log-probabilities, logits, decoder
+embeddings, encoder outputs of rank 0's batch) as ``DIR/<name>.npy`` (see ``host_outputs`` / ``dump_outputs``).
 The per-tier rooflines, the steady-state window, the decoder GEMM table, the training-step and EffB2 objects go to
 ``gpurun_out/bench_details.json`` (``details_file``) so that the printed line stays short.
 """
@@ -214,6 +216,49 @@ def timed_steps(ranks, run, steps):
     return ranks.max_seconds(ranks.last_own), out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+PER_STEP_KEYS = ("seq", "sampled_logprob", "logit", "embed")   # (B, max_length, ...) arrays of a greedy decode
+
+
+def host_outputs(out, steps_ran=None):
+    """The arrays of one step's result on the host: tensors and numeric lists of ``out``, floating types as float32
+    (float64 kept), integer and bool types as float64 (exact).  ``steps_ran`` (bool per decode step): columns of the
+    PER_STEP_KEYS arrays for steps that did not run are zeroed - they hold whatever their buffer held before."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            v = v.double() if not v.is_floating_point() else v if v.dtype == torch.float64 else v.float()
+            a = v.numpy().copy()
+        elif isinstance(v, (list, tuple)) and v and all(isinstance(x, (int, float)) for x in v):
+            a = np.asarray(v, dtype=np.float64)
+        else:
+            continue
+        if steps_ran is not None and k in PER_STEP_KEYS and a.ndim >= 2 and a.shape[1] == len(steps_ran):
+            a[:, ~steps_ran] = 0
+        arrays[k] = a
+    return arrays
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """``--dump-outputs``: every array as ``dirpath/<name>.npy``.  Beyond ``budget`` bytes in all, the same fixed seeded
+    sample of batch rows (axis 0) is taken from every array with the largest leading dimension, and the chosen row
+    indices go to ``sample_rows.npy``."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        rows = max(a.shape[0] for a in arrays.values() if a.ndim)
+        keep = max(1, int(rows * budget / total) - 1)
+        pick = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        arrays = {k: a[pick] if a.ndim and a.shape[0] == rows else a for k, a in arrays.items()}
+        arrays["sample_rows"] = pick.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{k}.npy"), a)
+    return sorted(arrays)
+
+
 def collective_record(ranks, dev, nccl_floats=10_700_000):
     """What makes an N > 1 line self-describing about the node's collectives: on RCCL the all-reduce / reduce-scatter +
     all-gather rates on a buffer of the training step's gradient size; on gloo (CPU ranks, tests) the same two spellings of
@@ -261,7 +306,9 @@ def bench_stub(args, ranks):
         return y
 
     run(args.warmup)
-    elapsed, _ = timed_steps(ranks, run, args.steps)
+    elapsed, y = timed_steps(ranks, run, args.steps)
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, host_outputs({"y": y}))
     who = ranks.describe()      # collective: every rank calls it
     per_rank = seconds_per_rank(ranks, ranks.last_own, "cpu")
     rccl = collective_record(ranks, "cpu")
@@ -765,7 +812,15 @@ def main():
     ap.add_argument("--train-batch", type=int, default=32, help="clips per GPU per training step")
     ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step measurement")
     ap.add_argument("--stub-workload", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's batch) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all; the inputs are seeded, so two runs with the same "
+                         "arguments can be compared array for array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "infer":
+        ap.error("--dump-outputs covers the headline workload (--mode infer)")
 
     # `python bench.py --gpus N` without a launcher: spawn the N ranks ourselves
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -896,6 +951,12 @@ def main():
     # ---- timed region: exactly K steps of the default tier ----
     elapsed, out, events = measure(default_tier, args.steps, args.warmup)
     elapsed_own = ranks.last_own
+    if args.dump_outputs and rank == 0:
+        # before any later measurement reuses the decoder's buffers; step t ran iff rows were unfinished after t - 1
+        cnt = out["unfinished_cnt"].cpu()
+        ran = torch.ones(cnt.shape[0], dtype=torch.bool)
+        ran[1:] = cnt[:-1] > 0
+        dump_outputs(args.dump_outputs, host_outputs(out, steps_ran=ran.numpy()))
     ref_steps = min(int((out["unfinished_cnt"].cpu() > 0).sum().item()) + 1, args.max_length)
     # the headline line cites this round's PMC file: missing = error (AUDIOCAPTION_TRAFFIC_OPTIONAL=1: the collection passes
     # themselves, tools/round_profiles.sh, which run before the file exists)

@@ -80,3 +80,39 @@ def test_bench_two_ranks_real_workload_on_one_gpu():
     assert [r["rank"] for r in res["ranks"]] == [0, 1] and len(res["seconds_per_rank"]) == 2
     assert res["rccl"]["world_size"] == 2 and res["scaling"] == "weak"
     assert abs(res["value"] - 8 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: what the last timed step returned, as float32 / float64 .npy files; seeded inputs, so two runs with
+    the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        res = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-workload", "--dump-outputs", str(d)])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert list(dumps[0]) == ["y.npy"] and dumps[0]["y.npy"].dtype == np.float32
+    assert dumps[0]["y.npy"].shape == (128, 128) and np.array_equal(dumps[0]["y.npy"], dumps[1]["y.npy"])
+
+
+def test_dump_outputs_samples_the_same_rows_of_every_array_within_the_budget(tmp_path):
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    import torch
+    steps = torch.tensor([True, True, False])
+    arrays = bench.host_outputs({"logit": torch.arange(64 * 3 * 100, dtype=torch.float16).view(64, 3, 100),
+                                 "seq": torch.arange(64 * 3).view(64, 3), "attn_emb_len": [5] * 64,
+                                 "note": "not an array"}, steps_ran=steps.numpy())
+    assert sorted(arrays) == ["attn_emb_len", "logit", "seq"]
+    assert arrays["logit"].dtype == np.float32 and arrays["seq"].dtype == np.float64
+    assert not arrays["logit"][:, 2].any() and arrays["seq"][3, 1] == 10          # the step that did not run is zeroed
+    names = bench.dump_outputs(str(tmp_path), arrays, budget=20_000)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert sum(a.nbytes for a in got.values()) <= 20_000
+    rows = got["sample_rows"].astype(np.int64)
+    assert 0 < len(rows) < 64 and np.array_equal(got["seq"], arrays["seq"][rows])
+    assert np.array_equal(got["logit"], arrays["logit"][rows])
+    again = bench.dump_outputs(str(tmp_path / "again"), arrays, budget=20_000)
+    assert again == names and np.array_equal(np.load(tmp_path / "again" / "sample_rows.npy"), got["sample_rows"])

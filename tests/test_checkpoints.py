@@ -1,7 +1,7 @@
 """CPU tests of the checkpoint side of the boundary: every checkpoint layout the
 reference's loaders accept is fabricated here (procedural weights, the reference's key names) and loaded through this
-package's mirror of those loaders; and the reference's OWN plugin loader builds this package's classes from the
-reference's unchanged YAML files after ``compat.install()`` (container only: /root/reference does not travel)."""
+package's mirror of those loaders; and the reference's dotted class paths build this package's classes after
+``compat.install()``."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,6 @@ import audiocaption_amd as A
 from audiocaption_amd import config, procedural as P
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -252,23 +251,23 @@ def test_decoder_load_pretrained_takes_the_decoder_entries(tmp_path, state4981):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the reference's own plugin loader on its unchanged YAML files (container only)
+# the reference's dotted class paths, resolved through compat.install() alone (no alias table)
 # ---------------------------------------------------------------------------------------------------------------------
-_REF_LOADER = r'''
-import sys, types
+_COMPAT_LOADER = r"""
+import sys
 sys.dont_write_bytecode = True
-sys.path.insert(0, {repo!r}); sys.path.insert(0, {ref!r})
-for name, attrs in (("toml", dict(loads=lambda s: {{}}, load=lambda f: {{}})), ("h5py", {{}}), ("wandb", dict(run=None))):
-    m = types.ModuleType(name); m.__dict__.update(attrs); sys.modules[name] = m     # non-arithmetic imports of train_util / loss
-from audiocaption_amd import compat
+sys.path.insert(0, {repo!r})
+from audiocaption_amd import compat, config
 compat.install()
-from captioning.utils import train_util                                            # the REFERENCE's loader
+config.ALIASES.clear()              # every captioning.* path must now resolve through the modules compat registered
 import audiocaption_amd as A
 said = []
-for yaml_path, vocab, total in (("eg_configs/audiocaps/waveform/cnn14rnn_trm.yaml", 4981, 90395840),
-                                ("eg_configs/clotho_v2/waveform/cnn14rnn_trm.yaml", 4368, 90081984)):
-    cfg = train_util.load_config({ref!r} + "/" + yaml_path)                        # inherit_from resolved by the reference
-    model = train_util.init_model_from_config(cfg["model"], print_fn=said.append)
+for vocab, encoder_name, total in ((4981, "CrnnEncoder", 90395840),         # eg_configs/audiocaps/waveform/cnn14rnn_trm.yaml
+                                   (4368, "Cnn14RnnEncoder", 90081984)):    # eg_configs/clotho_v2/waveform/cnn14rnn_trm.yaml
+    section = config.cnn14rnn_trm_config(vocab, encoder_name)
+    assert all(section[k]["type"].startswith("captioning.") for k in ("encoder", "decoder"))
+    section["encoder"]["cnn"]["pretrained"] = "experiments/pretrained_encoder/Cnn14_mAP=0.431.pth"   # as in the YAML files
+    model = config.init_model_from_config(section, print_fn=said.append)
     assert type(model) is A.TransformerModel, type(model)
     assert type(model.encoder) is A.CrnnEncoder and type(model.encoder.cnn) is A.Cnn14Encoder
     assert type(model.encoder.rnn) is A.RnnEncoder and type(model.decoder) is A.TransformerDecoder
@@ -276,16 +275,18 @@ for yaml_path, vocab, total in (("eg_configs/audiocaps/waveform/cnn14rnn_trm.yam
     assert sum(p.numel() for p in model.parameters()) == total, sum(p.numel() for p in model.parameters())
     assert not any(p.requires_grad for p in model.encoder.cnn.parameters())         # freeze_cnn: True
     assert model.encoder.freeze_cnn_bn
-loss = train_util.init_obj_from_dict(cfg["loss"])
+loss = config.init_obj_from_dict({{"type": "captioning.losses.loss.LabelSmoothingLoss", "args": {{"smoothing": 0.1}}}})
 assert type(loss).__module__ == "audiocaption_amd.loss", type(loss)
-assert any("not exist" in s for s in said), said                                    # the PANNs file of the YAML is absent here
-print("REF-LOADER-OK")
-'''
+assert any("not exist" in s for s in said), said                                    # the PANNs file of the YAML is absent
+print("COMPAT-LOADER-OK")
+"""
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the build container")
-def test_reference_loader_builds_this_package_from_unchanged_yaml():
-    code = _REF_LOADER.format(repo=REPO, ref=REF)
-    r = subprocess.run([sys.executable, "-c", code], cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=600)
-    assert r.returncode == 0 and "REF-LOADER-OK" in r.stdout, r.stderr[-3000:]
+def test_reference_dotted_paths_build_this_package_through_compat(tmp_path):
+    """The model and loss sections of the reference's cnn14rnn_trm YAML files (AudioCaps and Clotho), built in a fresh
+    interpreter after ``compat.install()`` with the package's alias table emptied: the reference's dotted class paths
+    alone must yield this package's classes, parameter counts and freeze flags."""
+    code = _COMPAT_LOADER.format(repo=REPO)
+    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=600)
+    assert r.returncode == 0 and "COMPAT-LOADER-OK" in r.stdout, r.stderr[-3000:]

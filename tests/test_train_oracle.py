@@ -99,7 +99,9 @@ def _allreduce_worker(rank, world, port, out):
             assert allreduce_flat_gradients(b, algo="rs_ag") == world
             allreduce_flat_gradients(c, async_op=True, algo="rs_ag").wait()
             same = same and torch.equal(a, b) and torch.equal(a, c)
-        out.put((rank, w, flat.clone(), coef, same))
+        # a numpy copy travels by value: a torch tensor would be shared through a descriptor that this process must stay
+        # alive to hand over, and it exits right after the put
+        out.put((rank, w, flat.numpy().copy(), coef, same))
     finally:
         dist.destroy_process_group()
 
@@ -117,7 +119,7 @@ def test_flat_gradient_allreduce_world2_gloo():
         assert p.exitcode == 0
     want = torch.arange(1000, dtype=torch.float32) * 3
     for rank, w, flat, coef, same in res:
-        assert w == 2 and torch.equal(flat, want)
+        assert w == 2 and torch.equal(torch.from_numpy(flat), want)
         avg = want / 2
         assert coef * 2 == pytest.approx(min(1.0, 1.0 / (float(avg.norm()) + 1e-6)))
         assert same, "reduce_scatter + all_gather differs from all_reduce"
