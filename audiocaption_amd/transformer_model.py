@@ -665,13 +665,15 @@ class TransformerModel(CaptionModel):
         if not run["use_graph"]:
             run["segment"](t0, t1)
         else:
-            graph = st["graphs"].get(t0)
+            # keyed by the step range: AUDIOCAPTION_BEAM_SEGMENTS is read per call, and a segment that starts at the same
+            # step under another list ends at another step
+            graph = st["graphs"].get((t0, t1))
             if graph is None:
                 torch.cuda.synchronize(run["dev"])
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     run["segment"](t0, t1)
-                st["graphs"][t0] = graph
+                st["graphs"][(t0, t1)] = graph
             graph.replay()
         run["next"] = i + 1
         return True

@@ -323,7 +323,9 @@ def beam_search(state, attn_emb, attn_emb_len, beam_size=3, max_length=20, temp=
             if trace is not None:
                 cand = (lp[0] if t == 0 else lp.view(-1)).topk(beam_size + 1).values
                 trace.append({"clip": i, "t": t, "prev_beam": prev_beam.tolist(), "ended": is_end.tolist(),
-                              "margin": float((cand[:-1] - cand[1:]).min())})   # smallest gap among the kept and to the first cut
+                              "margin": float((cand[:-1] - cand[1:]).min()),    # smallest gap among the kept and to the first cut
+                              "cut": float(cand[-2] - cand[-1]),                # gap between the last kept and the first cut
+                              "end_scores": [topk_logprob[b].item() / (t + 1) for b in range(beam_size) if is_end[b]]})
             for b in range(beam_size):
                 if is_end[b]:
                     done.append({"seq": seq[b].clone(), "score": topk_logprob[b].item() / (t + 1)})
