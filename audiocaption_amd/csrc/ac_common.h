@@ -92,3 +92,30 @@ static inline int ac_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? AC_OK : AC_ERR_LAUNCH;
 }
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011): the counter-based generator
+// of the on-device samplers.  Ten rounds of two 32x32 -> 64-bit multiplies; the key is bumped by the Weyl constants between
+// rounds.  A draw depends on (key, counter) only: no state, so it is the same in any launch order, batch or graph replay.
+// ctr[4] is replaced by the output block.  Known answers (Random123 kat_vectors) in tests/test_sampling_cpu.py.
+__host__ __device__ inline void ac_philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * ctr[0];
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ctr[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ ctr[1] ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ ctr[3] ^ k1;
+    ctr[0] = n0;
+    ctr[1] = (uint32_t)p1;
+    ctr[2] = n2;
+    ctr[3] = (uint32_t)p0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// The sampler's uniform for (seed, step, row): counter (step, row, 0, 0), key (seed lo, seed hi), word 0 ->
+// ((x0 >> 8) + 1) * 2^-24, a float in (0, 1] (24 random bits; exact in f32).
+__host__ __device__ inline float ac_sample_uniform(uint64_t seed, uint32_t step, uint32_t row) {
+  uint32_t c[4] = {step, row, 0u, 0u};
+  ac_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (float)((c[0] >> 8) + 1u) * 5.9604644775390625e-8f;
+}

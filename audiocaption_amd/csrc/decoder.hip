@@ -16,6 +16,7 @@
 // Projections run on the f32 matrix cores through ac_linear; softmax / LayerNorm reductions are
 // 64-lane wavefront shuffles.
 #include "ac_common.h"
+#include "ac_sample.h"
 #include "../../include/audiocaption_hip.h"
 #include <stdlib.h>
 #include <string.h>
@@ -1546,13 +1547,16 @@ extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int m
   return (long)carve(w, rows, max_len, nullptr).total;
 }
 
-extern "C" int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm,
-                             int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
-                             float* logprob, float* embed, int* unfinished_cnt, float* ws_base, void* stream) {
+// The on-device search of ac_trm_greedy / ac_trm_sample: `sp` null = the argmax pick, else the sampler with these
+// method parameters (its row / bookkeeping fields are filled per step here).
+static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm, int max_len,
+                      int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob, float* embed,
+                      int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !seq || !logit || !logprob || !embed || !unfinished_cnt || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || Tm <= 0 || Tm > MAX_KEYS || max_len <= 0 || max_len > w->max_pos) return AC_ERR_ARG;
   if (w->vocab > PICK_MAXV) return AC_ERR_ARG;
+  if (sp && (ac_sample_check(w->vocab, sp->method, sp->k, sp->top_p, sp->temp) != AC_OK || !sp->seed)) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const Ws ws = carve(w, B, max_len, ws_base);
   const int d = w->d_model, V = w->vocab;
@@ -1566,6 +1570,15 @@ extern "C" int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const 
                         &fin, s));
     AC_TRY(classifier_step(w, fin, B, embed + (size_t)t * d, (long)max_len * d, logit + (size_t)t * V,
                            (long)max_len * V, s));
+    if (sp) {
+      SampleParams q = *sp;
+      q.logit = logit + (size_t)t * V; q.ldl = (long)max_len * V; q.rows = B; q.V = V; q.t = t; q.word = nullptr;
+      q.logprob = logprob + t; q.ld_lp = max_len;
+      q.seq = seq; q.max_len = max_len; q.end_idx = end_idx; q.pad_idx = pad_idx;
+      q.tok = ws.tok; q.mask = ws.mask; q.unfinished = ws.unfinished; q.cnt = unfinished_cnt;
+      AC_TRY(ac_sample_launch(q, s));
+      continue;
+    }
     PickParams p;
     p.logit = logit + (size_t)t * V; p.ldl = (long)max_len * V;
     p.V = V; p.t = t; p.max_len = max_len; p.end_idx = end_idx; p.pad_idx = pad_idx;
@@ -1575,6 +1588,23 @@ extern "C" int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const 
     AC_TRY(ac_check_launch());
   }
   return AC_OK;
+}
+
+extern "C" int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm,
+                             int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
+                             float* logprob, float* embed, int* unfinished_cnt, float* ws_base, void* stream) {
+  return trm_search(w, memkv, mem_len, B, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, nullptr, stream);
+}
+
+extern "C" int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm, int max_len,
+                             int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                             float* embed, int* unfinished_cnt, float* ws_base, int method, int k, float top_p, float temp,
+                             const uint64_t* seed_dev, void* stream) {
+  SampleParams sp = {};
+  sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
+  return trm_search(w, memkv, mem_len, B, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, &sp, stream);
 }
 
 extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv, const int* mem_len, int N,

@@ -240,6 +240,22 @@ class TransformerDecoder(BaseDecoder):
                                 ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()),
               "ac_trm_greedy")
 
+    def _search_buffers(self, key, dev, B, Tm, A, max_length):
+        """Static buffers of an on-device search (greedy or sampled) over B rows: inputs, workspace, outputs."""
+        f32 = dict(device=dev, dtype=torch.float32)
+        ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), B, max_length)
+        return {
+            "key": key, "graph": None, "uses": 0,
+            "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
+            "memkv": torch.empty(self.nlayers, B * Tm, 2 * self.d_model, **f32),
+            "tmp": torch.empty(B * Tm, self.d_model, **f32), "ws": torch.empty(ws_n, **f32),
+            "seq": torch.empty(B, max_length, device=dev, dtype=torch.int64),
+            "logit": torch.empty(B, max_length, self.vocab_size, **f32),
+            "sampled_logprob": torch.empty(B, max_length, **f32),
+            "embed": torch.empty(B, max_length, self.d_model, **f32),
+            "unfinished_cnt": torch.empty(max_length, device=dev, dtype=torch.int32),
+        }
+
     def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None):
         """On-device greedy search.  Returns device tensors seq (int64), logit, logprob, embed, cnt.  ``attn_emb`` /
         ``attn_emb_len``: one batch, or lists of batches of the same (frames, width) decoded as one chain.
@@ -277,19 +293,7 @@ class TransformerDecoder(BaseDecoder):
         states = self._greedy_state
         st = states.pop(key, None)
         if st is None:
-            f32 = dict(device=dev, dtype=torch.float32)
-            ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), B, max_length)
-            st = {
-                "key": key, "graph": None, "uses": 0,
-                "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
-                "memkv": torch.empty(self.nlayers, B * Tm, 2 * self.d_model, **f32),
-                "tmp": torch.empty(B * Tm, self.d_model, **f32), "ws": torch.empty(ws_n, **f32),
-                "seq": torch.empty(B, max_length, device=dev, dtype=torch.int64),
-                "logit": torch.empty(B, max_length, self.vocab_size, **f32),
-                "sampled_logprob": torch.empty(B, max_length, **f32),
-                "embed": torch.empty(B, max_length, self.d_model, **f32),
-                "unfinished_cnt": torch.empty(max_length, device=dev, dtype=torch.int32),
-            }
+            st = self._search_buffers(key, dev, B, Tm, A, max_length)
             if cluster:
                 nb = _lib.load().ac_trm_cluster_workspace_bytes(B)
                 st["cluster_ws"] = torch.zeros((nb + 7) // 8, device=dev, dtype=torch.int64)   # (the error word is reset by every call)
@@ -322,6 +326,60 @@ class TransformerDecoder(BaseDecoder):
         if cluster:
             out["cluster_error"] = st["cluster_ws"][:1].clone()
         return out
+
+    def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params):
+        """Memory preparation + the whole sampled search on the current stream (capturable; the seed is read on the device)."""
+        lib = _lib.load()
+        B, Tm, _ = st["attn_emb"].shape
+        w = ctypes.byref(self.weights())
+        method, k, top_p, temp = params
+        check(lib.ac_trm_memory(w, ptr(st["attn_emb"]), B, Tm, ptr(st["memkv"]), ptr(st["tmp"]), stream()),
+              "ac_trm_memory")
+        check(lib.ac_trm_sample(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx, pad_idx,
+                                ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
+                                ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp),
+                                ptr(st["seed"]), stream()), "ac_trm_sample")
+
+    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed):
+        """On-device sampled search (base.py:152-170 with a sampling ``sample_method``; csrc/sample.hip).  ``method``, ``k``,
+        ``top_p``, ``temp``: ``sampling.parse_sample_method``; ``seed``: 64-bit Philox key - row b of step t draws from
+        counter (t, b), so a caption depends on (seed, row, step) only.  Returns what ``greedy`` returns.
+
+        Always the launch chain (the one-launch cluster form picks the argmax only).  Like ``greedy``, the launch sequence
+        is captured per shape AND sampling parameters (second use) into a HIP graph over static buffers and replayed; the
+        seed lives in a device word that is written before every launch or replay, so one graph serves every seed.
+        AUDIOCAPTION_DECODE_GRAPH=0 launches eagerly."""
+        from .sampling import seed_word
+        dev = attn_emb.device
+        B, Tm, A = attn_emb.shape
+        use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
+        params = (int(method), int(k), float(top_p), float(temp))
+        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key())
+        if getattr(self, "_sample_state", None) is None:
+            self._sample_state = {}
+        states = self._sample_state
+        st = states.pop(key, None)
+        if st is None:
+            st = self._search_buffers(key, dev, B, Tm, A, max_length)
+            st["seed"] = torch.zeros(1, device=dev, dtype=torch.int64)
+        states[key] = st                       # most recently used last
+        while len(states) > 8:
+            states.pop(next(iter(states)))
+        st["uses"] += 1
+        st["attn_emb"].copy_(attn_emb)
+        st["mem_len"].copy_(K.upload(attn_emb_len, dev, torch.int32))
+        st["seed"].fill_(seed_word(seed))
+        if not use_graph or st["uses"] < 2:
+            self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params)
+        else:
+            if st["graph"] is None:
+                torch.cuda.synchronize(dev)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params)
+                st["graph"] = graph
+            st["graph"].replay()
+        return {k_: st[k_].clone() for k_ in ("seq", "logit", "sampled_logprob", "embed", "unfinished_cnt")}
 
     def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws):
         lib = _lib.load()

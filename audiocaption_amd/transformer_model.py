@@ -130,6 +130,8 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             forward_dict["beam_size"] = input_dict.get("beam_size", 3)
             forward_dict["n_best"] = input_dict.get("n_best", False)
             forward_dict["n_best_size"] = input_dict.get("n_best_size", forward_dict["beam_size"])
+        if input_dict.get("seed") is not None:    # sampling: the caller's 64-bit seed (otherwise drawn per call)
+            forward_dict["seed"] = input_dict["seed"]
         forward_dict.update(encoder_output_dict)
         return forward_dict
 
@@ -139,9 +141,11 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             return self.beam_search(input_dict)
         if method == "greedy":
             return self.greedy_search(input_dict)
-        raise NotImplementedError(
-            f"sample_method={method!r}: only 'greedy' and 'beam' are on the accelerated path "
-            "(dbs / gumbel / top-k / top-p sampling are out of scope, SURVEY.md §2.1 row 7)")
+        if method == "dbs":
+            # the reference's TransformerModel has no prepare_dbs_decoder_input either: it raises there too
+            raise NotImplementedError(
+                "sample_method='dbs': diverse beam search is not on the accelerated path (SURVEY.md §2.1 row 7)")
+        return self.sample_search(input_dict)
 
 
 def _device_flags(enc):
@@ -545,6 +549,28 @@ class TransformerModel(CaptionModel):
             res = self.decoder.greedy(*args, mode="chain")
         return {
             "seq": res["seq"].cpu(),                          # the reference keeps seq on the CPU (base.py:122)
+            "logit": res["logit"],
+            "sampled_logprob": res["sampled_logprob"].cpu(),  # CPU as in base.py:126
+            "embed": res["embed"],
+            "unfinished_cnt": res["unfinished_cnt"],
+        }
+
+    # ---- sampling (base.py:152-170 + sample_next_word :214-252) -----------------------------------------
+    def sample_search(self, input_dict):
+        """Temperature / top-k / top-p / Gumbel sampling, the whole search on the device (``TransformerDecoder.sample``).
+        ``input_dict["seed"]`` (64-bit) fixes the draws; without it a seed is drawn from torch's default CPU generator, so
+        ``torch.manual_seed`` makes runs reproducible as in the reference.  Gumbel-max is exactly a categorical draw from
+        softmax(lp), so "gumbel" takes the same one-uniform inverse-CDF draw as plain sampling at temp 1 (the stored
+        ``sampled_logprob`` is lp[w], per row - the reference's gather keeps a trailing dimension that fails for batches
+        larger than one)."""
+        from .sampling import draw_seed, parse_sample_method
+        method, k, top_p, temp = parse_sample_method(input_dict["sample_method"], self.vocab_size, input_dict.get("temp", 1.0))
+        seed = input_dict.get("seed")
+        seed = draw_seed() if seed is None else int(seed)
+        res = self.decoder.sample(input_dict["attn_emb"], input_dict["attn_emb_len"], int(input_dict["max_length"]),
+                                  self.start_idx, self.end_idx, self.pad_idx, method, k, top_p, temp, seed)
+        return {
+            "seq": res["seq"].cpu(),                          # CPU as in base.py:122
             "logit": res["logit"],
             "sampled_logprob": res["sampled_logprob"].cpu(),  # CPU as in base.py:126
             "embed": res["embed"],

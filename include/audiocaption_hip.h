@@ -345,6 +345,35 @@ int ac_trm_greedy_cluster(const ac_trm_weights* w, const float* cluster_pk, cons
                           int Tm, int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
                           float* logprob, float* embed, int* unfinished_cnt, void* workspace, int early_stop, void* stream);
 
+/* ---- sampling (base.py:214-252 sample_next_word; stepwise_forward base.py:152-170) -------------
+ * method: AC_SAMPLE_PLAIN ("sample" and any name not below: softmax(lp / temp)), AC_SAMPLE_TOPK ("top<k>", k >= 1: the k
+ * largest lp, softmax(lp / temp) over them), AC_SAMPLE_TOPP ("top<p>", 0 < p < 1: q = softmax(logit), the shortest prefix of
+ * q sorted descending whose mass reaches p, renormalised; temp not used), AC_SAMPLE_GUMBEL ("gumbel": argmax(lp + Gumbel
+ * noise) is a draw from softmax(lp); temp does not change the argmax).  lp = log_softmax(logit) in f32.  Ties at the top-k /
+ * top-p boundary keep the lower index.  The draw is the inverse CDF in vocabulary order over the kept weights with
+ * u = ((x0 >> 8) + 1) * 2^-24, x0 = word 0 of Philox4x32-10 at counter (step, row, 0, 0) and key (seed lo, seed hi): it
+ * depends on (seed, row, step) only.  The stored log-probability of the word: lp[w] / temp (plain, top-k: not renormalised),
+ * log(q[w] / sum of the kept q) (top-p), lp[w] (gumbel).  seed_dev: ONE uint64 in device memory, read by the kernels (a
+ * captured graph replays with the seed the word holds then).  V <= 16384.  AC_ERR_ARG: temp <= 0 (plain, top-k), k < 1 or
+ * k > V, p outside (0, 1), unknown method. */
+#define AC_SAMPLE_PLAIN 0
+#define AC_SAMPLE_TOPK 1
+#define AC_SAMPLE_TOPP 2
+#define AC_SAMPLE_GUMBEL 3
+
+/* The sampler alone: row r of logit (at logit + r * ld, V words) -> word_out[r] (int32), logprob_out[r], Philox step `step`. */
+int ac_sample_rows(const float* logit, long ld, int rows, int V, int method, int k, float top_p, float temp,
+                   const uint64_t* seed_dev, int step, int* word_out, float* logprob_out, void* stream);
+
+/* Sampled decoding: ac_trm_greedy's search (same arguments, same outputs, the launch chain) with the token of every step drawn
+ * by the sampler above instead of the argmax (base.py:152-170 with sample_method != "greedy"): row b of step t draws with
+ * counter (t, b).  Bookkeeping as in greedy decoding: a finished row's seq column is end_idx, its logprob column keeps the
+ * drawn word's value (what the reference stores); unfinished_cnt as in ac_trm_greedy. */
+int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm, int max_len,
+                  int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                  float* embed, int* unfinished_cnt, float* ws, int method, int k, float top_p, float temp,
+                  const uint64_t* seed_dev, void* stream);
+
 /* Decoder forward on given tokens (teacher forcing / plugin call, transformer_decoder.py:80-103):
  * tokens [N][T] int32; key_mask [N][T] uint8 (1 = masked key, the reference's cap_padding_mask /
  * tgt_key_padding_mask, transformer_model.py:22-23,55) or NULL.  embed [N][T][d], logit [N][T][V]. */
