@@ -1221,11 +1221,12 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long n
 __global__ void adam_commit_kernel(int* step_dev, const float* norm_state) {
   if (!(norm_state && norm_state[3] != 0.f)) *step_dev += 1;
 }
-// stochastic weight averaging (train_util.py:233-253 with torch's default avg_fn): avg += (p - avg) / (n_averaged + 1)
+// stochastic weight averaging (train_util.py:233-253 with torch's default avg_fn): avg += (p - avg) / (n_averaged + 1);
+// n_averaged = 0 is AveragedModel's first update, a plain copy: avg + (p - avg) is not p when avg is far from p (or NaN)
 __global__ void swa_kernel(float* avg, const float* p, long n, float inv) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float a = avg[i];
-    avg[i] = a + (p[i] - a) * inv;
+    avg[i] = inv == 1.0f ? p[i] : a + (p[i] - a) * inv;
   }
 }
 __global__ void scale_kernel(float* x, long n, const float* norm_state) {

@@ -267,23 +267,9 @@ def test_gru_layer_train_forward_backward(lib):
     bhh = torch.randn(2, 3 * H, generator=g) * 0.1
     dout = torch.randn(B, T, 2 * H, generator=g)
     # reference: explicit recurrence with autograd (gx plays x W_ih^T + b_ih: identity input projection)
+    from _train_ref import gru_bidir_reference
     gxr, whr, bhr = (t.clone().requires_grad_(True) for t in (gx, whh, bhh))
-    outs = []
-    lens_t = torch.tensor(lens)
-    for d in range(2):
-        out = torch.zeros(B, T, H)
-        h = torch.zeros(B, H)
-        for t in (range(T - 1, -1, -1) if d else range(T)):
-            gh = torch.nn.functional.linear(h, whr[d], bhr[d])
-            r = torch.sigmoid(gxr[:, t, d, :H] + gh[:, :H])
-            z = torch.sigmoid(gxr[:, t, d, H:2 * H] + gh[:, H:2 * H])
-            n = torch.tanh(gxr[:, t, d, 2 * H:] + r * gh[:, 2 * H:])
-            hn = (1 - z) * n + z * h
-            valid = (t < lens_t).unsqueeze(1)
-            h = torch.where(valid, hn, h)
-            out[:, t] = torch.where(valid, hn, torch.zeros_like(hn))
-        outs.append(out)
-    out_ref = torch.cat(outs, -1)
+    out_ref = gru_bidir_reference(gxr, whr, bhr, lens)
     out_ref.backward(dout)
     dev = "cuda"
     whhT = torch.empty(2, H, 3 * H, device=dev)
