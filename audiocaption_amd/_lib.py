@@ -99,6 +99,8 @@ SIGNATURES = {
                              _I, _I, _I, _F, _U64, _P, _P]),
     "ac_attn_seq_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _I,
                              _I, _I, _I, _I, _I, _F, _U64, _P, _P]),
+    "ac_attn_self_bwd_tiled": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P,
+                                    _I, _I, _I, _I, _I, _I, _F, _U64, _P, _P, _P]),
     "ac_gather_rows": (_I, [_P, _P, _P, _L, _I, _P]),
     "ac_scatter_add_rows": (_I, [_P, _P, _P, _L, _I, _P]),
     "ac_specaug": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -95,6 +95,27 @@ def cnn14rnn_trm_config(vocab_size=4368, encoder_name="CrnnEncoder"):
     }
 
 
+def cnn14trm_trm_config(vocab_size=4368):
+    """Cnn14TransformerEncoder (frozen Cnn14 + 2-layer TransformerEncoder, d_model 256) + TransformerDecoder: the
+    reference's ``crnn_trm_encoder.Cnn14TransformerEncoder`` / ``transformer_encoder.TransformerEncoder`` wired like
+    cnn14rnn_trm.yaml, with the decoder's memory width set to the encoder's 256."""
+    return {
+        "encoder": {
+            "type": "captioning.models.crnn_trm_encoder.Cnn14TransformerEncoder",
+            "args": {"freeze_cnn": True, "freeze_cnn_bn": True},
+            "cnn": {"type": "captioning.models.cnn_encoder.Cnn14Encoder", "args": {"sample_rate": 32000}},
+            "transformer": {"type": "captioning.models.transformer_encoder.TransformerEncoder",
+                            "args": {"spec_dim": -1, "fc_feat_dim": 2048, "attn_feat_dim": 2048, "d_model": 256,
+                                     "nlayers": 2, "dropout": 0.2}},
+        },
+        "decoder": {"type": "captioning.models.transformer_decoder.TransformerDecoder",
+                    "args": {"vocab_size": vocab_size, "emb_dim": 256, "fc_emb_dim": 256, "attn_emb_dim": 256,
+                             "nlayers": 2, "dropout": 0.2}},
+        "type": "captioning.models.transformer_model.TransformerModel",
+        "args": {},
+    }
+
+
 def effb2_trm_config(vocab_size=4981):
     """The model ``Effb2TrmCaptioningModel`` builds from ``Effb2TrmConfig`` defaults (hf_wrapper.py:1115-1160):
     EfficientNetB2 encoder (16 kHz), 2-layer decoder with the word embedding tied to the classifier."""

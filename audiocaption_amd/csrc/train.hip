@@ -680,6 +680,7 @@ struct AttnP {
   float* dq; long lddq;
   float* dk; long lddk;
   float* dv; long lddv;
+  float* dws;                          // row-tiled backward only, optional: D_i per (launched sequence, head, row)
 };
 
 __global__ __launch_bounds__(256) void attn_seq_fwd_kernel(AttnP p) {
@@ -809,6 +810,151 @@ __global__ __launch_bounds__(256) void attn_seq_bwd_kernel(AttnP p) {
     for (int i = 0; i < L; ++i) a = fmaf(sp(i, j), sq[i][c], a);
     p.dk[(k0 + j) * p.lddk + h * HD + c] = a;
   }
+}
+
+// =========================================================================================================
+// The same backward tiled over rows, for sequences whose L x Tk score blocks do not fit one workgroup's LDS (the
+// Transformer encoder's T' + 1 rows at 30 s clips).  Two launches, no atomics, LDS linear in L and Tk:
+//   attn_bwd_q_kernel   one workgroup per (sequence, head, ATT_TILE query rows): K, V whole, dO and dS of its rows -> dq;
+//   attn_bwd_kv_kernel  one workgroup per (sequence, head, ATT_TILE key rows): V whole, then the query rows in chunks of
+//                       ATT_TILE (Q, dO, the chunk's dropped P and dS) -> dk, dv accumulated in registers in row order.
+// Both need D_i = sum_j dP_ij P_ij (dP with the dropout folded in, = dO_i . O_i), computed with the same code and
+// summation order as attn_seq_bwd_kernel.  With a workspace (`dws`) the q pass stores it and the kv pass reads it;
+// without one the kv pass recomputes it for all rows in each of its key tiles (same values, more work).
+// =========================================================================================================
+constexpr int ATT_TILE = 16;
+
+__device__ __forceinline__ float attn_row_dot(const float* a, const float* b) {
+  float acc = 0.f;
+#pragma unroll 16
+  for (int c = 0; c < HD; ++c) acc = fmaf(a[c], b[c], acc);
+  return acc;
+}
+
+// D_i of query row i (dO row in LDS at `dorow`, all Tk rows of V in LDS), one wave; the result on every lane.
+// Here and in the two kernels dP = rnd(dO . V * mask) is rounded before it is used: no contraction of the product into
+// the `dP - D` of dS (with a single visible key, dS must come out exactly 0, as in attn_seq_bwd_kernel).
+__device__ __forceinline__ float attn_row_D(const AttnP& p, const float* dorow, const float (*sv)[HDP], long pb, int Tk,
+                                            int lane) {
+#pragma clang fp contract(off)
+  float dot = 0.f;
+  for (int j = lane; j < Tk; j += 64) {
+    const float dp = attn_row_dot(dorow, sv[j]) * p.drop.mask((uint64_t)(pb + j));
+    dot = fmaf(dp, p.P[pb + j], dot);
+  }
+  return wave_sum(dot);
+}
+
+__global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnP p) {
+#pragma clang fp contract(off)
+  extern __shared__ float att_smem[];
+  const int QT = min(ATT_TILE, p.lmax), PP = p.tkmax + 1;
+  float (*sk)[HDP] = (float (*)[HDP])att_smem;
+  float (*sv)[HDP] = sk + p.tkmax;
+  float (*sdo)[HDP] = sv + p.tkmax;
+  float* sds_ = (float*)(sdo + QT);      // dP, then dS, of the tile's rows
+#define sds(i, j) sds_[(i) * PP + (j)]
+  const int s = p.seq0 + blockIdx.x, h = blockIdx.y, nh = gridDim.y, tid = threadIdx.x;
+  const int L = p.qlen[s], Tk = p.klen[s];
+  const int i0 = blockIdx.z * QT;
+  if (i0 >= L || L > p.lmax || Tk > p.tkmax) return;
+  const int nq = min(QT, L - i0);
+  const long q0 = p.qrow0[s] + i0, k0 = p.krow0[s];
+  for (int e = tid; e < nq * HD; e += 256) sdo[e / HD][e % HD] = p.dout[(q0 + e / HD) * p.lddo + h * HD + e % HD];
+  for (int e = tid; e < Tk * HD; e += 256) {
+    sk[e / HD][e % HD] = p.k[(k0 + e / HD) * p.ldk + h * HD + e % HD];
+    sv[e / HD][e % HD] = p.v[(k0 + e / HD) * p.ldv + h * HD + e % HD];
+  }
+  __syncthreads();
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int i = wave; i < nq; i += 4) {
+    const long pb = ((long)(s * nh + h) * p.pl + i0 + i) * p.ptk;
+    const float D = attn_row_D(p, sdo[i], sv, pb, Tk, lane);
+    if (p.dws && lane == 0) p.dws[((long)blockIdx.x * nh + h) * p.pl + i0 + i] = D;
+    for (int j = lane; j < Tk; j += 64) {
+      const float dp = attn_row_dot(sdo[i], sv[j]) * p.drop.mask((uint64_t)(pb + j));
+      sds(i, j) = p.P[pb + j] * (dp - D) * p.scale;
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < nq * HD; e += 256) {
+    const int i = e / HD, c = e % HD;
+    float a = 0.f;
+    for (int j = 0; j < Tk; ++j) a = fmaf(sds(i, j), sk[j][c], a);
+    p.dq[(q0 + i) * p.lddq + h * HD + c] = a;
+  }
+#undef sds
+}
+
+__global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnP p) {
+#pragma clang fp contract(off)
+  extern __shared__ float att_smem[];
+  const int QT = min(ATT_TILE, p.lmax), KT = min(ATT_TILE, p.tkmax), KP = KT + 1;
+  float (*sv)[HDP] = (float (*)[HDP])att_smem;
+  float (*sq)[HDP] = sv + p.tkmax;
+  float (*sdo)[HDP] = sq + QT;
+  float* spd_ = (float*)(sdo + QT);      // dropped P of (chunk rows) x (tile keys)
+  float* sds_ = spd_ + QT * KP;          // dS of the same block
+  float* sD = sds_ + QT * KP;            // D_i of the chunk rows
+#define spd(i, j) spd_[(i) * KP + (j)]
+#define sds(i, j) sds_[(i) * KP + (j)]
+  const int s = p.seq0 + blockIdx.x, h = blockIdx.y, nh = gridDim.y, tid = threadIdx.x;
+  const int L = p.qlen[s], Tk = p.klen[s];
+  const int j0 = blockIdx.z * KT;
+  if (j0 >= Tk || L > p.lmax || Tk > p.tkmax) return;
+  const int nk = min(KT, Tk - j0);
+  const long q0 = p.qrow0[s], k0 = p.krow0[s];
+  for (int e = tid; e < Tk * HD; e += 256) sv[e / HD][e % HD] = p.v[(k0 + e / HD) * p.ldv + h * HD + e % HD];
+  const int lane = tid & 63, wave = tid >> 6;
+  // thread owns outputs (key tid / 64 + 4 r, column lane) of the tile: KT * HD <= 4 * 256
+  float adv[4] = {0.f, 0.f, 0.f, 0.f}, adk[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int ic = 0; ic < L; ic += QT) {
+    const int nq = min(QT, L - ic);
+    __syncthreads();   // V is in; the previous chunk's readers are done
+    for (int e = tid; e < nq * HD; e += 256) {
+      sq[e / HD][e % HD] = p.q[(q0 + ic + e / HD) * p.ldq + h * HD + e % HD];
+      sdo[e / HD][e % HD] = p.dout[(q0 + ic + e / HD) * p.lddo + h * HD + e % HD];
+    }
+    __syncthreads();
+    if (p.dws) {          // written by attn_bwd_q_kernel, launched before this kernel on the same stream
+      for (int i = tid; i < nq; i += 256) sD[i] = p.dws[((long)blockIdx.x * nh + h) * p.pl + ic + i];
+    } else {
+      for (int i = wave; i < nq; i += 4) {
+        const float D = attn_row_D(p, sdo[i], sv, ((long)(s * nh + h) * p.pl + ic + i) * p.ptk, Tk, lane);
+        if (lane == 0) sD[i] = D;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < nq * nk; e += 256) {
+      const int i = e / nk, jj = e % nk;
+      const long pi = ((long)(s * nh + h) * p.pl + ic + i) * p.ptk + j0 + jj;
+      const float pr = p.P[pi], m = p.drop.mask((uint64_t)pi);
+      const float dp = attn_row_dot(sdo[i], sv[j0 + jj]) * m;
+      spd(i, jj) = pr * m;
+      sds(i, jj) = pr * (dp - sD[i]) * p.scale;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int jj = wave + 4 * r;
+      if (jj < nk) {
+        for (int i = 0; i < nq; ++i) {
+          adv[r] = fmaf(spd(i, jj), sdo[i][lane], adv[r]);
+          adk[r] = fmaf(sds(i, jj), sq[i][lane], adk[r]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int jj = wave + 4 * r;
+    if (jj < nk) {
+      p.dv[(k0 + j0 + jj) * p.lddv + h * HD + lane] = adv[r];
+      p.dk[(k0 + j0 + jj) * p.lddk + h * HD + lane] = adk[r];
+    }
+  }
+#undef spd
+#undef sds
 }
 
 // ---- row gather / scatter-add through an index list (classifier on the last position of each pass) ---------
@@ -1449,6 +1595,48 @@ int ac_attn_seq_bwd(const float* q, long ldq, const float* k, long ldk, const fl
   static AcLdsAttr allowed;   // per device
   if (attn_allow_lds((const void*)attn_seq_bwd_kernel, &allowed) != AC_OK) return AC_ERR_LAUNCH;
   hipLaunchKernelGGL(attn_seq_bwd_kernel, dim3(nseq, nhead), dim3(256), lds, (hipStream_t)stream, p);
+  return ac_check_launch();
+}
+
+// LDS of the two row-tiled backward kernels (attn_bwd_q_kernel, attn_bwd_kv_kernel): linear in lmax and tkmax, and
+// within ac_attn_seq_fwd's own carve-up whenever that one fits (the tiles are at most lmax / tkmax rows)
+static size_t attn_tiled_q_lds(int lmax, int tkmax) {
+  const size_t qt = lmax < ATT_TILE ? lmax : ATT_TILE;
+  return ((2 * (size_t)tkmax + qt) * HDP + qt * (tkmax + 1)) * sizeof(float);
+}
+static size_t attn_tiled_kv_lds(int lmax, int tkmax) {
+  const size_t qt = lmax < ATT_TILE ? lmax : ATT_TILE, kt = tkmax < ATT_TILE ? tkmax : ATT_TILE;
+  return (((size_t)tkmax + 2 * qt) * HDP + 2 * qt * (kt + 1) + qt) * sizeof(float);
+}
+
+int ac_attn_self_bwd_tiled(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* P,
+                           int pl, int ptk, const float* dout, long lddo, float* dq, long lddq, float* dk, long lddk,
+                           float* dv, long lddv, const int* qrow0, const int* qlen, const int* krow0, const int* klen,
+                           int seq0, int nseq, int nhead, int head_dim, int lmax, int tkmax, float drop_p,
+                           unsigned long long seed, const unsigned long long* seed_dev, float* d_ws, void* stream) {
+  if (!q || !k || !v || !P || !dout || !dq || !dk || !dv || !qrow0 || !qlen || !krow0 || !klen ||
+      !attn_args_ok(nseq, nhead, head_dim, lmax, tkmax, pl, ptk))
+    return AC_ERR_ARG;
+  AttnP p = {};
+  p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv;
+  p.P = const_cast<float*>(P); p.pl = pl; p.ptk = ptk; p.qrow0 = qrow0; p.qlen = qlen; p.krow0 = krow0; p.klen = klen;
+  p.seq0 = seq0;
+  p.scale = 1.0f / sqrtf((float)head_dim);
+  p.drop = make_drop(drop_p, seed, seed_dev);
+  p.dout = dout; p.lddo = lddo; p.dq = dq; p.lddq = lddq; p.dk = dk; p.lddk = lddk; p.dv = dv; p.lddv = lddv;
+  p.dws = d_ws;
+  p.lmax = lmax; p.tkmax = tkmax;
+  const size_t lq = attn_tiled_q_lds(lmax, tkmax), lkv = attn_tiled_kv_lds(lmax, tkmax);
+  if (lq > (size_t)ATT_LDS_MAX || lkv > (size_t)ATT_LDS_MAX) return AC_ERR_ARG;
+  static AcLdsAttr allowed_q, allowed_kv;   // per device
+  if (attn_allow_lds((const void*)attn_bwd_q_kernel, &allowed_q) != AC_OK ||
+      attn_allow_lds((const void*)attn_bwd_kv_kernel, &allowed_kv) != AC_OK)
+    return AC_ERR_LAUNCH;
+  const int qt = lmax < ATT_TILE ? lmax : ATT_TILE, kt = tkmax < ATT_TILE ? tkmax : ATT_TILE;
+  hipLaunchKernelGGL(attn_bwd_q_kernel, dim3(nseq, nhead, (lmax + qt - 1) / qt), dim3(256), lq, (hipStream_t)stream, p);
+  int rc = ac_check_launch();
+  if (rc != AC_OK) return rc;
+  hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3(nseq, nhead, (tkmax + kt - 1) / kt), dim3(256), lkv, (hipStream_t)stream, p);
   return ac_check_launch();
 }
 

@@ -175,6 +175,15 @@ def cnn14rnn_trm_state(vocab_size=4368, seed=BASE_SEED):
     return out
 
 
+def cnn14trm_trm_state(vocab_size=4368, seed=BASE_SEED):
+    """Full state dict of the Cnn14-TransformerEncoder captioner (config.cnn14trm_trm_config)."""
+    out = {}
+    out.update(cnn14_state("encoder.cnn.", seed))
+    out.update(trm_encoder_state("encoder.trm.", 2048, 256, 2, 1024, seed))
+    out.update(decoder_state("decoder.", vocab_size, 256, 256, 2, 1024, seed))
+    return out
+
+
 # (repeats, kernel, stride, expand, in, out) of EfficientNet-B0 (Tan & Le 2019, table 1); B2 scales width by 1.1 and
 # depth by 1.2.  The reference spells the same construction out in eff_latent_encoder.py:74-186.
 _EFFNET_B0 = [(1, 3, 1, 1, 32, 16), (2, 3, 2, 6, 16, 24), (2, 5, 2, 6, 24, 40), (3, 3, 2, 6, 40, 80),

@@ -1,4 +1,6 @@
-"""Training step of the Cnn14Rnn-Trm captioner on the MI355X path.
+"""Training step of the Cnn14Rnn-Trm captioner on the MI355X path, and of the
+Cnn14-TransformerEncoder captioner (the bi-GRU replaced by crnn_trm_encoder.Cnn14TransformerEncoder's 2-layer
+TransformerEncoder: ``_launch_forward_trm`` / ``_launch_backward_trm``; everything else is shared).
 
 What the reference does per iteration (run.py:77-148): ``model.train()``; ``output = model(input_dict)`` with
 ``mode="train"`` - the frozen Cnn14 (dropout active, BatchNorm in eval mode), the 3-layer bi-GRU and the
@@ -35,6 +37,12 @@ OP_GRU_LAYER = 10
 OP_MEM = 20
 OP_EMB_A, OP_EMB_B = 21, 22
 OP_LAYER = 30
+# Transformer encoder (Cnn14TransformerEncoder): attn_proj dropout, then per layer l
+# OP_ENC_LAYER + 10 * l + {0: self-attention P, 1: dropout1, 2: feed-forward dropout, 3: dropout2}
+OP_ENC_PROJ = 100
+OP_ENC_LAYER = 110
+# longest encoder sequence (T' + 1 rows) whose self-attention forward fits one workgroup (csrc/train.hip ac_attn_seq_fwd)
+ENC_LMAX = 126
 
 D = 256
 H = 256
@@ -55,12 +63,16 @@ class FlatParams:
     ([W_ih fwd; W_ih rev] is one (2*3H, In) matrix)."""
 
     def __init__(self, model):
-        rnn = model.encoder.rnn.network
-        names = []
-        for l in range(rnn.num_layers):
-            for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
-                names += [f"encoder.rnn.network.{kind}_l{l}", f"encoder.rnn.network.{kind}_l{l}_reverse"]
         named = dict(model.named_parameters())
+        names = []
+        if hasattr(model.encoder, "rnn"):
+            rnn = model.encoder.rnn.network
+            for l in range(rnn.num_layers):
+                for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                    names += [f"encoder.rnn.network.{kind}_l{l}", f"encoder.rnn.network.{kind}_l{l}_reverse"]
+        else:
+            # Transformer encoder (Cnn14TransformerEncoder): attn_proj, the layers, cls_token - before the decoder
+            names = [k for k in named if k.startswith("encoder.trm.")]
         for k, p in named.items():
             if k.startswith("decoder.") and p.requires_grad:
                 names.append(k)
@@ -71,7 +83,8 @@ class FlatParams:
         for k, p in named.items():
             if p.requires_grad and k not in names:
                 raise NotImplementedError(
-                    f"TrainEngine: {k} requires grad, but only the GRU and the decoder are trainable on the HIP path "
+                    f"TrainEngine: {k} requires grad, but only the temporal encoder (GRU or Transformer) and the decoder "
+                    "are trainable on the HIP path "
                     "(the reference configs freeze the Cnn14: freeze_cnn / freeze_cnn_bn, cnn14rnn_trm.yaml:11-13)")
         self.names = names
         self.params = [named[k] for k in names]
@@ -91,8 +104,8 @@ class FlatParams:
                 p.data = v
                 self.grad_views.append(self.grad[o:o + p.numel()].view(p.shape))
         self.index = {k: i for i, k in enumerate(names)}
-        # the GRU tensors come first, the decoder's after them: [0, decoder_offset) is final only after the GRU's
-        # backward through time, [decoder_offset, total) as soon as the decoder's backward is done
+        # the encoder's (GRU or Transformer) tensors come first, the decoder's after them: [0, decoder_offset) is final
+        # only after the encoder's backward, [decoder_offset, total) as soon as the decoder's backward is done
         self.decoder_offset = next((o for k, o in zip(names, self.offsets) if k.startswith("decoder.")), off)
         # tied parameters (``tie_weights=True``: decoder.classifier.weight IS decoder.word_embedding.weight) appear once
         # in named_parameters(); the other name resolves to the same slot, so both uses accumulate into one gradient
@@ -273,14 +286,29 @@ class _Ws:
 class TrainEngine:
 
     def __init__(self, model, seed=0):
-        from .crnn_trm_encoder import CrnnEncoder
-        if not isinstance(model.encoder, CrnnEncoder) or not model.encoder.freeze_cnn_bn:
+        from .crnn_trm_encoder import Cnn14TransformerEncoder, CrnnEncoder
+        enc = model.encoder
+        if isinstance(enc, Cnn14TransformerEncoder) and enc.freeze_cnn_bn:
+            self.enc_kind = "trm"
+        elif isinstance(enc, CrnnEncoder) and enc.freeze_cnn_bn:
+            self.enc_kind = "rnn"
+        else:
             raise NotImplementedError(
-                "TrainEngine: built for the reference's training recipe, CrnnEncoder(freeze_cnn=True, "
-                "freeze_cnn_bn=True) (cnn14rnn_trm.yaml:9-13); the backward through the Cnn14 is not built")
+                "TrainEngine: built for the reference's training recipe, CrnnEncoder or Cnn14TransformerEncoder with "
+                "freeze_cnn=True, freeze_cnn_bn=True (cnn14rnn_trm.yaml:9-13); the backward through the Cnn14 is not built")
         dec = model.decoder
-        if dec.d_model != D or dec.nhead * 64 != D or model.encoder.rnn.hidden_size != H:
-            raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 / GRU hidden 256 only")
+        if self.enc_kind == "trm":
+            trm = enc.trm
+            if dec.d_model != D or dec.nhead * 64 != D or trm.d_model != D or trm.nhead * 64 != D:
+                raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 (decoder and TransformerEncoder) only")
+            self.enc_width = trm.d_model
+            if dec.attn_emb_dim != self.enc_width:
+                raise NotImplementedError(f"TrainEngine: decoder attn_emb_dim {dec.attn_emb_dim} != TransformerEncoder "
+                                          f"d_model {self.enc_width}")
+        else:
+            if dec.d_model != D or dec.nhead * 64 != D or model.encoder.rnn.hidden_size != H:
+                raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 / GRU hidden 256 only")
+            self.enc_width = 2 * H
         self.model = model
         self.lib = _lib.load()
         self.flat = None
@@ -471,17 +499,29 @@ class TrainEngine:
         else:
             Tq = hook.shape[1]
         p_dec = float(dec.in_dropout.p)
-        p_rnn = float(enc.rnn.network.dropout)
+        trm = self.enc_kind == "trm"
+        if trm:
+            if Tq + 1 > ENC_LMAX:
+                raise ValueError(f"TrainEngine: {Tq} Cnn14 frames per clip; the Transformer encoder's self-attention is "
+                                 f"built for at most {ENC_LMAX} rows (T' + 1), i.e. clips up to ~40 s")
+            # dropout of every encoder site: attn_proj, then per layer (P, dropout1, feed-forward, dropout2)
+            p_rnn = (float(enc.trm.attn_proj[2].p),) + tuple(
+                (float(ly.self_attn.dropout), float(ly.dropout1.p), float(ly.dropout.p), float(ly.dropout2.p))
+                for ly in enc.trm.model.layers)
+        else:
+            p_rnn = float(enc.rnn.network.dropout)
         p_cnn = 0.2 if enc.cnn.training else 0.0
+        Tm = Tq + 1 if trm else Tq      # decoder memory rows per clip (the Transformer encoder prepends cls_token)
         key = (dev, N, Tc, tuple(wav.shape) if hook is None else ("hook", Tq), teacher_forcing, p_dec, p_rnn, p_cnn,
                model.start_idx, model.pad_idx, specaug and hook is None)
         st = self._states.get(key)
         if st is None:
-            lay = self._layout(N, T, Tq, teacher_forcing, dev)
+            lay = self._layout(N, T, Tm, teacher_forcing, dev)
             S = lay["S"]
             if self._wsg is None or self._wsg.device != dev:
                 self._wsg = _Ws(dev)
-            st = {"key": key, "ws": self._wsg, "lay": lay, "N": N, "T": T, "Tc": Tc, "Tq": Tq, "teacher_forcing": teacher_forcing,
+            st = {"key": key, "ws": self._wsg, "lay": lay, "N": N, "T": T, "Tc": Tc, "Tq": Tq, "Tm": Tm,
+                  "teacher_forcing": teacher_forcing,
                   "p_dec": p_dec, "p_rnn": p_rnn, "p_cnn": p_cnn, "graphs": {}, "steps": 0,
                   "wav": torch.empty_like(wav, dtype=torch.float32) if hook is None else None,
                   "cnn_attn_in": torch.empty(N, Tq, 2048, device=dev) if hook is not None else None,
@@ -521,7 +561,8 @@ class TrainEngine:
         if "cap_len" in input_dict:
             h[2 + N:2 + 2 * N] = (torch.as_tensor(input_dict["cap_len"]).to(torch.int32) - 1).clamp(max=T)
         h[2 + 2 * N:2 + 2 * N + T] = torch.as_tensor(use_cap, dtype=torch.int32)
-        h[2 + 2 * N + max(T, 1):] = lens.to(torch.int32).repeat(S // N)
+        mlens = lens + 1 if trm else lens      # valid memory rows per clip (cls + frames)
+        h[2 + 2 * N + max(T, 1):] = mlens.to(torch.int32).repeat(S // N)
         st["small"].copy_(h, non_blocking=True)
         ev.record()
         if st["specaug"] is not None:
@@ -537,7 +578,7 @@ class TrainEngine:
         else:
             st["cnn_attn_in"].copy_(hook, non_blocking=True)
         st["cap"].copy_(cap, non_blocking=True)
-        st["lens_host"] = lens
+        st["lens_host"] = mlens
         return st
 
     # ---- forward launches (no host synchronisation, capturable) ---------------------------------------------------
@@ -556,9 +597,7 @@ class TrainEngine:
         lens_p, ucap, mvalid = small + 8, small + 4 * (2 + 2 * N), small + 4 * (2 + 2 * N + max(T, 1))
         R, S, passes = lay["R"], lay["S"], lay["passes"]
         NP = len(passes)
-        Tm = Tq
-        B = N
-        rows_g = B * Tq
+        Tm = st["Tm"]
         # frozen Cnn14 (train mode: dropout after every block)
         if st["cnn_attn_in"] is not None:
             cnn_attn = st["cnn_attn_in"]
@@ -566,44 +605,12 @@ class TrainEngine:
             cnn_attn = enc.cnn.encode(st["wav"], dropout=(p_cnn, OP_CNN_BLOCK, self._seed_ptr) if p_cnn > 0 else None,
                                       specaug=st["specaug"], train=True)
         st["cnn_attn"] = cnn_attn
-        Cin = cnn_attn.shape[2]
 
-        # ---- GRU, saving the gates -------------------------------------------------------------------
-        nl = enc.rnn.num_layers
-        x_in = cnn_attn.data_ptr()
-        in_dim = Cin
-        gru = []
-        pre = "encoder.rnn.network."
-        for l in range(nl):
-            w_ih, w_hh = fp.p(f"{pre}weight_ih_l{l}"), fp.p(f"{pre}weight_hh_l{l}")
-            b_ih, b_hh = fp.p(f"{pre}bias_ih_l{l}"), fp.p(f"{pre}bias_hh_l{l}")
-            gx = ws.f(f"gx{l}", rows_g, 6 * H)
-            self._lin(s, x_in, w_ih, b_ih, gx, rows_g, 6 * H, in_dim)
-            out = ws.f(f"gru_out{l}", rows_g, 2 * H)
-            save = ws.f(f"gru_save{l}", rows_g, 2 * 4 * H)
-            if self.gru_algo == "split":
-                # four workgroups per (clip, direction), W_hh register resident, straight from the flat parameter buffer
-                xch = ws.f("gru_xch", (lib.ac_gru_split_workspace_bytes(B) + 3) // 4)
-                if not st.get("gru_xch_zeroed"):
-                    ws.tensor("gru_xch")[:1].zero_()       # the sticky error word (first word of the workspace)
-                    st["gru_xch_zeroed"] = True
-                check(lib.ac_gru_layer_split(gx, w_hh, b_hh, lens_p, out, save, xch, B, Tq, H, s), "ac_gru_layer_split")
-            else:
-                whhT = ws.f(f"whhT{l}", 2 * 3 * H * H)
-                check(lib.ac_gru_pack_whh(w_hh, whhT, H, s), "ac_gru_pack_whh")
-                check(lib.ac_gru_layer_train(gx, whhT, b_hh, lens_p, out, save, B, Tq, H, s), "ac_gru_layer_train")
-            nxt = out
-            if l < nl - 1 and p_rnn > 0:
-                nxt = ws.f(f"gru_drop{l}", rows_g, 2 * H)
-                check(lib.ac_dropout(out, nxt, rows_g * 2 * H, p_rnn, OP_GRU_LAYER + l, self._seed_ptr, 0, s),
-                      "ac_dropout")
-            gru.append({"x": x_in, "in_dim": in_dim, "out": out})
-            x_in, in_dim = nxt, 2 * H
-        # attn_emb (B, Tq, 512).  The reference truncates it to the longest clip (pad_packed_sequence); the frames
-        # beyond a clip's length are zero and masked as keys, so keeping all Tq frames changes no result and keeps
-        # the shapes static.
-        attn_emb = x_in
-        A = 2 * H
+        if self.enc_kind == "trm":
+            attn_emb, gru = self._launch_forward_trm(st, cnn_attn), []
+        else:
+            gru, attn_emb = self._launch_forward_gru(st, cnn_attn)
+        A = self.enc_width
 
         # ---- decoder: audio memory (shared by all passes up to its dropout mask) ---------------------
         dp = "decoder."
@@ -660,6 +667,126 @@ class TrainEngine:
             if free:
                 for t in st["free_ts"]:
                     self._decoder_passes(st, t, t + 1, ucap)
+
+    def _enc_layout(self, st):
+        """Index tables of the Transformer encoder's row space (host uploads: built by the first, eager, iteration of a
+        shape).  Clip n owns rows n*(T'+1) .. : its cls row, then its T' frames."""
+        el = st.get("enc_lay")
+        if el is None:
+            N, Tq, L = st["N"], st["Tq"], st["Tm"]
+            dev = st["cap"].device
+            t = torch.arange(L, dtype=torch.int32)
+            # x0 row n*L + t <- [cls_token | attn_proj rows] row 0 (t = 0) or 1 + n*T' + t - 1
+            x0_src = torch.where(t[None, :] == 0, torch.zeros(1, dtype=torch.int32),
+                                 torch.arange(N, dtype=torch.int32)[:, None] * Tq + t[None, :]).reshape(-1)
+            proj_src = (torch.arange(N, dtype=torch.int32)[:, None] * L + 1 + torch.arange(Tq, dtype=torch.int32)[None, :])
+            el = st["enc_lay"] = {k: v.to(dev) for k, v in (
+                ("row0", torch.arange(N, dtype=torch.int32) * L), ("len", torch.full((N,), L, dtype=torch.int32)),
+                ("x0_src", x0_src), ("proj_src", proj_src.reshape(-1)), ("zero", torch.zeros(1, dtype=torch.int32)))}
+        return {k: v.data_ptr() for k, v in el.items()}
+
+    def _launch_forward_trm(self, st, cnn_attn):
+        """The Transformer encoder in train mode (reference transformer_encoder.py:95-116, post-LN
+        nn.TransformerEncoderLayer): attn_proj (Linear, ReLU, dropout, LayerNorm) over the N*T' frame rows, cls_token
+        prepended to every clip, then the layers over N*(T'+1) rows - self-attention with the key padding of
+        ``attn_len + 1`` and dropout on P, dropout1 + add + norm1, linear1 + ReLU + dropout, linear2, dropout2 + add +
+        norm2.  Keeps what the backward reads; returns the address of the output (the decoder memory, Tm = T' + 1)."""
+        lib, fp, trm = self.lib, self.flat, self.model.encoder.trm
+        s = _lib.stream()
+        ws = st["ws"]
+        N, T, Tq, L = st["N"], st["T"], st["Tq"], st["Tm"]
+        p = st["p_rnn"]
+        d, Fe, nh = D, trm.dim_feedforward, trm.nhead
+        rows_f, Re = N * Tq, N * L
+        el = self._enc_layout(st)
+        kvalid = st["small"].data_ptr() + 4 * (2 + 2 * N + max(T, 1))    # lens + 1 (the first N words of mvalid)
+        pre = "encoder.trm."
+        Cin = cnn_attn.shape[2]
+        a = ws.f("enc_a", rows_f, d)
+        self._lin(s, cnn_attn.data_ptr(), fp.p(pre + "attn_proj.0.weight"), fp.p(pre + "attn_proj.0.bias"), a, rows_f, d,
+                  Cin, relu=1)
+        ppre = ws.f("enc_ppre", rows_f, d)
+        proj = ws.f("enc_proj", 1 + rows_f, d)          # row 0: cls_token, then the frame rows
+        ln = trm.attn_proj[3]
+        check(lib.ac_dropadd_ln_fwd(a, None, fp.p(pre + "attn_proj.3.weight"), fp.p(pre + "attn_proj.3.bias"), ppre,
+                                    proj + 4 * d, 0, rows_f, 0, d, p[0], OP_ENC_PROJ, self._seed_ptr, float(ln.eps), s),
+              "ac_dropadd_ln_fwd(enc proj)")
+        check(lib.ac_gather_rows(fp.p(pre + "cls_token"), el["zero"], proj, 1, d, s), "ac_gather_rows(cls)")
+        x = ws.f("enc_x0", Re, d)
+        check(lib.ac_gather_rows(proj, el["x0_src"], x, Re, d, s), "ac_gather_rows(enc x0)")
+        layers = []
+        for l, ly in enumerate(trm.model.layers):
+            lp = f"{pre}model.layers.{l}."
+            op = OP_ENC_LAYER + 10 * l
+            pa, pd1, pf, pd2 = p[1 + l]
+            b = {k: ws.f(f"enc_{k}{l}", Re, w) for k, w in (("qkv", 3 * d), ("ctx", d), ("sa", d), ("pre1", d), ("x1", d),
+                                                            ("hdn", Fe), ("ff", d), ("pre2", d), ("x2", d))}
+            b["x"], b["P"] = x, ws.f(f"enc_P{l}", N * nh * L * L)
+            qkv = b["qkv"]
+            self._lin(s, x, fp.p(lp + "self_attn.in_proj_weight"), fp.p(lp + "self_attn.in_proj_bias"), qkv, Re, 3 * d, d)
+            check(lib.ac_attn_seq_fwd(qkv, 3 * d, qkv + 4 * d, 3 * d, qkv + 8 * d, 3 * d, b["ctx"], d, b["P"], L, L,
+                                      el["row0"], el["len"], el["row0"], el["len"], kvalid, None, 0, 0, 0, N, nh, 64, L, L,
+                                      pa, op + 0, self._seed_ptr, s), "ac_attn_seq_fwd(enc)")
+            self._lin(s, b["ctx"], fp.p(lp + "self_attn.out_proj.weight"), fp.p(lp + "self_attn.out_proj.bias"), b["sa"],
+                      Re, d, d)
+            check(lib.ac_dropadd_ln_fwd(b["sa"], x, fp.p(lp + "norm1.weight"), fp.p(lp + "norm1.bias"), b["pre1"], b["x1"],
+                                        0, Re, 0, d, pd1, op + 1, self._seed_ptr, float(ly.norm1.eps), s), "enc ln1")
+            self._lin(s, b["x1"], fp.p(lp + "linear1.weight"), fp.p(lp + "linear1.bias"), b["hdn"], Re, Fe, d, relu=1,
+                      drop_p=pf, seed=op + 2, row0=0)
+            self._lin(s, b["hdn"], fp.p(lp + "linear2.weight"), fp.p(lp + "linear2.bias"), b["ff"], Re, d, Fe)
+            check(lib.ac_dropadd_ln_fwd(b["ff"], b["x1"], fp.p(lp + "norm2.weight"), fp.p(lp + "norm2.bias"), b["pre2"],
+                                        b["x2"], 0, Re, 0, d, pd2, op + 3, self._seed_ptr, float(ly.norm2.eps), s), "enc ln2")
+            layers.append(b)
+            x = b["x2"]
+        st["enc"] = {"a": a, "ppre": ppre, "layers": layers, "out": x}
+        return x
+
+    def _launch_forward_gru(self, st, cnn_attn):
+        """The 3-layer bi-GRU over the Cnn14 frames, saving the gates; returns (per-layer records, attn_emb address)."""
+        lib, fp, enc = self.lib, self.flat, self.model.encoder
+        s = _lib.stream()
+        ws = st["ws"]
+        B, Tq, p_rnn = st["N"], st["Tq"], st["p_rnn"]
+        lens_p = st["small"].data_ptr() + 8
+        rows_g = B * Tq
+        Cin = cnn_attn.shape[2]
+
+        # ---- GRU, saving the gates -------------------------------------------------------------------
+        nl = enc.rnn.num_layers
+        x_in = cnn_attn.data_ptr()
+        in_dim = Cin
+        gru = []
+        pre = "encoder.rnn.network."
+        for l in range(nl):
+            w_ih, w_hh = fp.p(f"{pre}weight_ih_l{l}"), fp.p(f"{pre}weight_hh_l{l}")
+            b_ih, b_hh = fp.p(f"{pre}bias_ih_l{l}"), fp.p(f"{pre}bias_hh_l{l}")
+            gx = ws.f(f"gx{l}", rows_g, 6 * H)
+            self._lin(s, x_in, w_ih, b_ih, gx, rows_g, 6 * H, in_dim)
+            out = ws.f(f"gru_out{l}", rows_g, 2 * H)
+            save = ws.f(f"gru_save{l}", rows_g, 2 * 4 * H)
+            if self.gru_algo == "split":
+                # four workgroups per (clip, direction), W_hh register resident, straight from the flat parameter buffer
+                xch = ws.f("gru_xch", (lib.ac_gru_split_workspace_bytes(B) + 3) // 4)
+                if not st.get("gru_xch_zeroed"):
+                    ws.tensor("gru_xch")[:1].zero_()       # the sticky error word (first word of the workspace)
+                    st["gru_xch_zeroed"] = True
+                check(lib.ac_gru_layer_split(gx, w_hh, b_hh, lens_p, out, save, xch, B, Tq, H, s), "ac_gru_layer_split")
+            else:
+                whhT = ws.f(f"whhT{l}", 2 * 3 * H * H)
+                check(lib.ac_gru_pack_whh(w_hh, whhT, H, s), "ac_gru_pack_whh")
+                check(lib.ac_gru_layer_train(gx, whhT, b_hh, lens_p, out, save, B, Tq, H, s), "ac_gru_layer_train")
+            nxt = out
+            if l < nl - 1 and p_rnn > 0:
+                nxt = ws.f(f"gru_drop{l}", rows_g, 2 * H)
+                check(lib.ac_dropout(out, nxt, rows_g * 2 * H, p_rnn, OP_GRU_LAYER + l, self._seed_ptr, 0, s),
+                      "ac_dropout")
+            gru.append({"x": x_in, "in_dim": in_dim, "out": out})
+            x_in, in_dim = nxt, 2 * H
+        # attn_emb (B, Tq, 512).  The reference truncates it to the longest clip (pad_packed_sequence); the frames
+        # beyond a clip's length are zero and masked as keys, so keeping all Tq frames changes no result and keeps
+        # the shapes static.
+        attn_emb = x_in
+        return gru, attn_emb
 
     def _decoder_passes(self, st, ta, tb, ucap_ptr):
         """Decoder passes [ta, tb) of the row space as one batch: prefixes (teacher tokens where ``ucap_ptr[t]`` is set,
@@ -773,17 +900,17 @@ class TrainEngine:
 
     def _launch_backward(self, sv, dl, part="all"):
         """``part``: "all", or the two halves of it - "head" (classifier, decoder layers, audio memory, attn_proj: every
-        decoder gradient is final after it, and d(loss)/d(GRU output) is in the workspace) and "gru" (the backward through
-        time of the three GRU layers) - so that the all-reduce of the decoder's gradients can run under the GRU's."""
+        decoder gradient is final after it, and d(loss)/d(encoder output) is in the workspace) and "gru" (the encoder's
+        backward: through time of the three GRU layers, or through the Transformer encoder) - so that the all-reduce of the decoder's gradients can run under the GRU's."""
         if part == "gru":
-            return self._launch_backward_gru(sv)
+            return self._launch_backward_enc(sv)
         model, lib, fp = self.model, self.lib, self.flat
         enc, dec = model.encoder, model.decoder
         s = _lib.stream()
         self._phase = "backward"
         ws, lay = sv["ws"], sv["lay"]
         N, T, Tq, V, F = sv["N"], sv["T"], sv["Tq"], sv["V"], sv["F"]
-        B, Tm = N, Tq
+        B, Tm = N, sv["Tm"]
         p_dec, p_rnn = sv["p_dec"], sv["p_rnn"]
         R, S = lay["R"], lay["S"]
         NP = len(lay["passes"])
@@ -890,16 +1017,95 @@ class TrainEngine:
                                     OP_MEM, self._seed_ptr, 1e-5, s), "mem ln bwd")
         da = ws.f("da", rows_m, D)
         check(lib.ac_sum_replicas(da_rep, da, rows_m * D, NP, s), "ac_sum_replicas")
-        A = 2 * H
+        A = self.enc_width
         s2 = side.fork()
         self._lin_dw(s2, da, D, sv["attn_emb"], A, fp.g(dp + "attn_proj.0.weight"), rows_m, D, A)
         self._colsum(s2, da, D, fp.g(dp + "attn_proj.0.bias"), rows_m, D)
-        rows_g = B * Tq
-        dout = ws.f("gru_dout", rows_g, A)
+        # d(loss)/d(encoder output): the GRU's (B*T' rows) or the Transformer encoder's (B*(T'+1) rows)
+        dout = ws.f("enc_dout", rows_m, A) if self.enc_kind == "trm" else ws.f("gru_dout", B * Tq, A)
         self._lin_dx(s, da, fp.p(dp + "attn_proj.0.weight"), dout, rows_m, D, A)
         if part == "all":
-            self._launch_backward_gru(sv)
+            self._launch_backward_enc(sv)
         side.join()   # every decoder gradient is final (the all-reduce of part "head" reads them next)
+
+    def _launch_backward_trm(self, sv):
+        """Backward of the Transformer encoder, from d(loss)/d(its output) (``enc_dout``, written by the decoder's
+        backward) into the encoder's slice of the flat gradient buffer.  The Cnn14 is frozen: attn_proj.0 gets its
+        weight gradients only, no input gradient."""
+        lib, fp, trm = self.lib, self.flat, self.model.encoder.trm
+        s = _lib.stream()
+        self._phase = "backward"
+        ws = sv["ws"]
+        N, Tq, L = sv["N"], sv["Tq"], sv["Tm"]
+        p = sv["p_rnn"]
+        d, Fe, nh = D, trm.dim_feedforward, trm.nhead
+        rows_f, Re = N * Tq, N * L
+        self._seed_ptr = sv["small"].data_ptr()
+        el = self._enc_layout(sv)
+        e = sv["enc"]
+        side = self._side = getattr(self, "_side", None) or _SideStream()
+        pre = "encoder.trm."
+        dx, dres = ws.f("enc_dout", Re, d), ws.f("enc_dres", Re, d)
+        dsub, dctx = ws.f("enc_dsub", Re, d), ws.f("enc_dctx", Re, d)
+        dhdn, dqkv = ws.f("enc_dhdn", Re, Fe), ws.f("enc_dqkv", Re, 3 * d)
+        for l in reversed(range(len(trm.model.layers))):
+            ly = trm.model.layers[l]
+            lp = f"{pre}model.layers.{l}."
+            op = OP_ENC_LAYER + 10 * l
+            pa, pd1, pf, pd2 = p[1 + l]
+            b = e["layers"][l]
+            # norm2 / feed-forward
+            side.join()   # dsub / dhdn / dqkv are about to be written again
+            check(lib.ac_dropadd_ln_bwd(dx, b["pre2"], fp.p(lp + "norm2.weight"), dsub, dres, 0, None, 0,
+                                        fp.g(lp + "norm2.weight"), fp.g(lp + "norm2.bias"), Re, d, pd2, op + 3,
+                                        self._seed_ptr, float(ly.norm2.eps), s), "enc ln2 bwd")
+            s2 = side.fork()
+            self._lin_dw(s2, dsub, d, b["hdn"], Fe, fp.g(lp + "linear2.weight"), Re, d, Fe)
+            self._colsum(s2, dsub, d, fp.g(lp + "linear2.bias"), Re, d)
+            self._lin_dx(s, dsub, fp.p(lp + "linear2.weight"), dhdn, Re, d, Fe)
+            check(lib.ac_mask_pos_scale(dhdn, b["hdn"], Re * Fe, 1.0 / (1.0 - pf) if pf > 0 else 1.0, s),
+                  "ac_mask_pos_scale")
+            s2 = side.fork()
+            self._lin_dw(s2, dhdn, Fe, b["x1"], d, fp.g(lp + "linear1.weight"), Re, Fe, d)
+            self._colsum(s2, dhdn, Fe, fp.g(lp + "linear1.bias"), Re, Fe)
+            self._lin_dx(s, dhdn, fp.p(lp + "linear1.weight"), dres, Re, Fe, d, beta=1.0)
+            dx, dres = dres, dx                                   # dx = d(x1)
+            # norm1 / self-attention
+            side.join()
+            check(lib.ac_dropadd_ln_bwd(dx, b["pre1"], fp.p(lp + "norm1.weight"), dsub, dres, 0, None, 0,
+                                        fp.g(lp + "norm1.weight"), fp.g(lp + "norm1.bias"), Re, d, pd1, op + 1,
+                                        self._seed_ptr, float(ly.norm1.eps), s), "enc ln1 bwd")
+            s2 = side.fork()
+            self._lin_dw(s2, dsub, d, b["ctx"], d, fp.g(lp + "self_attn.out_proj.weight"), Re, d, d)
+            self._colsum(s2, dsub, d, fp.g(lp + "self_attn.out_proj.bias"), Re, d)
+            self._lin_dx(s, dsub, fp.p(lp + "self_attn.out_proj.weight"), dctx, Re, d, d)
+            qkv = b["qkv"]
+            check(lib.ac_attn_self_bwd_tiled(qkv, 3 * d, qkv + 4 * d, 3 * d, qkv + 8 * d, 3 * d, b["P"], L, L, dctx, d,
+                                             dqkv, 3 * d, dqkv + 4 * d, 3 * d, dqkv + 8 * d, 3 * d, el["row0"], el["len"],
+                                             el["row0"], el["len"], 0, N, nh, 64, L, L, pa, op + 0, self._seed_ptr,
+                                             ws.f("enc_attn_D", N * nh * L), s),
+                  "ac_attn_self_bwd_tiled")
+            s2 = side.fork()
+            self._lin_dw(s2, dqkv, 3 * d, b["x"], d, fp.g(lp + "self_attn.in_proj_weight"), Re, 3 * d, d)
+            self._colsum(s2, dqkv, 3 * d, fp.g(lp + "self_attn.in_proj_bias"), Re, 3 * d)
+            self._lin_dx(s, dqkv, fp.p(lp + "self_attn.in_proj_weight"), dres, Re, 3 * d, d, beta=1.0)
+            dx, dres = dres, dx                                   # dx = d(layer input)
+        # cls_token: row 0 of every clip; the frame rows go back through attn_proj's LayerNorm, dropout and ReLU
+        self._colsum(s, dx, L * d, fp.g(pre + "cls_token"), N, d)
+        dproj, da = ws.f("enc_dproj", rows_f, d), ws.f("enc_da", rows_f, d)
+        check(lib.ac_gather_rows(dx, el["proj_src"], dproj, rows_f, d, s), "ac_gather_rows(enc dproj)")
+        check(lib.ac_dropadd_ln_bwd(dproj, e["ppre"], fp.p(pre + "attn_proj.3.weight"), da, None, 0, e["a"], 0,
+                                    fp.g(pre + "attn_proj.3.weight"), fp.g(pre + "attn_proj.3.bias"), rows_f, d, p[0],
+                                    OP_ENC_PROJ, self._seed_ptr, float(trm.attn_proj[3].eps), s), "enc proj ln bwd")
+        cnn_attn = sv["cnn_attn"]
+        s2 = side.fork()
+        self._lin_dw(s2, da, d, cnn_attn.data_ptr(), cnn_attn.shape[2], fp.g(pre + "attn_proj.0.weight"), rows_f, d,
+                     cnn_attn.shape[2])
+        self._colsum(s2, da, d, fp.g(pre + "attn_proj.0.bias"), rows_f, d)
+        side.join()
+
+    def _launch_backward_enc(self, sv):
+        return self._launch_backward_trm(sv) if self.enc_kind == "trm" else self._launch_backward_gru(sv)
 
     def _launch_backward_gru(self, sv):
         model, lib, fp = self.model, self.lib, self.flat

@@ -40,7 +40,9 @@ class TransformerEncoder(nn.Module):
 
     def forward(self, input_dict):
         if self.training:
-            raise NotImplementedError("TransformerEncoder (HIP path): inference only (no backward is built)")
+            raise NotImplementedError(
+                "TransformerEncoder (HIP path): in train mode the encoder only runs inside the whole-model training step "
+                "(audiocaption_amd.train.TrainEngine / TransformerModel.forward with mode='train')")
         lib = _lib.load()
         attn = f32c(input_dict["attn"])
         if not attn.is_cuda:

@@ -480,6 +480,18 @@ int ac_attn_seq_bwd(const float* q, long ldq, const float* k, long ldk, const fl
                     long lddv, const int* qrow0, const int* qlen, const int* krow0, const int* klen, int seq0, int nseq,
                     int nhead, int head_dim, int lmax, int tkmax, float drop_p, unsigned long long seed,
                     const unsigned long long* seed_dev, void* stream);
+/* The backward of ac_attn_seq_fwd with the same arguments as ac_attn_seq_bwd, tiled over rows for sequences whose
+ * score block does not fit one workgroup (the Transformer encoder's self-attention over T' + 1 rows): one launch of
+ * ATT_TILE query rows per workgroup writes dq, one of ATT_TILE key rows per workgroup writes dk / dv.  LDS grows
+ * linearly with lmax and tkmax; every (lmax, tkmax) ac_attn_seq_fwd accepts is accepted.  No atomics: the result is
+ * the same on every launch.  The dropout mask is regenerated from the P index, as in ac_attn_seq_bwd.  d_ws (optional,
+ * nseq*nhead*pl floats of scratch): the query pass stores each row's D = dO . O there for the key pass; without it the
+ * key pass recomputes D in every key tile (same result, more work). */
+int ac_attn_self_bwd_tiled(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* P,
+                           int pl, int ptk, const float* dout, long lddo, float* dq, long lddq, float* dk, long lddk,
+                           float* dv, long lddv, const int* qrow0, const int* qlen, const int* krow0, const int* klen,
+                           int seq0, int nseq, int nhead, int head_dim, int lmax, int tkmax, float drop_p,
+                           unsigned long long seed, const unsigned long long* seed_dev, float* d_ws, void* stream);
 /* dst[i] = src[index[i]] / dst[index[i]] += src[i] over rows of C floats (classifier on each pass's last position,
  * base.py:181-183). */
 int ac_gather_rows(const float* src, const int* index, float* dst, long nrows, int C, void* stream);

@@ -17,11 +17,17 @@ ap.add_argument("--cap-len", type=int, default=22)
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--seconds", type=float, default=10.0)
 ap.add_argument("--vocab", type=int, default=4981)
+ap.add_argument("--encoder", choices=("rnn", "trm"), default="rnn",
+                help="temporal encoder: rnn = CrnnEncoder (bi-GRU), trm = Cnn14TransformerEncoder")
 args = ap.parse_args()
 
 B, L = args.batch, int(args.seconds * 32000)
-model = A.init_model_from_config(A.cnn14rnn_trm_config(args.vocab), print_fn=lambda s: None)
-model.load_state_dict(Pr.to_torch(Pr.cnn14rnn_trm_state(args.vocab)), strict=True)
+if args.encoder == "trm":
+    cfg, state = A.config.cnn14trm_trm_config(args.vocab), Pr.cnn14trm_trm_state(args.vocab)
+else:
+    cfg, state = A.cnn14rnn_trm_config(args.vocab), Pr.cnn14rnn_trm_state(args.vocab)
+model = A.init_model_from_config(cfg, print_fn=lambda s: None)
+model.load_state_dict(Pr.to_torch(state), strict=True)
 model = model.to("cuda:0").train()
 wav = torch.from_numpy(Pr.synthetic_wav(B, L, seed=1)).cuda()
 g = torch.Generator().manual_seed(0)
@@ -41,5 +47,5 @@ for _ in range(args.steps):
 t_host = time.perf_counter() - t0
 torch.cuda.synchronize()
 t = time.perf_counter() - t0
-print(f"B={B} cap_len={args.cap_len}: {1e3 * t / args.steps:.2f} ms/step ({B * args.steps / t:.0f} clips/s), "
+print(f"encoder={args.encoder} B={B} seconds={args.seconds:g} cap_len={args.cap_len}: {1e3 * t / args.steps:.2f} ms/step ({B * args.steps / t:.0f} clips/s), "
       f"host submit {1e3 * t_host / args.steps:.2f} ms/step, loss {float(r['loss']):.4f}")
