@@ -2,7 +2,11 @@
 """Headline benchmark: clips/s for encode + greedy decode of the Cnn14Rnn-Trm captioner on synthetic
 10 s @ 32 kHz clips (BASELINE.json metric, configs[1]: batch 64 per GPU, max_length 20).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--details-file FILE]]
+
+A plain run does what the headline figure needs and nothing else: set-up, the W warm-up steps, the K timed steps, the
+``--dump-outputs`` arrays and the JSON line.  ``--full`` adds every secondary measurement listed below (the ``--no-*``
+options leave single ones out of it).
 
 One process per GPU (torch.distributed / RCCL when N > 1): launched under ``torch.distributed.run`` the ranks are read
 from the environment; launched plainly with ``--gpus N > 1`` the script re-executes itself under
@@ -13,10 +17,16 @@ decoding, token ids back on the host) over one resident batch.  Rank 0 prints ON
 * ``value``: the throughput of the DEFAULT conv tier - "wino43", f32-grade: logits within 1e-4 of the fp32 reference,
   identical token ids (``config.precision_gate``) - over exactly K timed steps that rotate over four resident input
   batches;
-* ``roofline``: the dominant kernel (conv2 + BN + ReLU + 2x2 pool of blocks 2-5) timed live with HIP events on its
-  launch stream; ``achieved`` = algorithmic direct-convolution FLOPs / time, ``frac`` = achieved / the dense peak of the
-  pipe the products run on (the roofline fraction); ``mfma_issue_frac`` = MFMA FLOPs actually ISSUED / that peak (pipe
-  utilisation: the split-bf16 F(4,3) form issues 1.5 bf16 products per algorithmic f32 product);
+* ``roofline``: the dominant kernel (conv2 + BN + ReLU + 2x2 pool of blocks 2-5) timed with HIP events on its launch
+  stream during the K timed steps; ``achieved`` = algorithmic direct-convolution FLOPs / time, ``frac`` = achieved / the
+  dense peak of the pipe the products run on (the roofline fraction); ``mfma_issue_frac`` = MFMA FLOPs actually ISSUED /
+  that peak (pipe utilisation: the split-bf16 F(4,3) form issues 1.5 bf16 products per algorithmic f32 product);
+* with N > 1, ``ranks`` (where every rank sat) and ``seconds_per_rank`` (each rank's own time of the timed steps);
+
+and with ``--full`` also
+
+* ``roofline.sustained_mfma_tflops_measured``: what a bare MFMA loop reaches on this part, with ``frac_of_sustained``;
+* ``rccl`` (N > 1): the node's collective rates on a buffer of the training step's gradient size;
 * flat scalars measured in THIS run: ``value_f32_exact`` (Winograd on the f32 MFMA), ``value_bf16x3_direct``,
   ``value_f16x2_half_precision_gate`` (the opt-in fp16 tier: NOT reference precision), ``value_blocking_model_call`` (the
   reference's own call, one blocking ``model(input_dict)`` per step), ``latency_b1_greedy_ms`` / ``latency_b1_beam3_ms``
@@ -27,8 +37,8 @@ decoding, token ids back on the host) over one resident batch.  Rank 0 prints ON
   bounded 32-clip sample.
 ``--dump-outputs DIR`` writes the arrays the last timed step returned (token ids, log-probabilities, logits, decoder
 embeddings, encoder outputs of rank 0's batch) as ``DIR/<name>.npy`` (see ``host_outputs`` / ``dump_outputs``).
-The per-tier rooflines, the steady-state window, the decoder GEMM table, the training-step and EffB2 objects go to
-``gpurun_out/bench_details.json`` (``details_file``) so that the printed line stays short.
+With ``--full`` the per-tier rooflines, the steady-state window, the decoder GEMM table, the training-step and EffB2
+objects go to ``--details-file`` (``details_file`` in the line) so that the printed line stays short.
 """
 import argparse
 import json
@@ -789,6 +799,14 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="clips per GPU per step")
     ap.add_argument("--seconds", type=float, default=10.0, help="clip duration")
     ap.add_argument("--max-length", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary measurement: the other conv tiers, the steady-state "
+                         "window, the blocking call, batch-1 latency, log-mel / decoder / MFMA rooflines, the training step, "
+                         "EffB2-Trm, the ragged batch, H2D and ingest, collective rates (N > 1) and the CPU baseline; "
+                         "the --no-* options leave single ones out")
+    ap.add_argument("--details-file", default=os.path.join(REPO, "bench_out", "bench_details.json"), metavar="FILE",
+                    help="with --full: where the per-tier rooflines, steady state, decoder GEMMs, train_step and "
+                         "effb2_trm objects are written (default: bench_out/bench_details.json in the repository)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tiers", "--no-f32-path", dest="no_tiers", action="store_true",
                     help="skip the measurements of the other conv tiers")
@@ -821,6 +839,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.mode != "infer":
         ap.error("--dump-outputs covers the headline workload (--mode infer)")
+    if args.full and args.mode != "infer":
+        ap.error("--full adds the secondary measurements of the headline workload (--mode infer)")
 
     # `python bench.py --gpus N` without a launcher: spawn the N ranks ourselves
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -961,6 +981,65 @@ def main():
     # the headline line cites this round's PMC file: missing = error (AUDIOCAPTION_TRAFFIC_OPTIONAL=1: the collection passes
     # themselves, tools/round_profiles.sh, which run before the file exists)
     headline_roof = conv_roofline(default_tier, events, required_traffic=os.environ.get("AUDIOCAPTION_TRAFFIC_OPTIONAL") != "1")
+
+    # ---- the line: what the timed steps measured; --full adds the secondary measurements below to it ----
+    headline = None
+    if rank == 0:
+        clips = world * B * args.steps
+        headline = {
+            "metric": "clips/sec (10 s @ 32 kHz) encode+greedy-decode, Cnn14_Rnn-Trm",
+            "value": clips / elapsed,
+            "unit": "clips/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": TIERS[default_tier]["dtype"],
+            "data": "synthetic",
+            "config": {"workload": f"Cnn14Rnn-Trm greedy decode, batch {B} per GPU, {args.seconds:g} s @ 32 kHz "
+                                   f"synthetic clips, max_length {args.max_length}, vocab {vocab} (BASELINE configs[1])",
+                       "global_batch": world * B, "decode_steps_executed": args.max_length,
+                       "decode_steps_reference_would_run": ref_steps, "conv_algo": default_algo,
+                       "input_set": ("Clotho-shape: ragged 15-30 s clips, zero-padded, duration-balanced sharding; "
+                                     "%.0f s of audio per step on rank 0" % audio_seconds) if args.clotho_shape else
+                                    f"fixed-length, {NROT} resident batches in rotation",
+                       "precision_gate": "logits within 1e-4 of the fp32 CPU reference, identical token ids"
+                                         if default_tier != "f16x2" else "HALF-PRECISION gate only: logits within 1e-3",
+                       "precision": {
+                           "wino43": "f32 activations in HBM; 3x3 convolutions as Winograd along time on split-bf16 operands "
+                                     "(x = hi + lo, hi*hi + hi*lo + lo*hi, f32 accumulate: 2^-16 operand error) - F(4,3) on conv "
+                                     "blocks 1-6 (block 1 fused: conv1 computed inside conv2's staging; block 6 as column "
+                                     "tiles; input transform in f32, filter transform in f64, both BEFORE the split) - GRU "
+                                     "input projections on split-bf16 operands, everything else f32",
+                           "wino1d": "f32 activations in HBM; 3x3 convolutions as F(2,3) Winograd along time on split-bf16 "
+                                     "operands (x = hi + lo, hi*hi + hi*lo + lo*hi, f32 accumulate: 2^-16 operand error), "
+                                     "GRU input projections on split-bf16 operands, everything else f32",
+                           "bf16x3": "f32 activations; direct 3x3 convolutions on split-bf16 operands (2^-16), f32 accumulate",
+                           "f32": "f32 end to end (Winograd F(2x2,3x3) on the f32 MFMA)",
+                           "f16x2": "fp16 activations in HBM, fp16 hi+lo weights: NOT reference precision (logits within "
+                                    "1e-3); batches with a clip under 3.2 s or an fp16 overflow re-run on bf16x3"}[default_tier],
+                       "sharding": f"clips sharded over {world} rank(s), no data-path collective",
+                       "schedule": "blocking model() per step" if args.sync_steps else
+                                   "forward_async: encoder of step i+1 under the decode chain of step i (two HIP streams)"},
+            "roofline": {k: headline_roof[k] for k in ("bound", "achieved", "peak", "unit", "frac", "mfma_issue_frac",
+                                                       "issued_per_algorithmic", "traffic", "traffic_source", "avg_launch_ms",
+                                                       "launches_timed", "kernel")},
+        }
+    multi = None
+    if world > 1:
+        # N > 1: the inference path has no collective (clips are sharded), so the line says where every rank sat and its own
+        # time next to the max-over-ranks headline (collectives: every rank calls them)
+        multi = {"ranks": ranks.describe(), "seconds_per_rank": seconds_per_rank(ranks, elapsed_own, dev)}
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(dict(headline, **(multi or {}))), flush=True)
+        ranks.finish()
+        return
+
     tiers = {default_tier: {"value": world * B * args.steps / elapsed, "unit": "clips/s", "ms_per_step": elapsed / args.steps * 1e3,
                             "steps": args.steps, "conv_algo": default_algo, "dtype": TIERS[default_tier]["dtype"],
                             "precision_gate": TIERS[default_tier]["gate"], "roofline": headline_roof}}
@@ -1210,13 +1289,9 @@ def main():
                                                       "encoder_roofline")}
         except Exception as e:  # noqa: BLE001
             extra["effb2_trm"] = {"error": f"{type(e).__name__}: {e}"}
-    multi = None
     if world > 1:
-        # N > 1: the inference path has no collective (clips are sharded), so the line carries what makes the run
-        # self-describing - where every rank sat, its own time, and the node's collective rates on a buffer of the
-        # training step's gradient size (42.8 MB) - next to the max-over-ranks headline
-        multi = {"ranks": ranks.describe(), "seconds_per_rank": seconds_per_rank(ranks, elapsed_own, dev),
-                 "rccl": collective_record(ranks, dev)}
+        # the node's collective rates on a buffer of the training step's gradient size (42.8 MB)
+        multi["rccl"] = collective_record(ranks, dev)
     sustained = {}
     if rank == 0 and TIERS[default_tier]["peak"] == BF16_MFMA_PEAK_TFLOPS:
         try:   # context for `frac` (denominator: the nominal dense peak): what a bare MFMA loop reaches on this part
@@ -1228,49 +1303,9 @@ def main():
         except Exception as e:  # noqa: BLE001
             sustained = {"sustained_mfma_tflops_measured": None, "sustained_note": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        clips = world * B * args.steps
         val = lambda d_, k="value": (d_ or {}).get(k) if isinstance(d_, dict) else None
-        result = {
-            "metric": "clips/sec (10 s @ 32 kHz) encode+greedy-decode, Cnn14_Rnn-Trm",
-            "value": clips / elapsed,
-            "unit": "clips/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": TIERS[default_tier]["dtype"],
-            "data": "synthetic",
-            "config": {"workload": f"Cnn14Rnn-Trm greedy decode, batch {B} per GPU, {args.seconds:g} s @ 32 kHz "
-                                   f"synthetic clips, max_length {args.max_length}, vocab {vocab} (BASELINE configs[1])",
-                       "global_batch": world * B, "decode_steps_executed": args.max_length,
-                       "decode_steps_reference_would_run": ref_steps, "conv_algo": default_algo,
-                       "input_set": ("Clotho-shape: ragged 15-30 s clips, zero-padded, duration-balanced sharding; "
-                                     "%.0f s of audio per step on rank 0" % audio_seconds) if args.clotho_shape else
-                                    f"fixed-length, {NROT} resident batches in rotation",
-                       "precision_gate": "logits within 1e-4 of the fp32 CPU reference, identical token ids"
-                                         if default_tier != "f16x2" else "HALF-PRECISION gate only: logits within 1e-3",
-                       "precision": {
-                           "wino43": "f32 activations in HBM; 3x3 convolutions as Winograd along time on split-bf16 operands "
-                                     "(x = hi + lo, hi*hi + hi*lo + lo*hi, f32 accumulate: 2^-16 operand error) - F(4,3) on conv "
-                                     "blocks 1-6 (block 1 fused: conv1 computed inside conv2's staging; block 6 as column "
-                                     "tiles; input transform in f32, filter transform in f64, both BEFORE the split) - GRU "
-                                     "input projections on split-bf16 operands, everything else f32",
-                           "wino1d": "f32 activations in HBM; 3x3 convolutions as F(2,3) Winograd along time on split-bf16 "
-                                     "operands (x = hi + lo, hi*hi + hi*lo + lo*hi, f32 accumulate: 2^-16 operand error), "
-                                     "GRU input projections on split-bf16 operands, everything else f32",
-                           "bf16x3": "f32 activations; direct 3x3 convolutions on split-bf16 operands (2^-16), f32 accumulate",
-                           "f32": "f32 end to end (Winograd F(2x2,3x3) on the f32 MFMA)",
-                           "f16x2": "fp16 activations in HBM, fp16 hi+lo weights: NOT reference precision (logits within "
-                                    "1e-3); batches with a clip under 3.2 s or an fp16 overflow re-run on bf16x3"}[default_tier],
-                       "sharding": f"clips sharded over {world} rank(s), no data-path collective",
-                       "schedule": "blocking model() per step" if args.sync_steps else
-                                   "forward_async: encoder of step i+1 under the decode chain of step i (two HIP streams)"},
-            "roofline": dict({k: headline_roof[k] for k in ("bound", "achieved", "peak", "unit", "frac", "mfma_issue_frac",
-                                                            "issued_per_algorithmic", "traffic", "traffic_source", "avg_launch_ms",
-                                                            "launches_timed", "kernel")}, **sustained),
+        result = dict(headline, roofline=dict(headline["roofline"], **sustained))
+        result.update({
             # flat scalars, all measured in this run
             "value_f32_exact": val(tiers.get("f32")),
             "value_bf16x3_direct": val(tiers.get("bf16x3")),
@@ -1295,9 +1330,9 @@ def main():
             "ingest_kernel_clips_per_s": val(extra.get("ingest"), "kernel_clips_per_s"),
             "clotho_shape_clips_per_s": val((extra.get("ragged") or {}).get("skip")),
             "clotho_shape_no_skip_clips_per_s": val((extra.get("ragged") or {}).get("no_skip")),
-        }
+        })
         if multi is not None:
-            result.update({"ranks": multi["ranks"], "seconds_per_rank": multi["seconds_per_rank"], "rccl": multi["rccl"]})
+            result.update(multi)
         details = {"tiers": tiers, "steady_state": steady, "blocking_model_call": blocking, "latency_b1_ms": latency,
                    "rooflines_other": {"logmel": extra["mel_roofline"], "decoder": extra["decoder_roofline"]},
                    "train_step": extra.get("train_step"), "train_step_b4": extra.get("train_step_b4"), "effb2_trm": extra.get("effb2_trm"), "ragged": extra.get("ragged"),
@@ -1332,11 +1367,12 @@ def main():
             except Exception as e:  # noqa: BLE001
                 result["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
         try:
-            os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
-            dpath = os.path.join(REPO, "gpurun_out", "bench_details.json")
+            dpath = os.path.abspath(args.details_file)
+            os.makedirs(os.path.dirname(dpath), exist_ok=True)
             with open(dpath, "w") as f:
                 json.dump({"line": result, "details": details}, f, indent=1)
-            result["details_file"] = "gpurun_out/bench_details.json (per-tier rooflines, steady state, decoder GEMMs, train_step, effb2_trm)"
+            shown = os.path.relpath(dpath, REPO) if dpath.startswith(REPO + os.sep) else dpath
+            result["details_file"] = f"{shown} (per-tier rooflines, steady state, decoder GEMMs, train_step, effb2_trm)"
         except OSError:
             pass
         print(json.dumps(result), flush=True)

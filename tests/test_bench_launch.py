@@ -75,11 +75,26 @@ def test_bench_two_ranks_real_workload_on_one_gpu():
     rank records, per-rank seconds) with two gloo ranks sharing the only GPU of the box - RCCL refuses two ranks on one
     device, everything else is the code an 8-GPU run executes."""
     res = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--seconds", "2", "--max-length", "6",
-                "--no-tiers", "--no-train", "--no-effb2", "--no-steady-state", "--no-cpu-baseline"], timeout=600)
+                "--full", "--no-tiers", "--no-train", "--no-effb2", "--no-steady-state", "--no-cpu-baseline"], timeout=600)
     assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 8 and res["value"] > 0
     assert [r["rank"] for r in res["ranks"]] == [0, 1] and len(res["seconds_per_rank"]) == 2
     assert res["rccl"]["world_size"] == 2 and res["scaling"] == "weak"
     assert abs(res["value"] - 8 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_reports_the_headline_only(tmp_path):
+    """Without --full the real inference bench times the headline and stops: the line carries what the timed steps
+    measured and none of the secondary measurements, and no details file is written."""
+    details = tmp_path / "details.json"
+    res = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--seconds", "2", "--max-length", "6",
+                "--details-file", str(details)], timeout=600)
+    assert res["n_gpus"] == 1 and res["steps"] == 2 and res["warmup"] == 1 and res["higher_is_better"] is True
+    assert res["unit"] == "clips/s" and res["config"]["global_batch"] == 4
+    assert abs(res["value"] - 4 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]
+    assert not [k for k in res if k.startswith(("value_", "latency_", "train_", "effb2_", "ingest_", "clotho_", "steady_"))]
+    assert not {"cpu_baseline", "rccl", "details_file", "logmel_hbm_frac"} & set(res)
+    assert "sustained_mfma_tflops_measured" not in res["roofline"] and not details.exists()
 
 
 def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):

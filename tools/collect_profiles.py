@@ -1,4 +1,4 @@
-"""Development tool: copy the round's profile set from gpurun_out/ (written by tools/round_profiles.sh on the GPU box) into
+"""Development tool: copy the round's profile set from $OUT_DIR (default bench_out/, written by tools/round_profiles.sh) into
 profiles/ and derive profiles/rNN_traffic_<tier>.json (HBM bytes, matrix-pipe busy fraction and clock of the dominant conv
 kernel) from the four --pmc passes and the kernel stats of the same command.
 
@@ -13,7 +13,7 @@ import sys
 
 R = sys.argv[1] if len(sys.argv) > 1 else "r06"
 TIER = sys.argv[2] if len(sys.argv) > 2 else "wino43"
-src, dst = "gpurun_out", "profiles"
+src, dst = os.environ.get("OUT_DIR", "bench_out"), "profiles"
 names = {f"{R}_bench_final.json": f"{R}_bench.json", f"{R}_bench_details.json": None, f"{R}_kernel_stats.txt": None,
          f"{R}_train_kernel_stats.txt": None, f"{R}_train_bench.json": None, f"{R}_effb2_bench.json": None,
          f"{R}_effb2_30s_beam4.json": None, f"{R}_effb2_kernel_stats.txt": None, f"{R}_traffic_effb2.json": None,

@@ -1,5 +1,5 @@
 """Development tool: the kernels of ONE blocking model() call in launch order, with the idle time before each
-(rocprofv3 --kernel-trace rocpd database of `python bench.py --sync-steps --no-tiers ...`):
+(rocprofv3 --kernel-trace rocpd database of `python bench.py --full --sync-steps --no-tiers ...`):
 
     python tools/kernel_gaps.py <results.db> [anchor kernel substring = logmel]
 
