@@ -124,6 +124,14 @@ class FlatParams:
     def g(self, name):
         return self.grad.data_ptr() + 4 * self.offsets[self.index[name]]
 
+    def wb(self, name):
+        """(weight, bias) of a Linear; ``name`` ends where the two names part: "...linear1." / "...in_proj_"."""
+        return self.p(name + "weight"), self.p(name + "bias")
+
+    def wgb(self, name):
+        """(weight, d weight, d bias) of a Linear: what its backward takes (``TrainEngine._lin_bwd``)."""
+        return self.p(name + "weight"), self.g(name + "weight"), self.g(name + "bias")
+
     def attach_grads(self):
         """Fast path: make the views of the flat buffer the parameters' ``.grad`` (no copies)."""
         for p, v in zip(self.params, self.grad_views):
@@ -318,6 +326,7 @@ class TrainEngine:
         self._saved = None
         self._states = {}
         self._phase = "forward"
+        self._side = _SideStream()
         # GEMMs of the step: "bf16x3" = split-bf16 operands on the bf16 MFMA for the large products (the backward over
         # all rows, teacher forcing), "f32" = exact f32 MFMA everywhere
         # "pw" (default) = "bf16x3" with the products against a WEIGHT matrix (x W^T and dy W, two thirds of the GEMM time)
@@ -330,21 +339,24 @@ class TrainEngine:
         self.gru_algo = os.environ.get("AUDIOCAPTION_GRU_ALGO", "split")   # forward recurrence kernel (see RnnEncoder)
 
     # ---- small launch helpers (raw addresses; s = stream handle) ------------------------------------------
+    def _hooked(self, M, N, K, launch):
+        """One GEMM launch, between GEMM_HOOK's "pre" and "post" calls when a hook is set (read at call time)."""
+        hook = GEMM_HOOK
+        if hook is None:
+            return launch()
+        info = {"phase": self._phase, "M": M, "N": N, "K": K, "flops": 2.0 * M * N * K}
+        hook("pre", info)
+        launch()
+        hook("post", info)
+
     def _gemm(self, s, A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias=None, relu=0, beta=0.0, splitk=1, drop_p=0.0,
               seed=0, row0=0):
-        hook = GEMM_HOOK
-        if hook is not None:
-            info = {"phase": self._phase, "M": M, "N": N, "K": K, "flops": 2.0 * M * N * K}
-            hook("pre", info)
-        if self.gemm_algo in ("bf16x3", "pw"):
-            # split-bf16 operands (2^-16), f32 accumulation; small or unaligned products fall through to exact f32
-            check(self.lib.ac_gemm_bf16x3(A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, relu, beta, splitk, drop_p, seed,
-                                          self._seed_ptr, row0, None, 0, s), "ac_gemm_bf16x3")
-        else:
-            check(self.lib.ac_gemm(A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, relu, beta, splitk, drop_p, seed,
-                                   self._seed_ptr, row0, None, 0, s), "ac_gemm")
-        if hook is not None:
-            hook("post", info)
+        # "bf16x3" / "pw": split-bf16 operands (2^-16), f32 accumulation; small or unaligned products fall through to
+        # exact f32
+        name = "ac_gemm_bf16x3" if self.gemm_algo in ("bf16x3", "pw") else "ac_gemm"
+        self._hooked(M, N, K, lambda: check(getattr(self.lib, name)(
+            A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, relu, beta, splitk, drop_p, seed, self._seed_ptr, row0, None, 0,
+            s), name))
 
     # ---- products against a weight matrix on the activation-stationary kernel (csrc/pw_gemm.hip) ----
     def _pw_frag(self, s, W, N, K, transposed):
@@ -393,30 +405,18 @@ class TrainEngine:
         """y[M][N] = x[M][K] W[N][K]^T + b"""
         ldx, ldy = ldx or K, ldy or N
         if self.gemm_algo == "pw" and self._pw_ok(M, N, K, ldx, ldy, x, W, b, y):
-            hook = GEMM_HOOK
-            if hook is not None:
-                info = {"phase": self._phase, "M": M, "N": N, "K": K, "flops": 2.0 * M * N * K}
-                hook("pre", info)
-            check(self.lib.ac_pw_gemm_bf16x3_ex(x, ldx, self._pw_frag(s, W, N, K, False), b, y, ldy, M, N, K, relu, 0.0, None,
-                                                0, drop_p, seed, self._seed_ptr, row0, s), "ac_pw_gemm_bf16x3_ex")
-            if hook is not None:
-                hook("post", info)
-            return
+            return self._hooked(M, N, K, lambda: check(self.lib.ac_pw_gemm_bf16x3_ex(
+                x, ldx, self._pw_frag(s, W, N, K, False), b, y, ldy, M, N, K, relu, 0.0, None, 0, drop_p, seed,
+                self._seed_ptr, row0, s), "ac_pw_gemm_bf16x3_ex"))
         self._gemm(s, x, ldx, 1, W, 1, K, y, ldy, M, N, K, b, relu, 0.0, 1, drop_p, seed, row0)
 
     def _lin_dx(self, s, dy, W, dx, M, N, K, beta=0.0, lddy=None, lddx=None):
         """dx[M][K] (+)= dy[M][N] W[N][K]"""
         lddy, lddx = lddy or N, lddx or K
         if self.gemm_algo == "pw" and self._pw_ok(M, K, N, lddy, lddx, dy, W, dx):
-            hook = GEMM_HOOK
-            if hook is not None:
-                info = {"phase": self._phase, "M": M, "N": K, "K": N, "flops": 2.0 * M * N * K}
-                hook("pre", info)
-            check(self.lib.ac_pw_gemm_bf16x3_ex(dy, lddy, self._pw_frag(s, W, N, K, True), None, dx, lddx, M, K, N, 0, beta,
-                                                None, 0, 0.0, 0, None, 0, s), "ac_pw_gemm_bf16x3_ex")
-            if hook is not None:
-                hook("post", info)
-            return
+            return self._hooked(M, K, N, lambda: check(self.lib.ac_pw_gemm_bf16x3_ex(
+                dy, lddy, self._pw_frag(s, W, N, K, True), None, dx, lddx, M, K, N, 0, beta, None, 0, 0.0, 0, None, 0, s),
+                "ac_pw_gemm_bf16x3_ex"))
         # few output tiles over a long reduction (the classifier's dx: 672 x 256 outputs over 4981 vocabulary entries; the
         # GRU's dx: 992 x 512 over 1536 gate columns): slices of the reduction on separate workgroups (atomic accumulation,
         # like the weight gradients) instead of 44 / 128 workgroups walking all of it
@@ -437,6 +437,74 @@ class TrainEngine:
 
     def _colsum(self, s, x, ld, out, M, N):
         check(self.lib.ac_colsum(x, ld, out, M, N, s), "ac_colsum")
+
+    def _lin_bwd(self, s, side, dy, x, W, gW, gb, rows, N, K, dx=None, beta=0.0, s2=None):
+        """Backward of y[rows][N] = x[rows][K] W[N][K]^T + b (both dense): gW += dy^T x and, with ``gb``, gb += the column
+        sums of dy on the side stream - forked here, unless ``s2`` hands in the fork an earlier call returned (two
+        products behind one fork) -, then, with ``dx``, dx (+)= dy W on ``s``.  Returns the side stream's handle."""
+        if s2 is None:
+            s2 = side.fork()
+        self._lin_dw(s2, dy, N, x, K, gW, rows, N, K)
+        if gb is not None:
+            self._colsum(s2, dy, N, gb, rows, N)
+        if dx is not None:
+            self._lin_dx(s, dy, W, dx, rows, N, K, beta=beta)
+        return s2
+
+    # ---- the sub-layers of a post-LN Transformer layer, shared by the decoder and the Transformer encoder -------------
+    # lp = the layer's parameter-name prefix; r = its activation record, addresses of buffers over the stack's whole row
+    # space: x_in, qkv, ctx, sa, pre1, x1, P (self-attention), hdn, ff, pre_ff, x_out (feed-forward) - the decoder adds
+    # q2, ctx2, ca, pre2, x2, P2 (cross-attention).  The forward covers rows [off, off + nr), the backward all ``rows``.
+    def _self_attn_fwd(self, s, lp, r, off, nr, attn, p, op, eps):
+        """x1 = norm1(x_in + dropout(out_proj(attention(in_proj(x_in))))).  ``attn``: the arguments of ac_attn_seq_fwd
+        from the probabilities to the dropout site (index tables, masks, lengths: what the two stacks do differently)."""
+        fp, qkv, o4 = self.flat, r["qkv"], 4 * off * D
+        self._lin(s, r["x_in"] + o4, *fp.wb(lp + "self_attn.in_proj_"), qkv + 3 * o4, nr, 3 * D, D)
+        check(self.lib.ac_attn_seq_fwd(qkv, 3 * D, qkv + 4 * D, 3 * D, qkv + 8 * D, 3 * D, r["ctx"], D, *attn,
+                                       self._seed_ptr, s), "ac_attn_seq_fwd")
+        self._lin(s, r["ctx"] + o4, *fp.wb(lp + "self_attn.out_proj."), r["sa"] + o4, nr, D, D)
+        check(self.lib.ac_dropadd_ln_fwd(r["sa"], r["x_in"], *fp.wb(lp + "norm1."), r["pre1"], r["x1"], off, nr, 0, D, p, op,
+                                         self._seed_ptr, eps, s), "ac_dropadd_ln_fwd(norm1)")
+
+    def _ffn_fwd(self, s, lp, norm, r, x, off, nr, F, p_ff, op_ff, p, op, eps):
+        """x_out = norm(x + dropout(linear2(dropout(relu(linear1(x)))))); ``norm``: "norm3." (decoder) / "norm2."."""
+        fp, hdn, o4 = self.flat, r["hdn"] + 4 * off * F, 4 * off * D
+        self._lin(s, x + o4, *fp.wb(lp + "linear1."), hdn, nr, F, D, relu=1, drop_p=p_ff, seed=op_ff, row0=off)
+        self._lin(s, hdn, *fp.wb(lp + "linear2."), r["ff"] + o4, nr, D, F)
+        check(self.lib.ac_dropadd_ln_fwd(r["ff"], x, *fp.wb(lp + norm), r["pre_ff"], r["x_out"], off, nr, 0, D, p, op,
+                                         self._seed_ptr, eps, s), "ac_dropadd_ln_fwd(feed-forward)")
+
+    def _ln_bwd(self, s, norm, dy, pre, dsub, dres, rows, p, op, eps, relu_src=None, relu_mod=0):
+        """Backward of dropout + add + LayerNorm ``norm``: dsub = d(sub-layer output) [through the ReLU that made
+        ``relu_src``], dres = d(residual) or None."""
+        w, gw, gb = self.flat.wgb(norm)
+        check(self.lib.ac_dropadd_ln_bwd(dy, pre, w, dsub, dres, 0, relu_src, relu_mod, gw, gb, rows, D, p, op,
+                                         self._seed_ptr, eps, s), "ac_dropadd_ln_bwd(" + norm + ")")
+
+    # The backward of a sub-layer takes dx = d(loss)/d(its output) and a free buffer dres, leaves d(loss)/d(its input) in
+    # dres and returns the two swapped; g = the stack's scratch gradients (dsub, dctx, dhdn, dqkv).
+    def _ffn_bwd(self, s, side, lp, norm, r, x, g, dx, dres, rows, F, p_ff, p, op, eps):
+        fp, dsub, dhdn = self.flat, g["dsub"], g["dhdn"]
+        side.join()   # the scratch gradients the side stream read (dsub, dhdn, a layer on dqkv ...) are written again
+        self._ln_bwd(s, lp + norm, dx, r["pre_ff"], dsub, dres, rows, p, op, eps)
+        self._lin_bwd(s, side, dsub, r["hdn"], *fp.wgb(lp + "linear2."), rows, D, F, dx=dhdn)
+        check(self.lib.ac_mask_pos_scale(dhdn, r["hdn"], rows * F, 1.0 / (1.0 - p_ff) if p_ff > 0 else 1.0, s),
+              "ac_mask_pos_scale")
+        self._lin_bwd(s, side, dhdn, x, *fp.wgb(lp + "linear1."), rows, F, D, dx=dres, beta=1.0)
+        return dres, dx
+
+    def _self_attn_bwd(self, s, side, lp, r, g, dx, dres, rows, attn, p, op, eps):
+        """``attn`` = (entry, (P, its two strides), arguments from the index tables to the dropout site, arguments after
+        the seed): ac_attn_seq_bwd, or ac_attn_self_bwd_tiled with its D workspace."""
+        fp, qkv, dsub, dctx, dqkv = self.flat, r["qkv"], g["dsub"], g["dctx"], g["dqkv"]
+        entry, probs, tables, extra = attn
+        side.join()
+        self._ln_bwd(s, lp + "norm1.", dx, r["pre1"], dsub, dres, rows, p, op, eps)
+        self._lin_bwd(s, side, dsub, r["ctx"], *fp.wgb(lp + "self_attn.out_proj."), rows, D, D, dx=dctx)
+        check(getattr(self.lib, entry)(qkv, 3 * D, qkv + 4 * D, 3 * D, qkv + 8 * D, 3 * D, *probs, dctx, D, dqkv, 3 * D,
+                                       dqkv + 4 * D, 3 * D, dqkv + 8 * D, 3 * D, *tables, self._seed_ptr, *extra, s), entry)
+        self._lin_bwd(s, side, dqkv, r["x_in"], *fp.wgb(lp + "self_attn.in_proj_"), rows, 3 * D, D, dx=dres, beta=1.0)
+        return dres, dx
 
     # ---------------------------------------------------------------------------------------------------
     def _ensure(self, device):
@@ -588,13 +656,13 @@ class TrainEngine:
         s = _lib.stream()
         self._phase = "forward"
         ws, lay = st["ws"], st["lay"]
-        N, T, Tc, Tq = st["N"], st["T"], st["Tc"], st["Tq"]
-        p_dec, p_rnn, p_cnn = st["p_dec"], st["p_rnn"], st["p_cnn"]
+        N, T = st["N"], st["T"]
+        p_dec, p_cnn = st["p_dec"], st["p_cnn"]
         teacher_forcing = st["teacher_forcing"]
         small = st["small"].data_ptr()
         self._seed_ptr = small
         self._pw_pack_all(s)        # the optimiser moved the weights since the last iteration
-        lens_p, ucap, mvalid = small + 8, small + 4 * (2 + 2 * N), small + 4 * (2 + 2 * N + max(T, 1))
+        ucap, mvalid = small + 4 * (2 + 2 * N), small + 4 * (2 + 2 * N + max(T, 1))
         R, S, passes = lay["R"], lay["S"], lay["passes"]
         NP = len(passes)
         Tm = st["Tm"]
@@ -620,10 +688,10 @@ class TrainEngine:
         rows_m = N * Tm
         Rm = NP * rows_m
         mem_a = ws.f("mem_a", rows_m, D)
-        self._lin(s, attn_emb, fp.p(dp + "attn_proj.0.weight"), fp.p(dp + "attn_proj.0.bias"), mem_a, rows_m, D, A, relu=1)
+        self._lin(s, attn_emb, *fp.wb(dp + "attn_proj.0."), mem_a, rows_m, D, A, relu=1)
         mem_pre, mem = ws.f("mem_pre", Rm, D), ws.f("mem", Rm, D)
-        check(lib.ac_dropadd_ln_fwd(mem_a, None, fp.p(dp + "attn_proj.3.weight"), fp.p(dp + "attn_proj.3.bias"), mem_pre,
-                                    mem, 0, Rm, rows_m, D, p_dec, OP_MEM, self._seed_ptr, 1e-5, s), "ac_dropadd_ln_fwd")
+        check(lib.ac_dropadd_ln_fwd(mem_a, None, *fp.wb(dp + "attn_proj.3."), mem_pre, mem, 0, Rm, rows_m, D, p_dec, OP_MEM,
+                                    self._seed_ptr, 1e-5, s), "ac_dropadd_ln_fwd")
         kv = []
         for l in range(nlay):
             lp = f"{dp}model.layers.{l}."
@@ -642,16 +710,17 @@ class TrainEngine:
         nh = dec.nhead
         P1 = [ws.f(f"P1_{l}", S * nh * T * T) for l in range(nlay)]     # attention probabilities, kept per layer
         P2 = [ws.f(f"P2_{l}", S * nh * T * Tm) for l in range(nlay)]
-        x0 = ws.f("x_l0", R, D)
+        x = ws.f("x_l0", R, D)
         acts = []
         for l in range(nlay):
-            a = {k: ws.f(f"{k}{l}", R, w) for k, w in (("qkv", 3 * D), ("ctx1", D), ("sa", D), ("pre1", D), ("x1", D),
-                                                       ("q2", D), ("ctx2", D), ("ca", D), ("pre2", D), ("x2", D),
-                                                       ("hdn", F), ("ff", D), ("pre3", D))}
-            a["x3"] = ws.f(f"x_l{l + 1}", R, D)
+            a = {k: ws.f(f"{n}{l}", R, w) for k, n, w in (
+                ("qkv", "qkv", 3 * D), ("ctx", "ctx1", D), ("sa", "sa", D), ("pre1", "pre1", D), ("x1", "x1", D),
+                ("q2", "q2", D), ("ctx2", "ctx2", D), ("ca", "ca", D), ("pre2", "pre2", D), ("x2", "x2", D),
+                ("hdn", "hdn", F), ("ff", "ff", D), ("pre_ff", "pre3", D))}
+            a.update(x_in=x, x_out=ws.f(f"x_l{l + 1}", R, D), P=P1[l], P2=P2[l], kv=kv[l])
             acts.append(a)
-        st.update(V=V, F=F, gru=gru, kv=kv, acts=acts, x0=x0, word=word, P1=P1, P2=P2, mem=mem, mem_pre=mem_pre,
-                  mem_a=mem_a, attn_emb=attn_emb)
+            x = a["x_out"]
+        st.update(V=V, F=F, gru=gru, acts=acts, word=word, mem=mem, mem_pre=mem_pre, mem_a=mem_a, attn_emb=attn_emb)
         st["ctx"] = dict(seq=seq, logit=logit, pos=pos, qrow0=qrow0, qlen=qlen, mrow0=mrow0, mklen=mklen, emb=emb, pe=pe,
                          cls=cls, ucap=ucap, mvalid=mvalid, Tm=Tm)
         # The reference runs T sequential decoder passes (pass t on the prefix of length t + 1).  Which passes are
@@ -703,14 +772,12 @@ class TrainEngine:
         pre = "encoder.trm."
         Cin = cnn_attn.shape[2]
         a = ws.f("enc_a", rows_f, d)
-        self._lin(s, cnn_attn.data_ptr(), fp.p(pre + "attn_proj.0.weight"), fp.p(pre + "attn_proj.0.bias"), a, rows_f, d,
-                  Cin, relu=1)
+        self._lin(s, cnn_attn.data_ptr(), *fp.wb(pre + "attn_proj.0."), a, rows_f, d, Cin, relu=1)
         ppre = ws.f("enc_ppre", rows_f, d)
         proj = ws.f("enc_proj", 1 + rows_f, d)          # row 0: cls_token, then the frame rows
         ln = trm.attn_proj[3]
-        check(lib.ac_dropadd_ln_fwd(a, None, fp.p(pre + "attn_proj.3.weight"), fp.p(pre + "attn_proj.3.bias"), ppre,
-                                    proj + 4 * d, 0, rows_f, 0, d, p[0], OP_ENC_PROJ, self._seed_ptr, float(ln.eps), s),
-              "ac_dropadd_ln_fwd(enc proj)")
+        check(lib.ac_dropadd_ln_fwd(a, None, *fp.wb(pre + "attn_proj.3."), ppre, proj + 4 * d, 0, rows_f, 0, d, p[0],
+                                    OP_ENC_PROJ, self._seed_ptr, float(ln.eps), s), "ac_dropadd_ln_fwd(enc proj)")
         check(lib.ac_gather_rows(fp.p(pre + "cls_token"), el["zero"], proj, 1, d, s), "ac_gather_rows(cls)")
         x = ws.f("enc_x0", Re, d)
         check(lib.ac_gather_rows(proj, el["x0_src"], x, Re, d, s), "ac_gather_rows(enc x0)")
@@ -719,25 +786,15 @@ class TrainEngine:
             lp = f"{pre}model.layers.{l}."
             op = OP_ENC_LAYER + 10 * l
             pa, pd1, pf, pd2 = p[1 + l]
-            b = {k: ws.f(f"enc_{k}{l}", Re, w) for k, w in (("qkv", 3 * d), ("ctx", d), ("sa", d), ("pre1", d), ("x1", d),
-                                                            ("hdn", Fe), ("ff", d), ("pre2", d), ("x2", d))}
-            b["x"], b["P"] = x, ws.f(f"enc_P{l}", N * nh * L * L)
-            qkv = b["qkv"]
-            self._lin(s, x, fp.p(lp + "self_attn.in_proj_weight"), fp.p(lp + "self_attn.in_proj_bias"), qkv, Re, 3 * d, d)
-            check(lib.ac_attn_seq_fwd(qkv, 3 * d, qkv + 4 * d, 3 * d, qkv + 8 * d, 3 * d, b["ctx"], d, b["P"], L, L,
-                                      el["row0"], el["len"], el["row0"], el["len"], kvalid, None, 0, 0, 0, N, nh, 64, L, L,
-                                      pa, op + 0, self._seed_ptr, s), "ac_attn_seq_fwd(enc)")
-            self._lin(s, b["ctx"], fp.p(lp + "self_attn.out_proj.weight"), fp.p(lp + "self_attn.out_proj.bias"), b["sa"],
-                      Re, d, d)
-            check(lib.ac_dropadd_ln_fwd(b["sa"], x, fp.p(lp + "norm1.weight"), fp.p(lp + "norm1.bias"), b["pre1"], b["x1"],
-                                        0, Re, 0, d, pd1, op + 1, self._seed_ptr, float(ly.norm1.eps), s), "enc ln1")
-            self._lin(s, b["x1"], fp.p(lp + "linear1.weight"), fp.p(lp + "linear1.bias"), b["hdn"], Re, Fe, d, relu=1,
-                      drop_p=pf, seed=op + 2, row0=0)
-            self._lin(s, b["hdn"], fp.p(lp + "linear2.weight"), fp.p(lp + "linear2.bias"), b["ff"], Re, d, Fe)
-            check(lib.ac_dropadd_ln_fwd(b["ff"], b["x1"], fp.p(lp + "norm2.weight"), fp.p(lp + "norm2.bias"), b["pre2"],
-                                        b["x2"], 0, Re, 0, d, pd2, op + 3, self._seed_ptr, float(ly.norm2.eps), s), "enc ln2")
+            b = {k: ws.f(f"enc_{n}{l}", Re, w) for k, n, w in (
+                ("qkv", "qkv", 3 * d), ("ctx", "ctx", d), ("sa", "sa", d), ("pre1", "pre1", d), ("x1", "x1", d),
+                ("hdn", "hdn", Fe), ("ff", "ff", d), ("pre_ff", "pre2", d), ("x_out", "x2", d))}
+            b["x_in"], b["P"] = x, ws.f(f"enc_P{l}", N * nh * L * L)
+            self._self_attn_fwd(s, lp, b, 0, Re, (b["P"], L, L, el["row0"], el["len"], el["row0"], el["len"], kvalid, None,
+                                                  0, 0, 0, N, nh, 64, L, L, pa, op + 0), pd1, op + 1, float(ly.norm1.eps))
+            self._ffn_fwd(s, lp, "norm2.", b, b["x1"], 0, Re, Fe, pf, op + 2, pd2, op + 3, float(ly.norm2.eps))
             layers.append(b)
-            x = b["x2"]
+            x = b["x_out"]
         st["enc"] = {"a": a, "ppre": ppre, "layers": layers, "out": x}
         return x
 
@@ -798,11 +855,11 @@ class TrainEngine:
         self._phase = "forward"
         ws, lay, c = st["ws"], st["lay"], st["ctx"]
         N, T, Tc = st["N"], st["T"], st["Tc"]
-        V, F, acts, kv, P1, P2, x0, word = st["V"], st["F"], st["acts"], st["kv"], st["P1"], st["P2"], st["x0"], st["word"]
+        V, F, acts, word = st["V"], st["F"], st["acts"], st["word"]
         p_dec, teacher_forcing = st["p_dec"], st["teacher_forcing"]
         passes = lay["passes"]
         NP = len(passes)
-        nlay, nh, Tm = dec.nlayers, dec.nhead, c["Tm"]
+        nh, Tm = dec.nhead, c["Tm"]
         dp = "decoder."
         off = passes[ta][1]
         nr = sum(N * passes[t][0] for t in range(ta, tb))
@@ -814,42 +871,24 @@ class TrainEngine:
             L, off_t = passes[t]
             check(lib.ac_build_prefix(cap_p, Tc, c["seq"], T, ucap_ptr, 0 if teacher_forcing else t, model.start_idx, word,
                                       off_t, N, L, s), "ac_build_prefix")
-        check(lib.ac_embed_fwd(c["emb"], c["pe"], word, c["pos"], x0, off, nr, D, p_dec, OP_EMB_A, p_dec, OP_EMB_B,
-                               self._seed_ptr, s), "ac_embed_fwd")
+        check(lib.ac_embed_fwd(c["emb"], c["pe"], word, c["pos"], acts[0]["x_in"], off, nr, D, p_dec, OP_EMB_A, p_dec,
+                               OP_EMB_B, self._seed_ptr, s), "ac_embed_fwd")
         qrow0, qlen, mrow0, mklen, mvalid = c["qrow0"], c["qlen"], c["mrow0"], c["mklen"], c["mvalid"]
-        x = x0
-        for l in range(nlay):
+        for l, a in enumerate(acts):
             lp = f"{dp}model.layers.{l}."
-            a = acts[l]
             op = OP_LAYER + 10 * l
-            qkv = a["qkv"] + 4 * off * 3 * D
-            self._lin(s, x + o4, fp.p(lp + "self_attn.in_proj_weight"), fp.p(lp + "self_attn.in_proj_bias"), qkv, nr,
-                      3 * D, D)
-            check(lib.ac_attn_seq_fwd(a["qkv"], 3 * D, a["qkv"] + 4 * D, 3 * D, a["qkv"] + 8 * D, 3 * D, a["ctx1"], D,
-                                      P1[l], T, T, qrow0, qlen, qrow0, qlen, None, word, model.pad_idx, 1, seq0, nseq, nh,
-                                      64, lmax, lmax, p_dec, op + 0, self._seed_ptr, s), "ac_attn_seq_fwd")
-            self._lin(s, a["ctx1"] + o4, fp.p(lp + "self_attn.out_proj.weight"), fp.p(lp + "self_attn.out_proj.bias"),
-                      a["sa"] + o4, nr, D, D)
-            check(lib.ac_dropadd_ln_fwd(a["sa"], x, fp.p(lp + "norm1.weight"), fp.p(lp + "norm1.bias"), a["pre1"],
-                                        a["x1"], off, nr, 0, D, p_dec, op + 1, self._seed_ptr, 1e-5, s), "ln1")
-            self._lin(s, a["x1"] + o4, fp.p(lp + "multihead_attn.in_proj_weight"),
-                      fp.p(lp + "multihead_attn.in_proj_bias"), a["q2"] + o4, nr, D, D)
-            check(lib.ac_attn_seq_fwd(a["q2"], D, kv[l], 2 * D, kv[l] + 4 * D, 2 * D, a["ctx2"], D, P2[l], T, Tm, qrow0,
-                                      qlen, mrow0, mklen, mvalid, None, 0, 0, seq0, nseq, nh, 64, lmax, Tm, p_dec, op + 2,
-                                      self._seed_ptr, s), "ac_attn_seq_fwd(cross)")
-            self._lin(s, a["ctx2"] + o4, fp.p(lp + "multihead_attn.out_proj.weight"),
-                      fp.p(lp + "multihead_attn.out_proj.bias"), a["ca"] + o4, nr, D, D)
-            check(lib.ac_dropadd_ln_fwd(a["ca"], a["x1"], fp.p(lp + "norm2.weight"), fp.p(lp + "norm2.bias"),
-                                        a["pre2"], a["x2"], off, nr, 0, D, p_dec, op + 3, self._seed_ptr, 1e-5, s),
-                  "ln2")
-            self._lin(s, a["x2"] + o4, fp.p(lp + "linear1.weight"), fp.p(lp + "linear1.bias"),
-                      a["hdn"] + 4 * off * F, nr, F, D, relu=1, drop_p=p_dec, seed=op + 4, row0=off)
-            self._lin(s, a["hdn"] + 4 * off * F, fp.p(lp + "linear2.weight"), fp.p(lp + "linear2.bias"), a["ff"] + o4,
-                      nr, D, F)
-            check(lib.ac_dropadd_ln_fwd(a["ff"], a["x2"], fp.p(lp + "norm3.weight"), fp.p(lp + "norm3.bias"),
-                                        a["pre3"], a["x3"], off, nr, 0, D, p_dec, op + 5, self._seed_ptr, 1e-5, s),
-                  "ln3")
-            x = a["x3"]
+            self._self_attn_fwd(s, lp, a, off, nr, (a["P"], T, T, qrow0, qlen, qrow0, qlen, None, word, model.pad_idx, 1,
+                                                    seq0, nseq, nh, 64, lmax, lmax, p_dec, op + 0), p_dec, op + 1, 1e-5)
+            # cross-attention over the audio memory (its keys and values: a["kv"], projected once for all passes)
+            self._lin(s, a["x1"] + o4, *fp.wb(lp + "multihead_attn.in_proj_"), a["q2"] + o4, nr, D, D)
+            check(lib.ac_attn_seq_fwd(a["q2"], D, a["kv"], 2 * D, a["kv"] + 4 * D, 2 * D, a["ctx2"], D, a["P2"], T, Tm,
+                                      qrow0, qlen, mrow0, mklen, mvalid, None, 0, 0, seq0, nseq, nh, 64, lmax, Tm, p_dec,
+                                      op + 2, self._seed_ptr, s), "ac_attn_seq_fwd(cross)")
+            self._lin(s, a["ctx2"] + o4, *fp.wb(lp + "multihead_attn.out_proj."), a["ca"] + o4, nr, D, D)
+            check(lib.ac_dropadd_ln_fwd(a["ca"], a["x1"], *fp.wb(lp + "norm2."), a["pre2"], a["x2"], off, nr, 0, D, p_dec,
+                                        op + 3, self._seed_ptr, 1e-5, s), "ac_dropadd_ln_fwd(norm2)")
+            self._ffn_fwd(s, lp, "norm3.", a, a["x2"], off, nr, F, p_dec, op + 4, p_dec, op + 5, 1e-5)
+        x = acts[-1]["x_out"]
         logit, seq, cls = c["logit"], c["seq"], c["cls"]
         if teacher_forcing:
             self._lin(s, x, cls, None, logit, N * T, V, D)
@@ -904,14 +943,13 @@ class TrainEngine:
         backward: through time of the three GRU layers, or through the Transformer encoder) - so that the all-reduce of the decoder's gradients can run under the GRU's."""
         if part == "gru":
             return self._launch_backward_enc(sv)
-        model, lib, fp = self.model, self.lib, self.flat
-        enc, dec = model.encoder, model.decoder
+        lib, fp, dec = self.lib, self.flat, self.model.decoder
         s = _lib.stream()
         self._phase = "backward"
         ws, lay = sv["ws"], sv["lay"]
         N, T, Tq, V, F = sv["N"], sv["T"], sv["Tq"], sv["V"], sv["F"]
         B, Tm = N, sv["Tm"]
-        p_dec, p_rnn = sv["p_dec"], sv["p_rnn"]
+        p_dec = sv["p_dec"]
         R, S = lay["R"], lay["S"]
         NP = len(lay["passes"])
         rows_m = N * Tm
@@ -921,109 +959,61 @@ class TrainEngine:
         dp = "decoder."
         fp.grad.zero_()
         self._seed_ptr = sv["small"].data_ptr()
-        side = self._side = getattr(self, "_side", None) or _SideStream()
+        side = self._side
         qrow0, qlen = lay["qrow0"].data_ptr(), lay["qlen"].data_ptr()
         mrow0, mklen = lay["mrow0"].data_ptr(), lay["mklen"].data_ptr()
         cls_rows = lay["cls_rows"].data_ptr()
         NT = N * T
 
         # ---- classifier --------------------------------------------------------------------------------
-        xtop = sv["acts"][-1]["x3"]
-        xlast = ws.f("xlast", NT, D)
-        check(lib.ac_gather_rows(xtop, cls_rows, xlast, NT, D, s), "ac_gather_rows")
-        self._lin_dw(side.fork(), dl, V, xlast, D, fp.g(dp + "classifier.weight"), NT, V, D)
-        dxlast = ws.f("dxlast", NT, D)
-        self._lin_dx(s, dl, fp.p(dp + "classifier.weight"), dxlast, NT, V, D)
+        xlast, dxlast = ws.f("xlast", NT, D), ws.f("dxlast", NT, D)
+        check(lib.ac_gather_rows(sv["acts"][-1]["x_out"], cls_rows, xlast, NT, D, s), "ac_gather_rows")
+        self._lin_bwd(s, side, dl, xlast, fp.p(dp + "classifier.weight"), fp.g(dp + "classifier.weight"), None, NT, V, D,
+                      dx=dxlast)
         dx = ws.f("dx_a", R, D)
         dres = ws.f("dx_b", R, D)
         ws.tensor("dx_a")[:R * D].zero_()
         check(lib.ac_scatter_add_rows(dxlast, cls_rows, dx, NT, D, s), "ac_scatter_add_rows")
-        dsub = ws.f("dsub", R, D)
-        dhdn = ws.f("dhdn", R, F)
-        dctx = ws.f("dctx", R, D)
-        dq2 = ws.f("dq2", R, D)
-        dqkv = ws.f("dqkv", R, 3 * D)
+        g = {k: ws.f(k, R, w) for k, w in (("dsub", D), ("dhdn", F), ("dctx", D), ("dq2", D), ("dqkv", 3 * D))}
+        dsub, dctx, dq2 = g["dsub"], g["dctx"], g["dq2"]
         dmem = ws.f("dmem", Rm, D)
         dkv = ws.f("dkv", Rm, 2 * D)
-        scale = 1.0 / (1.0 - p_dec) if p_dec > 0 else 1.0
         for l in reversed(range(nlay)):
             lp = f"{dp}model.layers.{l}."
             a = sv["acts"][l]
             op = OP_LAYER + 10 * l
-            x_in = sv["x0"] if l == 0 else sv["acts"][l - 1]["x3"]
-            # norm3 / feed-forward
-            side.join()   # dsub (and, a layer on, dhdn / dq2 / dkv / dqkv) are about to be written again
-            check(lib.ac_dropadd_ln_bwd(dx, a["pre3"], fp.p(lp + "norm3.weight"), dsub, dres, 0, None, 0,
-                                        fp.g(lp + "norm3.weight"), fp.g(lp + "norm3.bias"), R, D, p_dec, op + 5,
-                                        self._seed_ptr, 1e-5, s), "ln3 bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dsub, D, a["hdn"], F, fp.g(lp + "linear2.weight"), R, D, F)
-            self._colsum(s2, dsub, D, fp.g(lp + "linear2.bias"), R, D)
-            self._lin_dx(s, dsub, fp.p(lp + "linear2.weight"), dhdn, R, D, F)
-            check(lib.ac_mask_pos_scale(dhdn, a["hdn"], R * F, scale, s), "ac_mask_pos_scale")
-            s2 = side.fork()
-            self._lin_dw(s2, dhdn, F, a["x2"], D, fp.g(lp + "linear1.weight"), R, F, D)
-            self._colsum(s2, dhdn, F, fp.g(lp + "linear1.bias"), R, F)
-            self._lin_dx(s, dhdn, fp.p(lp + "linear1.weight"), dres, R, F, D, beta=1.0)
-            dx, dres = dres, dx                                   # dx = d(x2)
-            # norm2 / cross attention
+            dx, dres = self._ffn_bwd(s, side, lp, "norm3.", a, a["x2"], g, dx, dres, R, F, p_dec, p_dec, op + 5, 1e-5)
+            # norm2 / cross attention: the query third of the in-projection over the R decoder rows, the key / value two
+            # thirds over the Rm memory rows - both weight gradients behind ONE fork
             side.join()
-            check(lib.ac_dropadd_ln_bwd(dx, a["pre2"], fp.p(lp + "norm2.weight"), dsub, dres, 0, None, 0,
-                                        fp.g(lp + "norm2.weight"), fp.g(lp + "norm2.bias"), R, D, p_dec, op + 3,
-                                        self._seed_ptr, 1e-5, s), "ln2 bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dsub, D, a["ctx2"], D, fp.g(lp + "multihead_attn.out_proj.weight"), R, D, D)
-            self._colsum(s2, dsub, D, fp.g(lp + "multihead_attn.out_proj.bias"), R, D)
-            self._lin_dx(s, dsub, fp.p(lp + "multihead_attn.out_proj.weight"), dctx, R, D, D)
-            kvl = sv["kv"][l]
-            check(lib.ac_attn_seq_bwd(a["q2"], D, kvl, 2 * D, kvl + 4 * D, 2 * D, sv["P2"][l], T, Tm, dctx, D, dq2, D, dkv,
+            self._ln_bwd(s, lp + "norm2.", dx, a["pre2"], dsub, dres, R, p_dec, op + 3, 1e-5)
+            self._lin_bwd(s, side, dsub, a["ctx2"], *fp.wgb(lp + "multihead_attn.out_proj."), R, D, D, dx=dctx)
+            kvl = a["kv"]
+            check(lib.ac_attn_seq_bwd(a["q2"], D, kvl, 2 * D, kvl + 4 * D, 2 * D, a["P2"], T, Tm, dctx, D, dq2, D, dkv,
                                       2 * D, dkv + 4 * D, 2 * D, qrow0, qlen, mrow0, mklen, 0, S, nh, 64, T, Tm, p_dec,
                                       op + 2, self._seed_ptr, s), "ac_attn_seq_bwd(cross)")
-            w_in, g_in = fp.p(lp + "multihead_attn.in_proj_weight"), fp.g(lp + "multihead_attn.in_proj_weight")
-            b_in_g = fp.g(lp + "multihead_attn.in_proj_bias")
-            s2 = side.fork()
-            self._lin_dw(s2, dq2, D, a["x1"], D, g_in, R, D, D)
-            self._colsum(s2, dq2, D, b_in_g, R, D)
-            self._lin_dw(s2, dkv, 2 * D, sv["mem"], D, g_in + 4 * D * D, Rm, 2 * D, D)
-            self._colsum(s2, dkv, 2 * D, b_in_g + 4 * D, Rm, 2 * D)
+            w_in, g_in, b_in_g = fp.wgb(lp + "multihead_attn.in_proj_")
+            s2 = self._lin_bwd(s, side, dq2, a["x1"], w_in, g_in, b_in_g, R, D, D)
+            self._lin_bwd(s, side, dkv, sv["mem"], w_in, g_in + 4 * D * D, b_in_g + 4 * D, Rm, 2 * D, D, s2=s2)
             self._lin_dx(s, dq2, w_in, dres, R, D, D, beta=1.0)
             self._lin_dx(s, dkv, w_in + 4 * D * D, dmem, Rm, 2 * D, D, beta=0.0 if l == nlay - 1 else 1.0)
             dx, dres = dres, dx                                   # dx = d(x1)
-            # norm1 / self attention
-            side.join()
-            check(lib.ac_dropadd_ln_bwd(dx, a["pre1"], fp.p(lp + "norm1.weight"), dsub, dres, 0, None, 0,
-                                        fp.g(lp + "norm1.weight"), fp.g(lp + "norm1.bias"), R, D, p_dec, op + 1,
-                                        self._seed_ptr, 1e-5, s), "ln1 bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dsub, D, a["ctx1"], D, fp.g(lp + "self_attn.out_proj.weight"), R, D, D)
-            self._colsum(s2, dsub, D, fp.g(lp + "self_attn.out_proj.bias"), R, D)
-            self._lin_dx(s, dsub, fp.p(lp + "self_attn.out_proj.weight"), dctx, R, D, D)
-            check(lib.ac_attn_seq_bwd(a["qkv"], 3 * D, a["qkv"] + 4 * D, 3 * D, a["qkv"] + 8 * D, 3 * D, sv["P1"][l], T, T,
-                                      dctx, D, dqkv, 3 * D, dqkv + 4 * D, 3 * D, dqkv + 8 * D, 3 * D, qrow0, qlen, qrow0,
-                                      qlen, 0, S, nh, 64, T, T, p_dec, op + 0, self._seed_ptr, s), "ac_attn_seq_bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dqkv, 3 * D, x_in, D, fp.g(lp + "self_attn.in_proj_weight"), R, 3 * D, D)
-            self._colsum(s2, dqkv, 3 * D, fp.g(lp + "self_attn.in_proj_bias"), R, 3 * D)
-            self._lin_dx(s, dqkv, fp.p(lp + "self_attn.in_proj_weight"), dres, R, 3 * D, D, beta=1.0)
-            dx, dres = dres, dx                                   # dx = d(layer input)
+            dx, dres = self._self_attn_bwd(s, side, lp, a, g, dx, dres, R, (
+                "ac_attn_seq_bwd", (a["P"], T, T), (qrow0, qlen, qrow0, qlen, 0, S, nh, 64, T, T, p_dec, op + 0), ()),
+                p_dec, op + 1, 1e-5)
         side.join()   # the embedding's gradient may be the classifier's (tied weights): no two writers at once
         check(lib.ac_embed_bwd(dx, sv["word"], fp.g(dp + "word_embedding.weight"), R, D, p_dec, OP_EMB_A, p_dec, OP_EMB_B,
                                self._seed_ptr, s), "ac_embed_bwd")
 
         # ---- audio memory -> attn_proj -> GRU output ---------------------------------------------------
         da_rep = ws.f("da_rep", Rm, D)
-        check(lib.ac_dropadd_ln_bwd(dmem, sv["mem_pre"], fp.p(dp + "attn_proj.3.weight"), da_rep, None, 0, sv["mem_a"],
-                                    rows_m, fp.g(dp + "attn_proj.3.weight"), fp.g(dp + "attn_proj.3.bias"), Rm, D, p_dec,
-                                    OP_MEM, self._seed_ptr, 1e-5, s), "mem ln bwd")
+        self._ln_bwd(s, dp + "attn_proj.3.", dmem, sv["mem_pre"], da_rep, None, Rm, p_dec, OP_MEM, 1e-5, sv["mem_a"], rows_m)
         da = ws.f("da", rows_m, D)
         check(lib.ac_sum_replicas(da_rep, da, rows_m * D, NP, s), "ac_sum_replicas")
         A = self.enc_width
-        s2 = side.fork()
-        self._lin_dw(s2, da, D, sv["attn_emb"], A, fp.g(dp + "attn_proj.0.weight"), rows_m, D, A)
-        self._colsum(s2, da, D, fp.g(dp + "attn_proj.0.bias"), rows_m, D)
         # d(loss)/d(encoder output): the GRU's (B*T' rows) or the Transformer encoder's (B*(T'+1) rows)
         dout = ws.f("enc_dout", rows_m, A) if self.enc_kind == "trm" else ws.f("gru_dout", B * Tq, A)
-        self._lin_dx(s, da, fp.p(dp + "attn_proj.0.weight"), dout, rows_m, D, A)
+        self._lin_bwd(s, side, da, sv["attn_emb"], *fp.wgb(dp + "attn_proj.0."), rows_m, D, A, dx=dout)
         if part == "all":
             self._launch_backward_enc(sv)
         side.join()   # every decoder gradient is final (the all-reduce of part "head" reads them next)
@@ -1043,65 +1033,30 @@ class TrainEngine:
         self._seed_ptr = sv["small"].data_ptr()
         el = self._enc_layout(sv)
         e = sv["enc"]
-        side = self._side = getattr(self, "_side", None) or _SideStream()
+        side = self._side
         pre = "encoder.trm."
         dx, dres = ws.f("enc_dout", Re, d), ws.f("enc_dres", Re, d)
-        dsub, dctx = ws.f("enc_dsub", Re, d), ws.f("enc_dctx", Re, d)
-        dhdn, dqkv = ws.f("enc_dhdn", Re, Fe), ws.f("enc_dqkv", Re, 3 * d)
+        g = {k: ws.f("enc_" + k, Re, w) for k, w in (("dsub", d), ("dctx", d), ("dhdn", Fe), ("dqkv", 3 * d))}
         for l in reversed(range(len(trm.model.layers))):
             ly = trm.model.layers[l]
             lp = f"{pre}model.layers.{l}."
             op = OP_ENC_LAYER + 10 * l
             pa, pd1, pf, pd2 = p[1 + l]
             b = e["layers"][l]
-            # norm2 / feed-forward
-            side.join()   # dsub / dhdn / dqkv are about to be written again
-            check(lib.ac_dropadd_ln_bwd(dx, b["pre2"], fp.p(lp + "norm2.weight"), dsub, dres, 0, None, 0,
-                                        fp.g(lp + "norm2.weight"), fp.g(lp + "norm2.bias"), Re, d, pd2, op + 3,
-                                        self._seed_ptr, float(ly.norm2.eps), s), "enc ln2 bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dsub, d, b["hdn"], Fe, fp.g(lp + "linear2.weight"), Re, d, Fe)
-            self._colsum(s2, dsub, d, fp.g(lp + "linear2.bias"), Re, d)
-            self._lin_dx(s, dsub, fp.p(lp + "linear2.weight"), dhdn, Re, d, Fe)
-            check(lib.ac_mask_pos_scale(dhdn, b["hdn"], Re * Fe, 1.0 / (1.0 - pf) if pf > 0 else 1.0, s),
-                  "ac_mask_pos_scale")
-            s2 = side.fork()
-            self._lin_dw(s2, dhdn, Fe, b["x1"], d, fp.g(lp + "linear1.weight"), Re, Fe, d)
-            self._colsum(s2, dhdn, Fe, fp.g(lp + "linear1.bias"), Re, Fe)
-            self._lin_dx(s, dhdn, fp.p(lp + "linear1.weight"), dres, Re, Fe, d, beta=1.0)
-            dx, dres = dres, dx                                   # dx = d(x1)
-            # norm1 / self-attention
-            side.join()
-            check(lib.ac_dropadd_ln_bwd(dx, b["pre1"], fp.p(lp + "norm1.weight"), dsub, dres, 0, None, 0,
-                                        fp.g(lp + "norm1.weight"), fp.g(lp + "norm1.bias"), Re, d, pd1, op + 1,
-                                        self._seed_ptr, float(ly.norm1.eps), s), "enc ln1 bwd")
-            s2 = side.fork()
-            self._lin_dw(s2, dsub, d, b["ctx"], d, fp.g(lp + "self_attn.out_proj.weight"), Re, d, d)
-            self._colsum(s2, dsub, d, fp.g(lp + "self_attn.out_proj.bias"), Re, d)
-            self._lin_dx(s, dsub, fp.p(lp + "self_attn.out_proj.weight"), dctx, Re, d, d)
-            qkv = b["qkv"]
-            check(lib.ac_attn_self_bwd_tiled(qkv, 3 * d, qkv + 4 * d, 3 * d, qkv + 8 * d, 3 * d, b["P"], L, L, dctx, d,
-                                             dqkv, 3 * d, dqkv + 4 * d, 3 * d, dqkv + 8 * d, 3 * d, el["row0"], el["len"],
-                                             el["row0"], el["len"], 0, N, nh, 64, L, L, pa, op + 0, self._seed_ptr,
-                                             ws.f("enc_attn_D", N * nh * L), s),
-                  "ac_attn_self_bwd_tiled")
-            s2 = side.fork()
-            self._lin_dw(s2, dqkv, 3 * d, b["x"], d, fp.g(lp + "self_attn.in_proj_weight"), Re, 3 * d, d)
-            self._colsum(s2, dqkv, 3 * d, fp.g(lp + "self_attn.in_proj_bias"), Re, 3 * d)
-            self._lin_dx(s, dqkv, fp.p(lp + "self_attn.in_proj_weight"), dres, Re, 3 * d, d, beta=1.0)
-            dx, dres = dres, dx                                   # dx = d(layer input)
+            dx, dres = self._ffn_bwd(s, side, lp, "norm2.", b, b["x1"], g, dx, dres, Re, Fe, pf, pd2, op + 3,
+                                     float(ly.norm2.eps))
+            dx, dres = self._self_attn_bwd(s, side, lp, b, g, dx, dres, Re, (
+                "ac_attn_self_bwd_tiled", (b["P"], L, L),
+                (el["row0"], el["len"], el["row0"], el["len"], 0, N, nh, 64, L, L, pa, op + 0),
+                (ws.f("enc_attn_D", N * nh * L),)), pd1, op + 1, float(ly.norm1.eps))
         # cls_token: row 0 of every clip; the frame rows go back through attn_proj's LayerNorm, dropout and ReLU
         self._colsum(s, dx, L * d, fp.g(pre + "cls_token"), N, d)
         dproj, da = ws.f("enc_dproj", rows_f, d), ws.f("enc_da", rows_f, d)
         check(lib.ac_gather_rows(dx, el["proj_src"], dproj, rows_f, d, s), "ac_gather_rows(enc dproj)")
-        check(lib.ac_dropadd_ln_bwd(dproj, e["ppre"], fp.p(pre + "attn_proj.3.weight"), da, None, 0, e["a"], 0,
-                                    fp.g(pre + "attn_proj.3.weight"), fp.g(pre + "attn_proj.3.bias"), rows_f, d, p[0],
-                                    OP_ENC_PROJ, self._seed_ptr, float(trm.attn_proj[3].eps), s), "enc proj ln bwd")
+        self._ln_bwd(s, pre + "attn_proj.3.", dproj, e["ppre"], da, None, rows_f, p[0], OP_ENC_PROJ,
+                     float(trm.attn_proj[3].eps), e["a"], 0)
         cnn_attn = sv["cnn_attn"]
-        s2 = side.fork()
-        self._lin_dw(s2, da, d, cnn_attn.data_ptr(), cnn_attn.shape[2], fp.g(pre + "attn_proj.0.weight"), rows_f, d,
-                     cnn_attn.shape[2])
-        self._colsum(s2, da, d, fp.g(pre + "attn_proj.0.bias"), rows_f, d)
+        self._lin_bwd(s, side, da, cnn_attn.data_ptr(), *fp.wgb(pre + "attn_proj.0."), rows_f, d, cnn_attn.shape[2])
         side.join()
 
     def _launch_backward_enc(self, sv):
@@ -1120,7 +1075,7 @@ class TrainEngine:
         dout = ws.f("gru_dout", rows_g, A)
         lens_p = sv["small"].data_ptr() + 8
         nl = enc.rnn.num_layers
-        side = self._side = getattr(self, "_side", None) or _SideStream()
+        side = self._side
         pre = "encoder.rnn.network."
         for l in reversed(range(nl)):
             g = sv["gru"][l]
@@ -1344,42 +1299,34 @@ class TrainEngine:
         return {"loss": st["ws"].tensor("loss")[0], "total_norm": clip.total_norm, "logit": out["logit"],
                 "seq": out.get("seq"), "skipped_updates": self._skipped[0]}
 
+    def _gru_error_word(self, st):
+        """The split-GRU kernel's sticky error word of this engine's workspace as a 1-element int32 device view, or None."""
+        if self.gru_algo != "split" or not st.get("gru_xch_zeroed"):
+            return None
+        return st["ws"].tensor("gru_xch").view(torch.int32)[:1]
 
-def _gru_error_word(self, st):
-    """The split-GRU kernel's sticky error word of this engine's workspace as a 1-element int32 device view, or None."""
-    if self.gru_algo != "split" or not st.get("gru_xch_zeroed"):
-        return None
-    return st["ws"].tensor("gru_xch").view(torch.int32)[:1]
-
-
-def gru_timeout(self):
-    """True if a split-GRU launch of this engine timed out waiting for a partner workgroup since the last call (reads the
-    device: synchronises).  ``step`` folds the kernel's error word into that iteration's skip flag and clears it, counting
-    the hits; a word raised by a forward that no ``step`` followed is picked up here.  The affected iterations' updates
-    were skipped on the device (on every rank under DDP)."""
-    hit = False
-    cnt = getattr(self, "_gru_timeouts", None)
-    if cnt is not None and float(cnt.item()) != 0.0:
-        hit = True
-        cnt.zero_()
-    for st in self._states.values():
-        err = _gru_error_word(self, st)
-        if err is not None and int(err.item()) != 0:
+    def gru_timeout(self):
+        """True if a split-GRU launch of this engine timed out waiting for a partner workgroup since the last call (reads the
+        device: synchronises).  ``step`` folds the kernel's error word into that iteration's skip flag and clears it, counting
+        the hits; a word raised by a forward that no ``step`` followed is picked up here.  The affected iterations' updates
+        were skipped on the device (on every rank under DDP)."""
+        hit = False
+        cnt = getattr(self, "_gru_timeouts", None)
+        if cnt is not None and float(cnt.item()) != 0.0:
             hit = True
-            err.zero_()
-    return hit
+            cnt.zero_()
+        for st in self._states.values():
+            err = self._gru_error_word(st)
+            if err is not None and int(err.item()) != 0:
+                hit = True
+                err.zero_()
+        return hit
 
-
-def skipped_updates(self):
-    """Optimiser updates ``step`` has skipped on the device so far (non-finite gradient norm, run.py:123, or a split-GRU
-    partner timeout); reads the device."""
-    c = getattr(self, "_skipped", None)
-    return int(c.item()) if c is not None else 0
-
-
-TrainEngine._gru_error_word = _gru_error_word
-TrainEngine.gru_timeout = gru_timeout
-TrainEngine.skipped_updates = skipped_updates
+    def skipped_updates(self):
+        """Optimiser updates ``step`` has skipped on the device so far (non-finite gradient norm, run.py:123, or a split-GRU
+        partner timeout); reads the device."""
+        c = getattr(self, "_skipped", None)
+        return int(c.item()) if c is not None else 0
 
 
 class _TrainBridge(torch.autograd.Function):
