@@ -8,7 +8,9 @@ The torch.nn sub-modules below only OWN the parameters (so checkpoints, ``.to()`
 log-mel -> bn0 -> 12 x (conv3x3 + BN + ReLU [+ pool]) -> mean over mel entirely in the HIP kernels of
 ``csrc/logmel.hip`` and ``csrc/conv3x3.hip`` and fails loudly if they are unavailable.
 """
+import dataclasses
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -51,13 +53,13 @@ def _wino1d_clip_chunk(B, Hp, W, Cin):
     return max(1, min(B, ((1 << 31) - 1) // (W * Cin * 4 * Hp) - 1))
 
 
-def _conv_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1, need=None, splitk_buf=None,
-                 dropout=None):
-    """The "wino1d" tier's launcher (``_pack`` packs a layer's weights for the kernel ``wino1d_covers`` names).
-    ``splitk_buf(floats) -> tensor``: workspace provider for the K-sliced launches of single clips.  A batch whose input
-    exceeds the kernel's 2 GiB addressing range is convolved in clip chunks (clips do not interact; rows are per clip)."""
-    if not wino1d_covers(Cout):
-        K.conv3x3_bn_relu_bf16x3_gw(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode)
+def _conv_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None,
+                 overflow=None, cold=False):
+    """The "wino1d" tier's launcher (``_pack_wino1d`` packs a layer's weights for the kernel ``wino1d_covers`` names; the
+    call signature is ``ConvTier.launch``).  A batch whose input exceeds the kernel's 2 GiB addressing range is convolved
+    in clip chunks (clips do not interact; rows are per clip)."""
+    if not wino1d_covers(Cout):   # (the direct kernel convolves every row: ``need`` is not used)
+        K.conv3x3_bn_relu_bf16x3_gw(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode)
         if dropout is not None:
             K.dropout_(out, out.numel() if mode != 1 else B * (Hp // 2) * (W // 2) * Cout, *dropout)
         return out
@@ -72,19 +74,18 @@ def _conv_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode
         for b0 in range(0, B, chunk):
             nb = min(chunk, B - b0)
             nd = (need[0][b0:b0 + nb], need[1], need[2]) if need is not None else None
-            _conv_wino1d(xf[b0 * in_clip:(b0 + nb) * in_clip], w, scale, shift, of[b0 * out_clip:(b0 + nb) * out_clip], nb, Hp, H, W,
-                         Cin, Cout, mode, map_mode, need=nd, splitk_buf=splitk_buf)
+            _conv_wino1d(xf[b0 * in_clip:(b0 + nb) * in_clip], w, scale, shift, of[b0 * out_clip:(b0 + nb) * out_clip], nb, Hp,
+                         H, W, Cin, Cout, mode, need=nd, workspace=workspace)
         return out
     if dropout is not None:   # F.dropout on the block's output in the kernel's epilogue (no extra pass over the buffer)
-        return K.conv3x3_bn_relu_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, dropout=dropout)
+        return K.conv3x3_bn_relu_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, dropout=dropout)
     ws = None
-    if splitk_buf is not None:
+    if workspace is not None:
         floats = K.wino1d_splitk_floats(B, Hp, W, Cin, Cout)
-        ws = splitk_buf(floats) if floats else None
-    return K.conv3x3_bn_relu_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need=need, workspace=ws)
+        ws = workspace(floats) if floats else None
+    return K.conv3x3_bn_relu_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=need, workspace=ws)
 
 
-WINO = ("wino43", "wino1d")   # the Winograd tiers: same layouts, epilogues, ragged-batch and dropout hooks
 W43_MIN_WORKGROUPS = int(os.environ.get("AUDIOCAPTION_W43_MIN_WG", "192"))
 
 
@@ -95,19 +96,24 @@ def wino43_covers(W, cout):
     return W in (32, 16, 8, 4, 2) and cout % 128 == 0
 
 
-def _conv_wino43(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1, need=None, splitk_buf=None,
-                 dropout=None, cold=False):
-    """The "wino43" tier's launcher: ``w`` is (F(2,3) pack, F(4,3) pack or None).  F(4,3) when the kernel covers the layer
-    and the launch fills the chip (a workgroup owns a CU: single clips run the K-sliced F(2,3) form instead)."""
-    w23, w43, lazy = (tuple(w) + (None,))[:3] if isinstance(w, tuple) else (w, None, None)
+class Wino43Pack(NamedTuple):
+    """The packs of one layer on the "wino43" tier."""
+    f23: torch.Tensor             # what ``_conv_wino1d`` launches: small launches (single clips) take the K-sliced F(2,3) form
+    f43: torch.Tensor = None      # F(4,3), where ``wino43_covers`` the layer
+    skinny: "_LazyPack" = None    # blocks 5-6 (W = 4, 2): the skinny form
+
+
+def _conv_wino43(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None,
+                 overflow=None, cold=False):
+    """The "wino43" tier's launcher (``w``: a ``Wino43Pack``).  F(4,3) when the kernel covers the layer and the launch fills
+    the chip (a workgroup owns a CU: single clips run the K-sliced F(2,3) form instead)."""
     # (AUDIOCAPTION_RAGGED_EXACT=1 only: batches of uneven lengths then keep block 6 on F(2,3) - the caller passes it the F(2,3)
     # pack only: its tiles are taller than a clip, nothing can be skipped there anyway, and the quad-wide input window of
     # F(4,3) would cost every layer upstream four more valid rows per clip - ``rows_needed``.  In the default mode ragged
     # batches run F(4,3) on block 6 too and valid frames are within 5e-5 of the dense run, not bit-identical)
-    if w43 is not None and (mode != 1 if W == 2 else mode != 2) and Hp % 4 == 0 \
+    if w.f43 is not None and (mode != 1 if W == 2 else mode != 2) and Hp % 4 == 0 \
             and K.wino43_workgroups(B, Hp, W, Cout) >= W43_MIN_WORKGROUPS:
-        return K.conv3x3_bn_relu_wino43(x, w43, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need=need,
-                                        dropout=dropout)
+        return K.conv3x3_bn_relu_wino43(x, w.f43, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=need, dropout=dropout)
     # Few pixels, heavy weights, COLD weights: blocks 5-6 in the training step at the reference's per-GPU batch of 4 - the
     # step touches a few hundred MB between two uses of these 360 MB of weights, so they come from HBM every iteration, and
     # the dropout epilogue of the F(2,3) kernel has no K-sliced form: 2 x 390 us for block 6 of four clips; the
@@ -115,14 +121,14 @@ def _conv_wino43(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode
     # per step).  Inference calls re-use the weights from the memory-side cache call after call, where the K-sliced F(2,3)
     # form is as fast or faster (B = 1: 36 + 61 us vs 27 + 55 for block 6, 34 + 48 vs 39 + 53 for block 5; B = 4: 116 vs
     # 165): they keep it.
-    if lazy is not None and need is None and splitk_buf is not None and SKINNY and (cold or dropout is not None) \
+    if w.skinny is not None and need is None and workspace is not None and SKINNY and (cold or dropout is not None) \
             and B * Hp * W <= SKINNY_MAX_PX:
         n = K.skinny_workspace_floats(B, Hp, W, Cin, Cout)
         if n > 0:
-            return K.conv3x3_bn_relu_skinny(x, lazy.get(), scale, shift, out, B, Hp, H, W, Cin, Cout, mode, splitk_buf(n),
+            return K.conv3x3_bn_relu_skinny(x, w.skinny.get(), scale, shift, out, B, Hp, H, W, Cin, Cout, mode, workspace(n),
                                             dropout=dropout)
-    return _conv_wino1d(x, w23, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need=need, splitk_buf=splitk_buf,
-                        dropout=dropout)
+    return _conv_wino1d(x, w.f23, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=need, dropout=dropout,
+                        workspace=workspace)
 
 
 # conv1 of block 1 inside the one-kernel block: "mfma" (split-bf16 product on the matrix cores) | "valu" (the f32 chain of
@@ -177,11 +183,100 @@ def rows_needed(block, conv, quads=False):
     return (mul, need) if conv == 2 else (mul, need + 4)
 
 
-def conv_kernel(algo):
-    """The launcher of a conv tier (``Cnn14.conv_algo``)."""
-    return {"winograd": K.conv3x3_bn_relu_winograd, "direct": K.conv3x3_bn_relu,
-            "bf16x3": K.conv3x3_bn_relu_bf16x3_gw, "bf16x3_lds": K.conv3x3_bn_relu_bf16x3,
-            "f16x2": K.conv3x3_bn_relu_f16x2_gw, "wino1d": _conv_wino1d, "wino43": _conv_wino43}[algo]
+@dataclasses.dataclass(frozen=True)
+class ConvTier:
+    """What a conv tier (``Cnn14Encoder.conv_algo``) is: how it packs a layer, how it launches one, and what callers may ask
+    of it.  ``pack(w, b, weight)``: OIHW f32 weights of a layer of conv block ``b`` (0..5), ``weight`` the parameter itself
+    -> (pack, inv_scale[Cout] to fold into the BN scale or None).  ``launch(x, pack, scale, shift, out, B, Hp, H, W, Cin,
+    Cout, mode, need=, dropout=, workspace=, overflow=, cold=)``: one layer, with all that ``conv_stack`` has for it; a
+    tier uses what it can and refuses ``need`` (``rows_needed`` of a ragged batch) / ``dropout`` when it cannot."""
+    pack: object
+    launch: object
+    act: torch.dtype = torch.float32   # activations of the stack in HBM
+    # block1(x0, conv1, conv2, pack, out, B, Hp, H, need, dropout, overflow) -> bool: conv block 1 in one kernel, from the
+    # (pack, scale, shift) of its two convs and ``pack = pack_block1(w of conv2)``, a pack only this kernel reads
+    # (AUDIOCAPTION_FUSE_BLOCK1=0: never); False: not for this launch
+    block1: object = None
+    pack_block1: object = None
+    skips_dead_rows: bool = False      # ragged batches: rows a clip's own length cannot bring to an output frame are not convolved
+    f43: bool = False                  # layers are ``Wino43Pack``s; F(4,3) reads row QUADS (``rows_needed(quads=)``)
+    dropout_epilogue: bool = False     # the block's F.dropout inside the conv kernel (else a separate pass)
+    overflow_word: bool = False        # fp16 activations: ``forward`` returns ``f16_overflow``
+    fallback: str = None               # the tier of the train-mode forward and of batches with a very short clip (``encode``)
+    block6: str = None                 # the tier conv block 6 runs on instead when ``Cnn14Encoder.f16x2_block6`` names it
+
+
+def _plain(kernel, takes_overflow=False):
+    """``ConvTier.launch`` of a tier whose kernel takes the layer and nothing else (the fp16 tier: and its overflow word)."""
+    def launch(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None, overflow=None,
+               cold=False):
+        if need is not None or dropout is not None:
+            raise ValueError("this conv tier has neither dead-row skipping nor a dropout epilogue")
+        if takes_overflow:
+            return kernel(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, overflow=overflow)
+        return kernel(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode)
+    return launch
+
+
+def _pack_with(pack):
+    return lambda w, b, weight: (pack(w), None)
+
+
+def _pack_wino1d(w, b, weight):
+    return (K.pack_conv_weight_wino1d_frag if wino1d_covers(w.shape[0]) else K.pack_conv_weight_bf16x3_frag)(w), None
+
+
+def _pack_wino43(w, b, weight):
+    return Wino43Pack(_pack_wino1d(w, b, weight)[0],
+                      K.pack_conv_weight_wino43_frag(w) if wino43_covers(64 >> b, w.shape[0]) else None,
+                      _LazyPack(weight) if b >= 4 else None), None
+
+
+def _block1_wino43(x0, conv1, conv2, f43, out, B, Hp, H, need, dropout, overflow):
+    """Conv block 1 in one kernel (conv1 computed into the F(4,3) staging of conv2) when the launch gives every CU a
+    persistent workgroup; single clips keep conv_first + the K-sliced F(2,3) form."""
+    if Hp % 8 != 0 or B * Hp // 8 < W43_MIN_WORKGROUPS:
+        return False
+    K.conv3x3_block1_wino43(x0, *conv1, f43, conv2[1], conv2[2], out, B, Hp, H, need=need, dropout=dropout,
+                            conv1=BLOCK1_CONV1)
+    return True
+
+
+def _block1_f16x2(x0, conv1, conv2, pack, out, B, Hp, H, need, dropout, overflow):
+    """conv1 is computed inside conv2's kernel: its 64-channel output never reaches HBM."""
+    K.conv3x3_block1_f16x2(x0, *conv1, *conv2, out, B, Hp, H, 64, overflow=overflow)
+    return True
+
+
+# "wino43" (default): Winograd along time on split-bf16 operands, f32 activations - f32-grade parity with the fp32
+# reference (logits within 1e-4, identical token ids): F(4,3) (1.5 bf16 MFMA products per f32 product) on conv blocks 2-5
+# when the launch fills the chip, F(2,3) (two products) elsewhere.  "wino1d": F(2,3) everywhere.  "bf16x3": the direct form
+# on split-bf16 operands, three products (same accuracy).  "f16x2" (opt-in, half-precision gate): fp16 activations (kept
+# as fp16 in HBM), fp16 hi + lo weights, two fp16 MFMA products - identical token ids, logits within 1e-3 (BASELINE.json's
+# half-precision bar), NOT reference precision; the train-mode forward never uses it.  "winograd": F(2x2,3x3) on the f32
+# MFMA, exact f32.  "direct": 9-tap f32 implicit GEMM.  "bf16x3_lds": bf16x3 with an LDS weight ring (kept for ablations).
+# The two Winograd tiers share layouts, epilogues, ragged-batch and dropout hooks.
+TIERS = {
+    "wino43": ConvTier(_pack_wino43, _conv_wino43, block1=_block1_wino43, pack_block1=K.pack_conv_weight_wino43_frag,
+                       skips_dead_rows=True, f43=True, dropout_epilogue=True),
+    "wino1d": ConvTier(_pack_wino1d, _conv_wino1d, skips_dead_rows=True, dropout_epilogue=True),
+    "bf16x3": ConvTier(_pack_with(K.pack_conv_weight_bf16x3_frag), _plain(K.conv3x3_bn_relu_bf16x3_gw)),
+    "bf16x3_lds": ConvTier(_pack_with(K.pack_conv_weight_bf16x3), _plain(K.conv3x3_bn_relu_bf16x3)),
+    # the fp16 pack scales every output channel by a power of two; its inverse goes into the BN scale.  The tier is MIXED:
+    # conv_block6 (K = 9216 / 18432, two pixels per frame to average over - half of the tier's logit error by the per-layer
+    # breakdown of DESIGN.md section 4) runs on the split-bf16 kernel with f32 activations
+    "f16x2": ConvTier(lambda w, b, weight: K.pack_conv_weight_f16x2_frag(w), _plain(K.conv3x3_bn_relu_f16x2_gw, True),
+                      act=torch.float16, block1=_block1_f16x2, overflow_word=True, fallback="bf16x3", block6="bf16x3"),
+    "winograd": ConvTier(_pack_with(K.pack_conv_weight_winograd), _plain(K.conv3x3_bn_relu_winograd)),
+    "direct": ConvTier(_pack_with(K.pack_conv_weight), _plain(K.conv3x3_bn_relu)),
+}
+
+
+def conv_tier(algo):
+    try:
+        return TIERS[algo]
+    except KeyError:
+        raise ValueError(f"unknown conv_algo {algo!r}") from None
 
 
 class Cnn14Encoder(nn.Module):
@@ -204,18 +299,10 @@ class Cnn14Encoder(nn.Module):
         nn.init.zeros_(self.fc1.bias)
         self.fc_emb_size = 2048
         self.freeze = freeze
-        # Conv tiers.  "wino43" (default): Winograd along time on split-bf16 operands, f32 activations - f32-grade parity
-        # with the fp32 reference (logits within 1e-4, identical token ids): F(4,3) (1.5 bf16 MFMA products per f32 product)
-        # on conv blocks 2-5 when the launch fills the chip, F(2,3) (two products) elsewhere.  "wino1d": F(2,3) everywhere.  "bf16x3": the direct form on split-bf16 operands, three products (same accuracy).  "f16x2" (opt-in,
-        # half-precision gate): fp16 activations (kept as fp16 in HBM), fp16 hi + lo weights, two fp16 MFMA products -
-        # identical token ids, logits within 1e-3 (BASELINE.json's half-precision bar), NOT reference precision.
-        # "winograd": F(2x2,3x3) on the f32 MFMA, exact f32.  "direct": 9-tap f32 implicit GEMM.  "bf16x3_lds": bf16x3
-        # with an LDS weight ring (kept for ablations).  The train-mode forward never uses "f16x2".
-        self.conv_algo = os.environ.get("AUDIOCAPTION_CONV_ALGO", "wino43")
+        self.conv_algo = os.environ.get("AUDIOCAPTION_CONV_ALGO", "wino43")   # the conv tier: a name of ``TIERS``
         self.f16x2_min_frames = int(os.environ.get("AUDIOCAPTION_F16X2_MIN_FRAMES", "10"))
-        # The "f16x2" tier is MIXED: conv_block6 (K = 9216 / 18432, two pixels per frame to average over - half of the
-        # tier's logit error by the per-layer breakdown of DESIGN.md section 4) runs on the split-bf16 kernel with f32
-        # activations; block 5's pooled output is then written as f32.  "f16x2" here restores the pure fp16 tier.
+        # The "f16x2" tier is MIXED (``ConvTier.block6``): block 6 runs on the split-bf16 kernel with f32 activations;
+        # block 5's pooled output is then written as f32.  "f16x2" here restores the pure fp16 tier.
         self.f16x2_block6 = os.environ.get("AUDIOCAPTION_F16X2_BLOCK6", "bf16x3")
         self._tables = None
         self._tables_key = None
@@ -246,58 +333,40 @@ class Cnn14Encoder(nn.Module):
     # ---- weight packing for the kernels (cached; invalidated by in-place updates / .to()) ----------
     def _pack(self, device, algo=None):
         algo = algo or self.conv_algo
+        tier = conv_tier(algo)
+        tier6 = conv_tier(tier.block6) if tier.block6 is not None and tier.block6 == self.f16x2_block6 else tier
+        layers = [(b, conv, bn) for b, blk in enumerate(getattr(self, f"conv_block{b + 1}") for b in range(6))
+                  for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2))]
         tensors = [self.bn0.weight, self.bn0.bias, self.bn0.running_mean, self.bn0.running_var]
-        for b in range(6):
-            blk = getattr(self, f"conv_block{b + 1}")
-            for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
-                tensors += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        for _, conv, bn in layers:
+            tensors += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
         # Keyed on the tensors themselves (address, torch version counter, and the per-tensor counter HIP optimisers
         # bump), NOT on the global parameter generation: an optimiser step on the GRU / decoder must not repack the
         # frozen Cnn14 - captured training graphs hold the addresses of this pack (and a repack costs ~0.3 s).
-        mixed = algo == "f16x2" and self.f16x2_block6 == "bf16x3"
-        key = tuple((t.data_ptr(), t._version, K._lib.tensor_generation(t)) for t in tensors) + (algo, mixed)
-        if not isinstance(self._packed, dict):
-            self._packed = {}
+        key = tuple((t.data_ptr(), t._version, K._lib.tensor_generation(t)) for t in tensors) + (algo, tier6 is not tier)
         hit = self._packed.get(algo)
         if hit is not None and hit[0] == key:
             return hit[1]
+
+        def fold(bn):
+            return K.fold_bn(bn.weight.float(), bn.bias.float(), bn.running_mean.float(), bn.running_var.float(), bn.eps)
+
         with torch.no_grad():
-            pk = {"bn0": K.fold_bn(self.bn0.weight.float(), self.bn0.bias.float(), self.bn0.running_mean.float(),
-                                   self.bn0.running_var.float(), self.bn0.eps), "convs": []}
-            for b in range(6):
-                blk = getattr(self, f"conv_block{b + 1}")
-                for j, (conv, bn) in enumerate(((blk.conv1, blk.bn1), (blk.conv2, blk.bn2))):
-                    w = conv.weight.detach().float()
-                    if b == 0 and j == 0:
-                        wp = w.reshape(64, 9).contiguous()
-                    elif algo == "winograd":
-                        wp = K.pack_conv_weight_winograd(w)
-                    elif algo == "direct":
-                        wp = K.pack_conv_weight(w)
-                    elif algo == "bf16x3" or (algo in WINO and not wino1d_covers(w.shape[0])):
-                        wp = K.pack_conv_weight_bf16x3_frag(w)
-                    elif algo == "wino1d":
-                        wp = K.pack_conv_weight_wino1d_frag(w)
-                    elif algo == "wino43":   # both packs: small launches (single clips) take the K-sliced F(2,3) form
-                        wp = (K.pack_conv_weight_wino1d_frag(w),
-                              K.pack_conv_weight_wino43_frag(w) if wino43_covers(64 >> b, w.shape[0]) else None,
-                              _LazyPack(conv.weight) if b >= 4 else None)   # blocks 5-6 (W = 4, 2): the skinny form
-                    elif algo == "bf16x3_lds":
-                        wp = K.pack_conv_weight_bf16x3(w)
-                    elif algo == "f16x2" and mixed and b == 5:
-                        wp, inv = K.pack_conv_weight_bf16x3_frag(w), None
-                    elif algo == "f16x2":
-                        wp, inv = K.pack_conv_weight_f16x2_frag(w)
-                    else:
-                        raise ValueError(f"unknown conv_algo {algo!r}")
-                    sc, sh = K.fold_bn(bn.weight.float(), bn.bias.float(), bn.running_mean.float(),
-                                       bn.running_var.float(), bn.eps)
-                    if algo == "f16x2" and not (b == 0 and j == 0) and inv is not None:
-                        sc = (sc * inv).contiguous()
-                    pk["convs"].append((wp, sc, sh))
-            pk["mixed"] = mixed
-            if algo == "wino43":
-                pk["b1c2_f43"] = K.pack_conv_weight_wino43_frag(self.conv_block1.conv2.weight.detach().float())
+            # "convs": (pack, BN scale, BN shift) of the 12 layers; "block6": the tier that packed, and launches, conv block 6;
+            # "block1": what the tier's one-kernel block 1 reads beside them
+            pk = {"bn0": fold(self.bn0), "convs": [], "block6": tier6, "block1": None}
+            for i, (b, conv, bn) in enumerate(layers):
+                w = conv.weight.detach().float()
+                if i == 0:   # conv1 of block 1 (one input channel): the same 64 x 9 array on every tier
+                    wp, inv = w.reshape(64, 9).contiguous(), None
+                else:
+                    wp, inv = (tier6 if b == 5 else tier).pack(w, b, conv.weight)
+                sc, sh = fold(bn)
+                if inv is not None:
+                    sc = (sc * inv).contiguous()
+                pk["convs"].append((wp, sc, sh))
+            if tier.pack_block1 is not None:
+                pk["block1"] = tier.pack_block1(self.conv_block1.conv2.weight.detach().float())
         self._packed[algo] = (key, pk)
         return pk
 
@@ -360,8 +429,8 @@ class Cnn14Encoder(nn.Module):
         fewer than ``f16x2_min_frames`` (10, = 3.2 s) frames runs on the split-bf16 tier (3e-5 at any length).
         ``algo``: conv tier of this call (default ``self.conv_algo``).  ``overflow``: int32 device word the fp16 tier ORs
         with 1 when an activation left the fp16 range (``forward`` returns it as ``f16_overflow``).
-        ``clip_frames``: int32 device tensor (B,) of every clip's own ``attn_emb_len`` - ragged batches: the "wino1d" tier
-        skips the conv rows that lie beyond what a clip's own length can bring to one of its output frames (the reference
+        ``clip_frames``: int32 device tensor (B,) of every clip's own ``attn_emb_len`` - ragged batches: the Winograd tiers
+        skip the conv rows that lie beyond what a clip's own length can bring to one of its output frames (the reference
         convolves the zero padding, collate_func.py:29-32); frames below ``attn_emb_len`` are bit-identical, frames at or
         beyond it - which no temporal encoder reads (model_util.py:10-27) - are then NOT the reference's values."""
         if wav.dim() != 2:
@@ -378,17 +447,16 @@ class Cnn14Encoder(nn.Module):
             x0 = K.logmel(wav, self._tables, pk["bn0"][0], pk["bn0"][1], rows_per_clip=Hp[0], channels_last=True)
         if specaug is not None:
             K.specaug_(x0, specaug, pk["bn0"][1], B, Hp[0], T)
-        return self.conv_stack(x0, B, H, Hp, pk, algo, dropout, overflow=overflow,
-                               clip_frames=clip_frames if algo in WINO else None, block6_f23=block6_f23)
+        return self.conv_stack(x0, B, H, Hp, pk, algo, dropout, overflow=overflow, clip_frames=clip_frames,
+                               block6_f23=block6_f23)
 
     def effective_algo(self, algo=None, train=False, min_frames=None):
         """The conv tier a call runs on: the fp16-activation tier is left for the train-mode forward and for batches
         that contain a very short clip (see ``encode``)."""
         algo = algo or self.conv_algo
-        if algo == "f16x2" and train:
-            return "bf16x3"
-        if algo == "f16x2" and min_frames is not None and min_frames < self.f16x2_min_frames:
-            return "bf16x3"
+        fallback = conv_tier(algo).fallback
+        if fallback is not None and (train or (min_frames is not None and min_frames < self.f16x2_min_frames)):
+            return fallback
         return algo
 
     def conv_stack(self, x0, B, H, Hp, pk, algo, dropout=None, blocks=None, overflow=None, clip_frames=None,
@@ -396,78 +464,63 @@ class Cnn14Encoder(nn.Module):
         """The six conv blocks on a bn0-normalised log-mel x0 [B*Hp[0]][64] -> attn_emb (B, H[5], 2048).
         ``blocks``: a list that receives a float32 (B, C, H, W) copy of every pooled block output (tests)."""
         dev = x0.device
-        act = torch.float16 if algo == "f16x2" else torch.float32
-        full = self._buf("full", B * Hp[0] * 64 * 64, dev, act)      # conv1 outputs (largest: level 1)
-        pooled = self._buf("pooled", B * Hp[1] * 32 * 64, dev, act)  # block outputs (largest: block 1)
+        tiers = [conv_tier(algo)] * 5 + [pk["block6"]]   # per conv block: the mixed "f16x2" stack hands block 6 to another tier
+        full = self._buf("full", B * Hp[0] * 64 * 64, dev, tiers[0].act)      # conv1 outputs (largest: level 1)
+        pooled = self._buf("pooled", B * Hp[1] * 32 * 64, dev, tiers[0].act)  # block outputs (largest: block 1)
         W = 64
-        conv = conv_kernel(algo)
-        if algo == "f16x2":
-            import functools
-            conv = functools.partial(conv, overflow=overflow)
-        fuse1 = algo == "f16x2" and os.environ.get("AUDIOCAPTION_FUSE_BLOCK1", "1") != "0"
-        # "wino43": conv block 1 in one kernel (conv1 computed into the F(4,3) staging of conv2) when the launch gives every
-        # CU a persistent workgroup; single clips keep conv_first + the K-sliced F(2,3) form
-        fuse1_w4 = algo == "wino43" and os.environ.get("AUDIOCAPTION_FUSE_BLOCK1", "1") != "0" and Hp[0] % 8 == 0 \
-            and B * Hp[0] // 8 >= W43_MIN_WORKGROUPS and pk.get("b1c2_f43") is not None
-        if algo in WINO and os.environ.get("AUDIOCAPTION_W1_SPLITK", "1") != "0":
-            import functools   # single clips: layers of a few workgroups run K-sliced over a shared workspace
-            conv = functools.partial(conv, splitk_buf=lambda n: self._buf("w1_splitk", n, dev))
-            if algo == "wino43" and dropout is not None:
-                conv = functools.partial(conv, cold=True)   # the training step: weights come from HBM every iteration
-
-        def need(block, j):   # ragged batches: the rows of this layer a clip's own length can bring to an output frame
-            return {"need": (clip_frames,) + rows_needed(block, j, quads=algo == "wino43" and ragged_exact())} \
-                if clip_frames is not None and algo in WINO else {}
-
-        mixed = algo == "f16x2" and pk.get("mixed", False)
+        # what every launch is offered beside its layer.  "workspace": single clips - layers of a few workgroups run K-sliced
+        # over a shared workspace; "cold": the training step - weights come from HBM every iteration
+        offer = {"workspace": None, "overflow": overflow, "cold": dropout is not None}
+        if os.environ.get("AUDIOCAPTION_W1_SPLITK", "1") != "0":
+            offer["workspace"] = lambda n: self._buf("w1_splitk", n, dev)
+        fuse1 = os.environ.get("AUDIOCAPTION_FUSE_BLOCK1", "1") != "0"
         for b in range(6):
+            tier = tiers[b]
             cin, cout = CHANNELS[b], CHANNELS[b + 1]
             w1, s1, t1 = pk["convs"][2 * b]
             w2, s2, t2 = pk["convs"][2 * b + 1]
-            if b == 5 and block6_f23 and isinstance(w1, tuple):
-                w1, w2 = (w1[0], None), (w2[0], None)
+            if b == 5 and block6_f23 and tier.f43:
+                w1, w2 = Wino43Pack(w1.f23), Wino43Pack(w2.f23)
+
+            def need(j):   # ragged batches: the rows of conv j of this block a clip's own length can bring to an output frame
+                if clip_frames is None or not tier.skips_dead_rows:
+                    return None
+                return (clip_frames,) + rows_needed(b + 1, j, quads=tier.f43 and ragged_exact())
+
+            # the block's F.dropout: in the conv kernel's epilogue where the tier has one, else a separate pass
+            drop = (dropout[0], dropout[1] + b, dropout[2]) if dropout is not None else None
+            epilogue = drop if tier.dropout_epilogue else None
             pool_out = pooled
-            if mixed and b == 4:     # block 5 hands block 6 (split-bf16, f32 activations) an f32 pooled output
-                pool_out = self._buf("pooled32", B * Hp[5] * 2 * CHANNELS[5], dev, torch.float32)
-            if mixed and b == 5:
-                conv = K.conv3x3_bn_relu_bf16x3_gw
-                full = self._buf("full32", B * Hp[5] * 2 * CHANNELS[6], dev, torch.float32)
-            if b == 0 and fuse1_w4:
-                K.conv3x3_block1_wino43(x0, w1, s1, t1, pk["b1c2_f43"], s2, t2, pooled, B, Hp[0], H[0],
-                                        dropout=(dropout[0], dropout[1], dropout[2]) if dropout is not None else None,
-                                        conv1=BLOCK1_CONV1, **need(1, 2))
-            elif b == 0 and fuse1:   # conv1 is computed inside conv2's kernel: its 64-channel output never reaches HBM
-                K.conv3x3_block1_f16x2(x0, w1, s1, t1, w2, s2, t2, pooled, B, Hp[0], H[0], W, overflow=overflow)
-            elif b == 0:
+            if b < 5 and tiers[b + 1].act != tier.act:   # block 5 hands a block 6 of f32 activations an f32 pooled output
+                pool_out = self._buf("pooled32", B * Hp[b + 1] * (W // 2) * cout, dev, tiers[b + 1].act)
+            if tier.act != tiers[0].act:
+                full = self._buf("full32", B * Hp[b] * W * cout, dev, tier.act)
+            one_kernel = b == 0 and fuse1 and tier.block1 is not None \
+                and tier.block1(x0, (w1, s1, t1), (w2, s2, t2), pk["block1"], pooled, B, Hp[0], H[0], need(2), epilogue, overflow)
+            if b == 0 and not one_kernel:
                 K.conv3x3_first(x0, w1, s1, t1, full, B, Hp[0], H[0], W, overflow=overflow)
-            else:
-                conv(pooled, w1, s1, t1, full, B, Hp[b], H[b], W, cin, cout, 0, **need(b + 1, 1))
+            elif b > 0:
+                tier.launch(pooled, w1, s1, t1, full, B, Hp[b], H[b], W, cin, cout, 0, need=need(1), **offer)
             if b < 5:
-                fused_drop = dropout is not None and algo in WINO and not (b == 0 and fuse1)
-                if not (b == 0 and (fuse1 or fuse1_w4)):
-                    kw = need(b + 1, 2) if algo not in WINO or wino1d_covers(cout) else {}
-                    if fused_drop:   # the block's F.dropout in the conv kernel's epilogue
-                        kw = {"dropout": (dropout[0], dropout[1] + b, dropout[2])}
-                    conv(full, w2, s2, t2, pool_out, B, Hp[b], H[b], W, cout, cout, 1, **kw)
+                if not one_kernel:
+                    tier.launch(full, w2, s2, t2, pool_out, B, Hp[b], H[b], W, cout, cout, 1,
+                                need=need(2) if epilogue is None else None, dropout=epilogue, **offer)
                 pooled = pool_out
                 W //= 2
-                if dropout is not None and not fused_drop:
-                    K.dropout_(pooled, B * Hp[b + 1] * W * cout, dropout[0], dropout[1] + b, dropout[2])
+                if drop is not None and epilogue is None:
+                    K.dropout_(pooled, B * Hp[b + 1] * W * cout, *drop)
                 if blocks is not None:
                     blk = pooled[:B * Hp[b + 1] * W * cout].reshape(B, Hp[b + 1], W, cout)[:, :H[b + 1]]
                     blocks.append(blk.permute(0, 3, 1, 2).float().clone())
             else:
                 attn = torch.empty(B, H[5], cout, device=dev, dtype=torch.float32)
-                if dropout is None:
-                    conv(full, w2, s2, t2, attn, B, Hp[b], H[b], W, cout, cout, 2, **need(6, 2))
+                if drop is None:
+                    tier.launch(full, w2, s2, t2, attn, B, Hp[b], H[b], W, cout, cout, 2, need=need(2), **offer)
                 else:  # dropout sits between the last block and the mean over mel bins
                     last = self._buf("last", B * Hp[5] * W * cout, dev)
-                    if algo in WINO:
-                        conv(full, w2, s2, t2, last, B, Hp[b], H[b], W, cout, cout, 0,
-                             dropout=(dropout[0], dropout[1] + b, dropout[2]))
-                    else:
-                        conv(full, w2, s2, t2, last, B, Hp[b], H[b], W, cout, cout, 0)
-                        K.dropout_(last, B * Hp[5] * W * cout, dropout[0], dropout[1] + b, dropout[2])
+                    tier.launch(full, w2, s2, t2, last, B, Hp[b], H[b], W, cout, cout, 0, dropout=epilogue, **offer)
+                    if epilogue is None:
+                        K.dropout_(last, B * Hp[5] * W * cout, *drop)
                     K.rows_mean_w(last, attn, B, Hp[5], H[5], W, cout)
         return attn
 
@@ -483,10 +536,11 @@ class Cnn14Encoder(nn.Module):
         # ``conv_algo`` in the input dict overrides the tier for this call (the model re-runs a batch whose fp16
         # activations overflowed on the f32-activation tier)
         algo = self.effective_algo(input_dict.get("conv_algo"), False, min_frames)
-        flag = torch.zeros(1, device=wav.device, dtype=torch.int32) if algo == "f16x2" else None
+        tier = conv_tier(algo)
+        flag = torch.zeros(1, device=wav.device, dtype=torch.int32) if tier.overflow_word else None
         # inside a composite encoder (skip_fc: CrnnEncoder / Cnn14TransformerEncoder mask by length) the rows a clip's own
         # length cannot bring to an output frame are not convolved; stand-alone, attn_emb is the reference's everywhere
-        ragged = skip_fc and algo in WINO and os.environ.get("AUDIOCAPTION_SKIP_DEAD_ROWS", "1") != "0" \
+        ragged = skip_fc and tier.skips_dead_rows and os.environ.get("AUDIOCAPTION_SKIP_DEAD_ROWS", "1") != "0" \
             and int(feat_length.min()) < int(feat_length.max())
         frames = K.upload(feat_length, wav.device, torch.int32) if ragged else None
         # AUDIOCAPTION_RAGGED_EXACT=1: a batch of uneven lengths keeps block 6 on the F(2,3) kernel whether or not rows are

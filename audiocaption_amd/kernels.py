@@ -4,6 +4,7 @@ Each function takes/returns torch tensors that live on the ROCm device, passes r
 current stream to libaudiocaption_hip.so and raises on any failure.  No function here computes
 anything on the host and none has a fallback.
 """
+import contextlib
 import os
 
 import torch
@@ -83,42 +84,51 @@ def conv3x3_block1_f16x2(x0, w1, scale1, shift1, wfrag2, scale2, shift2, out, B,
 CONV_LAUNCH_HOOK = None
 
 
+class _Observed:
+    """``with _observed(...):`` around a launch: "pre" before it and "post" after it - also when the library rejects the
+    launch: the observer's "pre" event must not stay unpaired (bench.py's hook completes the event "pre" opened)."""
+
+    def __init__(self, hook, info):
+        self.hook, self.info = hook, info
+
+    def __enter__(self):
+        self.hook("pre", self.info)
+
+    def __exit__(self, *exc):
+        self.hook("post", self.info)
+
+
+_UNOBSERVED = contextlib.nullcontext()
+
+
+def _observed(algo, B, Hp, H, W, Cin, Cout, mode, **more):
+    hook = CONV_LAUNCH_HOOK
+    if hook is None:
+        return _UNOBSERVED
+    return _Observed(hook, dict(B=B, H=H, Hp=Hp, W=W, Cin=Cin, Cout=Cout, mode=mode, algo=algo, **more))
+
+
 def conv3x3_bn_relu(x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "direct"}
-        hook("pre", info)
-    check(lib.ac_conv3x3_bn_relu(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                 mode, map_mode, stream()), "ac_conv3x3_bn_relu")
-    if hook is not None:
-        hook("post", info)
+    with _observed("direct", B, Hp, H, W, Cin, Cout, mode):
+        check(lib.ac_conv3x3_bn_relu(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                     mode, map_mode, stream()), "ac_conv3x3_bn_relu")
     return out
 
 
 def conv3x3_bn_relu_winograd(x, upk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "winograd"}
-        hook("pre", info)
-    check(lib.ac_conv3x3_bn_relu_winograd(ptr(x), ptr(upk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                          Cout, mode, map_mode, stream()), "ac_conv3x3_bn_relu_winograd")
-    if hook is not None:
-        hook("post", info)
+    with _observed("winograd", B, Hp, H, W, Cin, Cout, mode):
+        check(lib.ac_conv3x3_bn_relu_winograd(ptr(x), ptr(upk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                              mode, map_mode, stream()), "ac_conv3x3_bn_relu_winograd")
     return out
 
 
 def conv3x3_bn_relu_bf16x3(x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "bf16x3"}
-        hook("pre", info)
-    check(lib.ac_conv3x3_bn_relu_bf16x3(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                        mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3")
-    if hook is not None:
-        hook("post", info)
+    with _observed("bf16x3", B, Hp, H, W, Cin, Cout, mode):
+        check(lib.ac_conv3x3_bn_relu_bf16x3(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                            mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3")
     return out
 
 
@@ -137,14 +147,9 @@ def pack_conv_weight_bf16x3(w):
 
 def conv3x3_bn_relu_bf16x3_gw(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "bf16x3"}
-        hook("pre", info)
-    check(lib.ac_conv3x3_bn_relu_bf16x3_gw(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                           Cout, mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3_gw")
-    if hook is not None:
-        hook("post", info)
+    with _observed("bf16x3", B, Hp, H, W, Cin, Cout, mode):
+        check(lib.ac_conv3x3_bn_relu_bf16x3_gw(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                               mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3_gw")
     return out
 
 
@@ -164,28 +169,22 @@ def conv3x3_bn_relu_wino1d(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, 
     ``dropout = (p, seed, seed_dev)``: F.dropout on the layer's output inside the epilogue - the mask ``dropout_`` over
     ``out`` with the same seed would apply (train-mode forward of the frozen network; modes 0 and 1, uniform batches)."""
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "wino1d"}
-        hook("pre", info)
     cf, mul, add = need if need is not None else (None, 0, 0)
-    if dropout is not None:
-        if cf is not None:
-            raise ValueError("conv3x3_bn_relu_wino1d: dropout and dead-row skipping are not combined")
-        check(lib.ac_conv3x3_bn_relu_wino1d_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                                 mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2], stream()),
-              "ac_conv3x3_bn_relu_wino1d_drop")
-    elif workspace is not None:
-        check(lib.ac_conv3x3_bn_relu_wino1d_splitk(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                                   Cout, mode, map_mode, ptr(cf), int(mul), int(add), ptr(workspace),
-                                                   workspace.numel(), stream()),
-              "ac_conv3x3_bn_relu_wino1d_splitk")
-    else:
-        check(lib.ac_conv3x3_bn_relu_wino1d(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                            Cout, mode, map_mode, ptr(cf), int(mul), int(add), stream()),
-              "ac_conv3x3_bn_relu_wino1d")
-    if hook is not None:
-        hook("post", info)
+    if dropout is not None and cf is not None:
+        raise ValueError("conv3x3_bn_relu_wino1d: dropout and dead-row skipping are not combined")
+    with _observed("wino1d", B, Hp, H, W, Cin, Cout, mode):
+        if dropout is not None:
+            check(lib.ac_conv3x3_bn_relu_wino1d_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                     Cout, mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2],
+                                                     stream()), "ac_conv3x3_bn_relu_wino1d_drop")
+        elif workspace is not None:
+            check(lib.ac_conv3x3_bn_relu_wino1d_splitk(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                       Cout, mode, map_mode, ptr(cf), int(mul), int(add), ptr(workspace),
+                                                       workspace.numel(), stream()), "ac_conv3x3_bn_relu_wino1d_splitk")
+        else:
+            check(lib.ac_conv3x3_bn_relu_wino1d(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                Cout, mode, map_mode, ptr(cf), int(mul), int(add), stream()),
+                  "ac_conv3x3_bn_relu_wino1d")
     return out
 
 
@@ -199,23 +198,11 @@ def conv3x3_block1_wino43(x0, w1, scale1, shift1, wfrag2, scale2, shift2, out, B
         raise ValueError(f"conv1 = {conv1!r}")
     cf, mul, add = need if need is not None else (None, 0, 0)
     dp, dseed, ddev = dropout if dropout is not None else (0.0, 0, None)
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": 64, "Cin": 1, "Cout": 64, "mode": 1, "algo": "block1_w4", "conv1": conv1}
-        hook("pre", info)
-        try:
-            return _block1_wino43(x0, w1, scale1, shift1, wfrag2, scale2, shift2, out, B, Hp, H, cf, mul, add, dp, dseed, ddev,
-                                  conv1)
-        finally:
-            hook("post", info)
-    return _block1_wino43(x0, w1, scale1, shift1, wfrag2, scale2, shift2, out, B, Hp, H, cf, mul, add, dp, dseed, ddev, conv1)
-
-
-def _block1_wino43(x0, w1, scale1, shift1, wfrag2, scale2, shift2, out, B, Hp, H, cf, mul, add, dp, dseed, ddev, conv1):
     name = "ac_conv3x3_block1_wino43_mfma" if conv1 == "mfma" else "ac_conv3x3_block1_wino43"
-    check(getattr(_lib.load(), name)(ptr(x0), ptr(w1), ptr(scale1), ptr(shift1), ptr(wfrag2), ptr(scale2), ptr(shift2),
-                                     ptr(out), B, Hp, H, ptr(cf), int(mul), int(add), float(dp), int(dseed), ddev,
-                                     stream()), name)
+    with _observed("block1_w4", B, Hp, H, 64, 1, 64, 1, conv1=conv1):
+        check(getattr(_lib.load(), name)(ptr(x0), ptr(w1), ptr(scale1), ptr(shift1), ptr(wfrag2), ptr(scale2), ptr(shift2),
+                                         ptr(out), B, Hp, H, ptr(cf), int(mul), int(add), float(dp), int(dseed), ddev,
+                                         stream()), name)
     return out
 
 
@@ -237,23 +224,18 @@ def conv3x3_bn_relu_wino43(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, 
     ``pack_conv_weight_wino43_frag``.  Covers W in (32, 16, 8, 4) with modes 0 / 1 and W = 2 with modes 0 / 2 (mean over
     mel), Cout % 128 == 0, Hp % 4 == 0; ``need`` and ``dropout`` as for ``conv3x3_bn_relu_wino1d``."""
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "wino43"}
-        hook("pre", info)
     cf, mul, add = need if need is not None else (None, 0, 0)
-    if dropout is not None:
-        if cf is not None:
-            raise ValueError("conv3x3_bn_relu_wino43: dropout and dead-row skipping are not combined")
-        check(lib.ac_conv3x3_bn_relu_wino43_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                                 mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2], stream()),
-              "ac_conv3x3_bn_relu_wino43_drop")
-    else:
-        check(lib.ac_conv3x3_bn_relu_wino43(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                            mode, map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()),
-              "ac_conv3x3_bn_relu_wino43")
-    if hook is not None:
-        hook("post", info)
+    if dropout is not None and cf is not None:
+        raise ValueError("conv3x3_bn_relu_wino43: dropout and dead-row skipping are not combined")
+    with _observed("wino43", B, Hp, H, W, Cin, Cout, mode):
+        if dropout is not None:
+            check(lib.ac_conv3x3_bn_relu_wino43_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                     Cout, mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2],
+                                                     stream()), "ac_conv3x3_bn_relu_wino43_drop")
+        else:
+            check(lib.ac_conv3x3_bn_relu_wino43(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                                mode, map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()),
+                  "ac_conv3x3_bn_relu_wino43")
     return out
 
 
@@ -268,18 +250,11 @@ def conv3x3_bn_relu_skinny(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, 
     on split-bf16 operands that streams its weights once (csrc/conv3x3_skinny.hip); ``wfrag`` from
     ``pack_conv_weight_bf16x3_frag``; ``workspace``: f32 tensor of at least ``skinny_workspace_floats`` elements;
     ``dropout = (p, seed, seed_dev)`` as for ``conv3x3_bn_relu_wino1d`` (modes 0 and 1)."""
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "skinny"}
-        hook("pre", info)
     dp, dseed, ddev = dropout if dropout is not None else (0.0, 0, None)
-    try:
+    with _observed("skinny", B, Hp, H, W, Cin, Cout, mode):
         check(_lib.load().ac_conv3x3_bn_relu_skinny(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
                                                    mode, ptr(workspace), workspace.numel(), float(dp), int(dseed), ddev, stream()),
               "ac_conv3x3_bn_relu_skinny")
-    finally:   # a rejected launch must not leave the observer's "pre" event unpaired
-        if hook is not None:
-            hook("post", info)
     return out
 
 
@@ -288,18 +263,13 @@ def conv3x3_bn_relu_f16x2_gw(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout
     block), f32 for mode 2.  ``overflow``: a uint32 / int32 device word OR-ed with 1 when a value stored as fp16
     exceeded the fp16 range."""
     lib = _lib.load()
-    hook = CONV_LAUNCH_HOOK
-    if hook is not None:
-        info = {"B": B, "H": H, "Hp": Hp, "W": W, "Cin": Cin, "Cout": Cout, "mode": mode, "algo": "f16x2"}
-        hook("pre", info)
     out_f32 = 1 if (mode == 1 and out.dtype == torch.float32) else 0
     if x.dtype != torch.float16 or out.dtype != (torch.float32 if (mode == 2 or out_f32) else torch.float16):
         raise ValueError("f16x2 conv: fp16 activations in, fp16 out (f32 for mode 2)")
-    check(lib.ac_conv3x3_bn_relu_f16x2_gw(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W,
-                                          Cin, Cout, mode, map_mode, out_f32, ptr(overflow), stream()),
-          "ac_conv3x3_bn_relu_f16x2_gw")
-    if hook is not None:
-        hook("post", info)
+    with _observed("f16x2", B, Hp, H, W, Cin, Cout, mode):
+        check(lib.ac_conv3x3_bn_relu_f16x2_gw(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W,
+                                              Cin, Cout, mode, map_mode, out_f32, ptr(overflow), stream()),
+              "ac_conv3x3_bn_relu_f16x2_gw")
     return out
 
 

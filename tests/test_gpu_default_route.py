@@ -137,6 +137,28 @@ def test_bench_batch_launches_the_f43_family_on_every_layer(hip_model):
     assert seen == want, seen
 
 
+def test_launch_hook_is_paired_when_the_library_refuses_the_launch():
+    """A call the library's argument check refuses (csrc/conv3x3_wino1d.hip takes Cout % 128 == 0 or Cout == 64: 96 is
+    AC_ERR_ARG on the host, before anything is launched) still delivers "post" to the launch observer - bench.py's hook
+    completes the event its "pre" opened - and raises."""
+    from audiocaption_amd import kernels as K
+    from audiocaption_amd._lib import HipLibraryError
+    B, Hp, H, W, Cin, Cout = 1, 8, 6, 16, 32, 96
+    x = torch.zeros(B * Hp * W, Cin, device="cuda")
+    w = torch.zeros(Cin // 32, 12, 2, Cout // 32, 2, 64, 8, device="cuda", dtype=torch.bfloat16)
+    scale, shift = torch.ones(Cout, device="cuda"), torch.zeros(Cout, device="cuda")
+    out = torch.zeros(B * Hp * W, Cout, device="cuda")
+    phases = []
+    saved = K.CONV_LAUNCH_HOOK
+    K.CONV_LAUNCH_HOOK = lambda phase, info: phases.append((phase, info["algo"], info["Cout"]))
+    try:
+        with pytest.raises(HipLibraryError):
+            K.conv3x3_bn_relu_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, 0)
+    finally:
+        K.CONV_LAUNCH_HOOK = saved
+    assert phases == [("pre", "wino1d", 96), ("post", "wino1d", 96)]
+
+
 @pytest.fixture(scope="module")
 def clotho_models():
     """Product models at the Clotho vocabulary (4368, BASELINE configs[0] / configs[1]): the plain draw and the two

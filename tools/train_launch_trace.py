@@ -7,7 +7,6 @@ Pointer arguments (device addresses, the stream handle) are written as the ordin
 trace, NULL as None; integers and floats are written exactly.  The frozen Cnn14 is launched through
 audiocaption_amd.kernels, not through the engine's library handle, and is not part of the trace."""
 import argparse
-import ctypes
 import hashlib
 import os
 import random
@@ -18,9 +17,10 @@ import numpy as np
 import torch
 
 import audiocaption_amd as A
-from audiocaption_amd import _lib, procedural as Pr, train
+from audiocaption_amd import procedural as Pr, train
 from audiocaption_amd.optim import FusedAdam
 from audiocaption_amd.train import TrainEngine
+from launch_trace import TracingLib, ordinals, pointer, trace
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--encoder", choices=("rnn", "trm"), default="rnn")
@@ -46,36 +46,6 @@ cap = torch.randint(4, args.vocab, (B, args.cap_len), generator=torch.Generator(
 cap[:, 0], cap[:, -1] = 1, 2
 batch = {"mode": "train", "wav": wav, "wav_len": [L] * B, "specaug": False, "cap": cap.cuda(),
          "cap_len": np.array([args.cap_len] * B)}
-
-trace, ordinals = [], {}
-
-
-def pointer(v):
-    v = v.value if isinstance(v, ctypes.c_void_p) else v
-    if not v:
-        return "None"
-    return f"p{ordinals.setdefault(int(v), len(ordinals))}"
-
-
-class TracingLib:
-    """Forwards every call to the real library and records (symbol, normalised arguments)."""
-
-    def __init__(self, lib):
-        self._lib = lib
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        kinds = _lib.SIGNATURES[name][1]
-
-        def call(*a):
-            assert len(a) == len(kinds), name
-            trace.append(name + "(" + ", ".join(pointer(v) if k is ctypes.c_void_p else repr(v)
-                                                for v, k in zip(a, kinds)) + ")")
-            return fn(*a)
-
-        setattr(self, name, call)
-        return call
-
 
 _fork, _join = train._SideStream.fork, train._SideStream.join
 
