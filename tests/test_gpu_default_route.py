@@ -119,6 +119,70 @@ def test_default_route_vs_oracle(hip_model, state4981, B, seconds, all_f43):
     assert _check_against_chunks(out, ref, wav_len) < 1e-4
 
 
+def _flip_every_fifth_bn_channel(state):
+    """The sign of BatchNorm gamma AND beta flipped on every fifth channel of each Cnn14 BatchNorm (bn0 and the twelve of the
+    conv blocks): negative folded scales in every layer.  This changes the network function; the oracle runs the same state."""
+    st = {k: v.clone() for k, v in state.items()}
+    flipped = 0
+    for k in st:
+        if k.startswith("encoder.cnn.") and k.endswith(".running_var"):
+            for name in (k[:-len("running_var")] + "weight", k[:-len("running_var")] + "bias"):
+                st[name][::5] = -st[name][::5]
+            flipped += 1
+    assert flipped == 13, flipped
+    return st
+
+
+@pytest.mark.parametrize("seed,gains,flip,batches", [
+    (1, None, False, ((16, 4.0),)),
+    (2, {1: 256.0, 4: 64.0, 8: 128.0}, False, ((16, 4.0), (48, 10.0))),
+    (3, {0: 1 / 64.0, 5: 1 / 16.0, 9: 1 / 64.0}, False, ((16, 4.0),)),
+    (1, None, True, ((16, 4.0), (48, 10.0)))], ids=["seed1", "seed2-gains-up", "seed3-gains-down", "seed1-flipped"])
+def test_default_tier_with_panns_like_statistics(state4981, seed, gains, flip, batches):
+    """The DEFAULT tier (conv_algo "wino43", nothing overridden) on weights with the statistics of a trained checkpoint - the
+    draws of test_gpu_model.py::test_fp16_tier_with_panns_like_statistics (running variance over four decades, activations
+    256 x larger or 64 x smaller) and one more whose BatchNorms have NEGATIVE gamma on every fifth channel: fold_bn, the
+    weight packs and the epilogues of the assembled path under negative scales.  16 x 4 s is the mixed F(4,3) / F(2,3) route,
+    48 x 10 s the all-F(4,3) one (asserted from the launch hook).  Gates of test_default_route_vs_oracle, unchanged: ids
+    identical off near-ties, logits within 1e-4, attn_emb within 5e-4 of the oracle on the same state.  The tier's arithmetic
+    alone stays inside them: its CPU emulation (tests/wino_split_emulation.py conv_stack with F(4,3)) is within 3.5e-5 in
+    the logits and 1e-5 in attn_emb of the fp32 stack on all four draws."""
+    from audiocaption_amd import cnn_encoder as CE
+    from audiocaption_amd import procedural as P
+    from test_gpu_model import _model_with_state, _panns_like_state
+    st = _panns_like_state(state4981, seed, gains)
+    var = st["encoder.cnn.conv_block3.bn1.running_var"]
+    assert float(var.max() / var.min()) > 1e3
+    if flip:
+        st = _flip_every_fifth_bn_channel(st)
+        assert float(st["encoder.cnn.conv_block4.bn2.weight"].min()) < 0
+    model = _model_with_state(st)
+    assert model.encoder.cnn.conv_algo == "wino43" and CE.W43_MIN_WORKGROUPS == 192, "this test is about the defaults"
+    for B, seconds in batches:
+        L = int(seconds * 32000)
+        wav_len = [L - 3200 * (i % 5) * (1 if i % 3 else 0) for i in range(B)]
+        wav = P.synthetic_wav(B, L, varied=True, seed=20 + seed)
+        for i, n in enumerate(wav_len):
+            wav[i, n:] = 0.0
+        wav = torch.from_numpy(wav)
+        with _record_conv_launches() as seen:
+            out = model({"mode": "inference", "wav": wav.cuda(), "wav_len": wav_len, "specaug": False,
+                         "sample_method": "greedy", "max_length": 20})
+        torch.cuda.synchronize()
+        algos = [a for a, *_ in seen]
+        assert algos[0] == "block1_w4" and len(seen) == 11, seen
+        if B == 48:
+            assert set(algos[1:]) == {"wino43"}, algos
+        else:
+            assert algos[1:5] == ["wino43"] * 4 and set(algos[5:]) == {"wino1d"}, algos
+        ref = _oracle_in_chunks(st, wav, wav_len)
+        assert torch.equal(out["attn_emb_len"], ref["attn_emb_len"])
+        name = f"PANNs-like seed {seed}{' flipped' if flip else ''} {B} x {seconds} s"
+        print(f"[{name}] oracle attn_emb rms {float(ref['attn_emb'].pow(2).mean().sqrt()):.3f}")
+        assert _maxdiff(f"attn_emb, {name}", out["attn_emb"], ref["attn_emb"]) < 5e-4
+        assert _check_against_chunks(out, ref, wav_len) < 1e-4
+
+
 def test_bench_batch_launches_the_f43_family_on_every_layer(hip_model):
     """At the bench's batch (64 x 10 s) the default tier means: block 1 in its fused kernel, conv1 and conv2 of blocks 2-6
     on the F(4,3) kernel with the epilogue each layer needs (conv1: full output; conv2: + 2x2 pool; block 6: + mean over

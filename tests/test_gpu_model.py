@@ -612,8 +612,10 @@ def _model_with_state(state):
 
 @pytest.mark.parametrize("seed,gains", [(1, None), (2, {1: 256.0, 4: 64.0, 8: 128.0}), (3, {0: 1 / 64.0, 5: 1 / 16.0, 9: 1 / 64.0})])
 def test_fp16_tier_with_panns_like_statistics(state4981, seed, gains):
-    """Default tier on re-drawn weights (running_var over 1e-2...1e2, per-channel filter scales x0.1...x10, activations
-    up to ~2e4 or down to ~1e-2 of the procedural ones): logits within BASELINE.json's 1e-3 of the oracle, ids equal."""
+    """The fp16-activation tier (conv_algo forced to "f16x2") on re-drawn weights (running_var over 1e-2...1e2, per-channel
+    filter scales x0.1...x10, activations up to ~2e4 or down to ~1e-2 of the procedural ones): logits within BASELINE.json's
+    1e-3 of the oracle, ids equal.  The default tier's sibling on the same draws:
+    tests/test_gpu_default_route.py::test_default_tier_with_panns_like_statistics."""
     from audiocaption_amd import procedural as P
     from oracle import cpu_path as O
     st = _panns_like_state(state4981, seed, gains)

@@ -23,22 +23,8 @@ import torch.nn.functional as F
 from audiocaption_amd import procedural as P
 from oracle import cpu_path as O
 
-BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float64)
-G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)
-AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64)
-
-
-def split(x, fmt, flush=False):
-    """x (f32 / f64) -> (hi, lo) as f32 tensors holding values representable in fmt."""
-    x = x.float()
-    dt = {"bf16": torch.bfloat16, "f16": torch.float16}[fmt]
-    hi = x.to(dt).float()
-    lo = (x - hi).to(dt).float()
-    if flush and fmt == "f16":
-        tiny = 2.0 ** -14
-        hi = torch.where(hi.abs() < tiny, torch.zeros_like(hi), hi)
-        lo = torch.where(lo.abs() < tiny, torch.zeros_like(lo), lo)
-    return hi, lo
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _split_ref import AT, BT, G, XF, split   # noqa: E402  the transform matrices and the operand split, shared with the tests
 
 
 def mm3(a, b, fmt, flush):
@@ -91,17 +77,6 @@ def conv_wino1d(x, w, fmt, flush):
     Y = torch.einsum("ai,bion->boan", at, M)             # (B, O, 2, nt*W)
     Y = Y.reshape(B, -1, 2, nt, W).permute(0, 1, 3, 2, 4).reshape(B, -1, He, W)
     return Y[:, :, :H]
-
-
-# F(4,3), points 0, +-1, +-2, inf (Lavin & Gray) - the matrices csrc/ac_wino43.h spells out row by row
-BT4 = torch.tensor([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
-                    [0, 4, 0, -5, 0, 1]], dtype=torch.float64)
-G4 = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
-                   [0, 0, 1]], dtype=torch.float64)
-AT4 = torch.tensor([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], dtype=torch.float64)
-# "F(1,3)": the direct form as a degenerate transform (three positions = the three taps)
-BT1, G1, AT1 = torch.eye(3, dtype=torch.float64), torch.eye(3, dtype=torch.float64), torch.ones(1, 3, dtype=torch.float64)
-XF = {1: (BT1, G1, AT1), 2: (BT, G, AT), 4: (BT4, G4, AT4)}
 
 
 def conv_wino_nest(x, w, fmt, flush, mh, mw):
