@@ -7,6 +7,7 @@ from .crnn_trm_encoder import Cnn14RnnEncoder, CrnnEncoder
 from .rnn_encoder import RnnEncoder
 from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionModel, TransformerModel
+from .ensemble import EnsembleModel
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
-           "CaptionModel", "TransformerModel", "init_model_from_config", "cnn14rnn_trm_config"]
+           "CaptionModel", "TransformerModel", "EnsembleModel", "init_model_from_config", "cnn14rnn_trm_config"]

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AUDIOCAPTION_HIP_LIB") or os.path.join(_HERE, "libaudiocaption_hip.so")  # env: development builds
 
 AC_MAX_LAYERS = 8
+AC_ENS_MAX = 8     # include/audiocaption_hip.h: members of an ensemble pick
 ABI_VERSION = 2   # include/audiocaption_hip.h AC_ABI_VERSION
 
 c_float_p = ctypes.c_void_p
@@ -85,6 +86,12 @@ SIGNATURES = {
     "ac_trm_beam_step": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
     "ac_trm_beam_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ac_trm_beam_reorder": (_I, [_WP, _I, _I, _I, _P, _P, _P]),
+    "ac_trm_beam_update_all": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # ensemble decoding (csrc/ensemble.hip)
+    "ac_trm_step_logits": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P, _L, _P, _P]),
+    "ac_ens_greedy_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_ens_sample_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_ens_beam_step_select": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     # training step (csrc/train.hip)
     "ac_gemm": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),
     "ac_gemm_bf16x3": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),

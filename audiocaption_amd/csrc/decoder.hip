@@ -17,6 +17,7 @@
 // 64-lane wavefront shuffles.
 #include "ac_common.h"
 #include "ac_sample.h"
+#include "ac_beam.h"
 #include "../../include/audiocaption_hip.h"
 #include <stdlib.h>
 #include <string.h>
@@ -1051,11 +1052,13 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_val, c
 // re-gather the token rows by the chosen previous beams, append the new words, record the beams that END this step
 // (in beam order, score = logprob / (t + 1)), apply the -1000 trick to their cumulative scores and retire the clip
 // when its number of finished beams EQUALS the beam size (the reference's '==').  A retired clip keeps its rows.
+// retire == 0 (ac_trm_beam_update_all): the ensemble search of ensemble.py:195-261 has no such break - every clip searches to
+// max_len and collects every finished beam (at most beam * max_len of them).
 __global__ __launch_bounds__(64) void beam_update_kernel(const float* top_val, const int* top_idx, const int* tok_in,
                                                         int* tok_out, unsigned char* mask_out, float* cum, int* active,
                                                         int* done_cnt, int* done_seq, float* done_score, int* src_row,
                                                         int* n_active, int beam, int V, int max_len, int t, int end_idx,
-                                                        int pad_idx, int cap) {
+                                                        int pad_idx, int cap, int retire) {
   __shared__ int s_src[64];
   __shared__ int s_word[64];
   const int clip = blockIdx.x, tid = threadIdx.x;
@@ -1094,7 +1097,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const float* top_val, c
       cum[clip * beam + k] = v - (is_end ? 1000.0f : 0.0f);
     }
     done_cnt[clip] = cnt;
-    if (cnt == beam) {
+    if (retire && cnt == beam) {
       active[clip] = 0;
       atomicSub(n_active, 1);
     }
@@ -1624,6 +1627,23 @@ extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv
   return AC_OK;
 }
 
+extern "C" int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div,
+                                  int Tm, int max_len, int t, const int* tokens, const unsigned char* key_mask,
+                                  int cache_set, float* logit, long ldl, float* embed, long ld_embed, float* ws_base,
+                                  void* stream) {
+  AC_TRY(check_weights(w));
+  if (!memkv || !mem_len || !tokens || !key_mask || !logit || !ws_base) return AC_ERR_ARG;
+  if (R <= 0 || row_div <= 0 || R % row_div || Tm <= 0 || Tm > MAX_KEYS || t < 0 || t >= max_len) return AC_ERR_ARG;
+  if (max_len > w->max_pos || ldl < w->vocab || (cache_set != 0 && cache_set != 1)) return AC_ERR_ARG;
+  if (embed && ld_embed < w->d_model) return AC_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const Ws ws = carve(w, R, max_len, ws_base);
+  StepOut fin;
+  AC_TRY(decoder_step(w, memkv, mem_len, R, row_div, Tm, max_len, t, tokens, key_mask, max_len + 1,
+                      ws.cache[cache_set], ws, &fin, s));
+  return classifier_step(w, fin, R, embed, ld_embed, logit, ldl, s, ws.att);   // ws.att: dead once the last layer has consumed it
+}
+
 extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam,
                                 int Tm, int max_len, int t, float temp, const int* tokens,
                                 const unsigned char* key_mask, const float* cum_logprob, float* top_val,
@@ -1660,17 +1680,41 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
   return ac_check_launch();
 }
 
-extern "C" int ac_trm_beam_update(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,
-                                  unsigned char* key_mask_out, float* cum_logprob, int* active, int* done_count,
-                                  int* done_seq, float* done_score, int* src_row, int* n_active, int B, int beam, int V,
-                                  int max_len, int t, int end_idx, int pad_idx, int done_capacity, void* stream) {
+static int beam_update(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,
+                       unsigned char* key_mask_out, float* cum_logprob, int* active, int* done_count, int* done_seq,
+                       float* done_score, int* src_row, int* n_active, int B, int beam, int V, int max_len, int t,
+                       int end_idx, int pad_idx, int done_capacity, int retire, void* stream) {
   if (!top_val || !top_idx || !tokens_in || !tokens_out || !key_mask_out || !cum_logprob || !active || !done_count ||
       !done_seq || !done_score || !src_row || !n_active || B <= 0 || beam <= 0 || beam > 64 || V <= 0 || max_len <= 0 ||
       t < 0 || t >= max_len || done_capacity <= 0)
     return AC_ERR_ARG;
   hipLaunchKernelGGL(beam_update_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, top_val, top_idx, tokens_in, tokens_out,
                      key_mask_out, cum_logprob, active, done_count, done_seq, done_score, src_row, n_active, beam, V,
-                     max_len, t, end_idx, pad_idx, done_capacity);
+                     max_len, t, end_idx, pad_idx, done_capacity, retire);
+  return ac_check_launch();
+}
+
+extern "C" int ac_trm_beam_update(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,
+                                  unsigned char* key_mask_out, float* cum_logprob, int* active, int* done_count,
+                                  int* done_seq, float* done_score, int* src_row, int* n_active, int B, int beam, int V,
+                                  int max_len, int t, int end_idx, int pad_idx, int done_capacity, void* stream) {
+  return beam_update(top_val, top_idx, tokens_in, tokens_out, key_mask_out, cum_logprob, active, done_count, done_seq,
+                     done_score, src_row, n_active, B, beam, V, max_len, t, end_idx, pad_idx, done_capacity, 1, stream);
+}
+
+extern "C" int ac_trm_beam_update_all(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,
+                                      unsigned char* key_mask_out, float* cum_logprob, int* active, int* done_count,
+                                      int* done_seq, float* done_score, int* src_row, int* n_active, int B, int beam,
+                                      int V, int max_len, int t, int end_idx, int pad_idx, int done_capacity,
+                                      void* stream) {
+  return beam_update(top_val, top_idx, tokens_in, tokens_out, key_mask_out, cum_logprob, active, done_count, done_seq,
+                     done_score, src_row, n_active, B, beam, V, max_len, t, end_idx, pad_idx, done_capacity, 0, stream);
+}
+
+// csrc/ensemble.hip merges its per-row candidates with the single-model search's kernel (ac_beam.h)
+int ac_beam_merge_launch(const float* cand_val, const int* cand_idx, int B, int beam, int nrows, float* top_val,
+                         int* top_idx, hipStream_t s) {
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(64), 0, s, cand_val, cand_idx, beam, nrows, top_val, top_idx);
   return ac_check_launch();
 }
 

@@ -86,7 +86,7 @@ __device__ __forceinline__ void block_min_max(int& a, int& b, int* sh) {
 
 constexpr float SAMPLE_FIX = 1099511627776.0f;   // 2^40: fixed-point scale of the top-p masses (exp(x - m) <= 1)
 
-template <int NPT>
+template <int NPT, bool ENS>
 __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __shared__ unsigned long long hmass[256];
   __shared__ unsigned int hcnt[256];
@@ -97,10 +97,14 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __shared__ unsigned int sel_bin, sel_cnt;
   const int r = blockIdx.x, tid = threadIdx.x, c0 = tid * NPT;
   if (p.seq && p.t > 0 && p.cnt[p.t - 1] == 0) return;   // the reference loop has already stopped (base.py:167)
-  const float* row = p.logit + (size_t)r * p.ldl;
   float x[NPT];
+  if (ENS) {
+    ens_mean<NPT, false>(p.ens, r, p.V, x, sh_f);
+  } else {
+    const float* row = p.logit + (size_t)r * p.ldl;
 #pragma unroll
-  for (int i = 0; i < NPT; ++i) x[i] = c0 + i < p.V ? row[c0 + i] : -INFINITY;
+    for (int i = 0; i < NPT; ++i) x[i] = c0 + i < p.V ? row[c0 + i] : -INFINITY;
+  }
   float m = -INFINITY;
 #pragma unroll
   for (int i = 0; i < NPT; ++i) m = fmaxf(m, x[i]);
@@ -108,7 +112,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
 
   const bool topk = p.method == AC_SAMPLE_TOPK, topp = p.method == AC_SAMPLE_TOPP;
   // lp / temp for plain and top-k; top-p draws from softmax(logit) and Gumbel-max from softmax(lp): temp has no effect
-  const float inv_t = (topk || p.method == AC_SAMPLE_PLAIN) ? 1.0f / p.temp : 1.0f;
+  // (ENS: ensemble.py:427 divides by temp before the top-p branch as well)
+  const float inv_t = (topk || p.method == AC_SAMPLE_PLAIN || (ENS && topp)) ? 1.0f / p.temp : 1.0f;
   float lse = 0.f;
   if (!topp) {
     float s = 0.f;
@@ -138,7 +143,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         if (c0 + i < p.V && (shift == 24 || (key >> (shift + 8)) == prefix)) {
           const uint32_t dg = (key >> shift) & 255u;
           atomicAdd(&hcnt[dg], 1u);
-          if (topp) atomicAdd(&hmass[dg], __float2ull_rn(expf(x[i] - m) * SAMPLE_FIX));   // top-k: the count is the measure
+          if (topp) atomicAdd(&hmass[dg], __float2ull_rn(expf((x[i] - m) * inv_t) * SAMPLE_FIX));   // (inv_t = 1 for base.py's top-p) top-k: the count is the measure
         }
       }
       __syncthreads();
@@ -234,16 +239,18 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   for (int i = 0; i < NPT; ++i)
     if (c0 + i == word) xw = x[i];
   float lp;
-  if (topp) lp = (xw - m) - logf(total);                    // log(q_w / sum of the kept q), q = softmax(logit)
+  if (topp) lp = (xw - m) * inv_t - logf(total);            // log(q_w / sum of the kept q), q = softmax(logit) (ENS: of x / temp)
+  else if (ENS) lp = p.method == AC_SAMPLE_GUMBEL ? xw : xw / p.temp;   // ensemble.py:425,:446 gather the mean itself
   else if (p.method == AC_SAMPLE_GUMBEL) lp = (xw - m) - lse;  // lp[w]
   else lp = ((xw - m) - lse) / p.temp;                      // lp[w] / temp (top-k: not renormalised)
-  p.logprob[(size_t)r * p.ld_lp] = lp;
   if (!p.seq) {
+    p.logprob[(size_t)r * p.ld_lp] = lp;
     p.word[r] = word;
     return;
   }
   // greedy_pick_kernel's bookkeeping (base.py:157-168): a finished row emits end_idx, its logprob keeps the drawn word's
   const int prev = p.t == 0 ? 1 : p.unfinished[r];
+  if (!(ENS && !prev)) p.logprob[(size_t)r * p.ld_lp] = lp;
   const int unf = prev && (word != p.end_idx);
   const int w = unf ? word : p.end_idx;
   p.unfinished[r] = unf;
@@ -267,15 +274,23 @@ int ac_sample_check(int V, int method, int k, float top_p, float temp) {
 }
 
 int ac_sample_launch(const SampleParams& p, hipStream_t s) {
-  if (ac_sample_check(p.V, p.method, p.k, p.top_p, p.temp) != AC_OK || p.rows <= 0 || !p.logit || !p.seed || !p.logprob)
+  const bool ens = p.ens.n > 0;
+  if (ac_sample_check(p.V, p.method, p.k, p.top_p, p.temp) != AC_OK || p.rows <= 0 || (!ens && !p.logit) || !p.seed || !p.logprob)
     return AC_ERR_ARG;
+  if (ens && p.method == AC_SAMPLE_TOPP && !(p.temp > 0.f && isfinite(p.temp))) return AC_ERR_ARG;
   if (!p.seq && !p.word) return AC_ERR_ARG;
   if (p.seq && (!p.tok || !p.mask || !p.unfinished || !p.cnt || p.t < 0 || p.t >= p.max_len)) return AC_ERR_ARG;
   const dim3 grid(p.rows), block(256);
-  if (p.V <= 256 * 8) hipLaunchKernelGGL(sample_kernel<8>, grid, block, 0, s, p);
-  else if (p.V <= 256 * 20) hipLaunchKernelGGL(sample_kernel<20>, grid, block, 0, s, p);
-  else if (p.V <= 256 * 32) hipLaunchKernelGGL(sample_kernel<32>, grid, block, 0, s, p);
-  else hipLaunchKernelGGL(sample_kernel<64>, grid, block, 0, s, p);
+  if (ens) {   // the same kernel over the mean of the members' log-softmaxes (ac_ens.h)
+    if (p.V <= 256 * 20) hipLaunchKernelGGL((sample_kernel<20, true>), grid, block, 0, s, p);
+    else if (p.V <= 256 * 32) hipLaunchKernelGGL((sample_kernel<32, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((sample_kernel<64, true>), grid, block, 0, s, p);
+    return ac_check_launch();
+  }
+  if (p.V <= 256 * 8) hipLaunchKernelGGL((sample_kernel<8, false>), grid, block, 0, s, p);
+  else if (p.V <= 256 * 20) hipLaunchKernelGGL((sample_kernel<20, false>), grid, block, 0, s, p);
+  else if (p.V <= 256 * 32) hipLaunchKernelGGL((sample_kernel<32, false>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((sample_kernel<64, false>), grid, block, 0, s, p);
   return ac_check_launch();
 }
 

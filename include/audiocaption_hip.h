@@ -405,6 +405,57 @@ int ac_trm_beam_update(const float* top_val, const int* top_idx, const int* toke
 int ac_trm_beam_reorder(const ac_trm_weights* w, int R, int max_len, int t, const int* src_row, float* ws,
                         void* stream);
 
+/* The same bookkeeping for a search that never retires a clip (ensemble.py:195-261 has no "enough finished beams" break):
+ * every clip stays active to max_len and collects every finished beam - at most beam * max_len, so done_capacity =
+ * beam * max_len holds them all.  Same arguments, same kernel; n_active is left alone. */
+int ac_trm_beam_update_all(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,
+                           unsigned char* key_mask_out, float* cum_logprob, int* active, int* done_count, int* done_seq,
+                           float* done_score, int* src_row, int* n_active, int B, int beam, int V, int max_len, int t,
+                           int end_idx, int pad_idx, int done_capacity, void* stream);
+
+/* ---- ensemble decoding (ensemble.py:94-151 stepwise_forward, :154-276 beam_search) -------------
+ * Several captioners decode one batch together: at every step each member's decoder runs on the shared prefix, the word
+ * is chosen from m = mean_n log_softmax(logit_n) (f32, NOT renormalised) and is appended for all of them.  The members
+ * share tokens / key_mask / unfinished / seq and the vocabulary; each keeps its own weights, audio memory and workspace.
+ *
+ * ac_trm_step_logits: ONE decoder step for position t over R rows of one member - ac_trm_beam_step's arguments up to the
+ * KV-cache set, with row_div in place of beam (row r uses the audio memory of clip r / row_div; R % row_div == 0) and
+ * cache_set (0 / 1) naming the active self-attention cache set of the workspace (a greedy or sampled search stays on 0, a
+ * beam search alternates t & 1 with ac_trm_beam_reorder).  Writes logit row r at logit + r * ldl (ldl >= V) and, when embed
+ * is not NULL, the classifier's input row at embed + r * ld_embed. */
+#define AC_ENS_MAX 8
+int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
+                       int max_len, int t, const int* tokens, const unsigned char* key_mask, int cache_set,
+                       float* logit, long ldl, float* embed, long ld_embed, float* ws, void* stream);
+
+/* The picks.  logits: n_models (1 .. AC_ENS_MAX, AC_ERR_ARG beyond) HOST pointers to the members' planes, row r of every
+ * plane at + r * ld (16-byte aligned planes with ld % 4 == 0 are read with 16-byte loads).  V <= 16384.
+ *
+ * ac_ens_greedy_pick: word = argmax m (lowest index wins ties); logprob[r][t] = m[word] (ensemble.py:415).  Bookkeeping of
+ * ac_trm_greedy on the shared buffers: seq [rows][max_len], tokens / key_mask [rows][max_len + 1] (column t + 1 is
+ * written), unfinished [rows], unfinished_cnt [max_len] (zeroed by the caller; the kernel returns at once when
+ * unfinished_cnt[t - 1] == 0).  A row that finished before step t emits end_idx and stores no value (the caller's 0 stays) -
+ * the reference keeps writing words after <end>; up to and including a row's first <end> the two agree.
+ *
+ * ac_ens_sample_pick: the sampler of ac_sample_rows / ac_trm_sample over m with ensemble.py:412-449's rules where they
+ * depart from base.py: temp divides m before top-p as well; the stored value is m[w] / temp (plain, top-k), the log of the
+ * renormalised kept probability (top-p), m[w] (gumbel).  Same Philox counter (t, row) and inverse CDF in vocabulary order.
+ * seq != NULL: step t of a search with the bookkeeping above (logprob [rows][max_len]); seq == NULL: the pick alone,
+ * word_out[r] and logprob[r].
+ *
+ * ac_ens_beam_step_select: per row log_softmax(m / temp) + cum_logprob[r], per clip the `beam` best over the flattened
+ * (beam * V) scores (only the clip's first row at t == 0): top_val / top_idx [B][beam] as ac_trm_beam_update reads them.
+ * beam <= 8; scratch: 2 * B * beam * beam words. */
+int ac_ens_greedy_pick(const float* const* logits, int n_models, long ld, int rows, int V, int t, int max_len,
+                       int end_idx, int pad_idx, int64_t* seq, float* logprob, int* tokens, unsigned char* key_mask,
+                       int* unfinished, int* unfinished_cnt, void* stream);
+int ac_ens_sample_pick(const float* const* logits, int n_models, long ld, int rows, int V, int method, int k,
+                       float top_p, float temp, const uint64_t* seed_dev, int t, int max_len, int end_idx, int pad_idx,
+                       int64_t* seq, float* logprob, int* tokens, unsigned char* key_mask, int* unfinished,
+                       int* unfinished_cnt, int* word_out, void* stream);
+int ac_ens_beam_step_select(const float* const* logits, int n_models, long ld, int B, int beam, int V, int t, float temp,
+                            const float* cum_logprob, float* top_val, int* top_idx, float* scratch, void* stream);
+
 /* ================================== training step ==================================
  * The reference trains GRU + decoder on the frozen Cnn14 with scheduled sampling: step t runs the decoder on a
  * (N, t+1) prefix and keeps the last position's logit (base.py:131-137,152-199, transformer_model.py:34-57).  The
