@@ -74,6 +74,7 @@ SIGNATURES = {
     "ac_dec_wide_gemm": (_I, [_I, _P, _L, _P, _L, _P, _P, _P, _L, _I, _P, _P, _F, _P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
     "ac_trm_workspace_floats": (_L, [_WP, _I, _I]),
     "ac_trm_greedy": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_trm_greedy_segments": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ac_sample_rows": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P]),
     "ac_trm_sample": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
     "ac_conv3x3_skinny_workspace_floats": (_L, [_I, _I, _I, _I, _I]),

@@ -6,7 +6,8 @@
 // One row of logits -> one sampled word (base.py:214-252 sample_next_word, methods AC_SAMPLE_* of the public header).
 // Without `seq` the word goes to word[r] and its log-probability to logprob[r * ld_lp] (ac_sample_rows).  With `seq` the
 // kernel also does greedy_pick_kernel's bookkeeping for step t of a decode chain (base.py:157-168): unfinished flag, seq,
-// next step's token / mask, unfinished count - and returns at once when no row was left unfinished after step t - 1.
+// next step's token / mask, unfinished count of the row's segment - and returns at once when no row of that segment was
+// left unfinished after step t - 1.
 struct SampleParams {
   const float* logit; long ldl;      // row r at logit + r * ldl
   int rows, V, method, k;
@@ -18,6 +19,8 @@ struct SampleParams {
   // decode-chain bookkeeping (null seq: none)
   int64_t* seq; int max_len, end_idx, pad_idx;
   int* tok; unsigned char* mask; int* unfinished; int* cnt;
+  int seg_rows;                      // rows per segment of the chain, cnt [segments][max_len] (csrc/decoder.hip struct Live);
+                                     // 0: one segment
   // Ensemble decoding (csrc/ensemble.hip): with ens.n > 0 `logit` is not read - the row sampled is the mean of the members'
   // log-softmaxes, formed in registers (ac_ens.h), and the kernel is instantiated with ensemble.py:412-449's rules where
   // they depart from base.py: temp divides the mean before top-p as well; the stored value is x[w] / temp (plain, top-k) or

@@ -12,7 +12,9 @@
 //    cached self-attention K/V (the causal mask makes position t independent of later tokens);
 //  * the greedy loop never returns to the host: argmax, log-prob, <end> bookkeeping and the
 //    "every clip finished" test live in one kernel per step, so a whole decode is a fixed launch
-//    sequence on one stream.
+//    sequence on one stream.  The reference leaves its loop once every clip of the batch has finished;
+//    here the launches of the remaining steps stay in the sequence and their workgroups return at once
+//    (struct Live), per batch when several batches share the chain.
 // Projections run on the f32 matrix cores through ac_linear; softmax / LayerNorm reductions are
 // 64-lane wavefront shuffles.
 #include "ac_common.h"
@@ -47,6 +49,27 @@ extern "C" int ac_dec_wide_gemm(int producer, const float* X, long ldx, const fl
 
 namespace {
 
+// Which rows of a step of the on-device search still run.  The rows of a chain are `segments` of seg_rows rows each (the
+// batches that share it; a lone batch is one segment), and the reference stops a batch's loop once every row of that batch
+// has emitted <end> (base.py:167): row r runs step t iff t == 0 or cnt[r / seg_rows][t - 1] > 0, the number of rows of its
+// segment still unfinished after step t - 1 (written by that step's pick, a kernel earlier on the stream).  Per segment,
+// never per row: a finished row keeps decoding while its batch runs, as in the reference.  cnt null: every row runs (beam
+// search, teacher forcing).
+struct Live {
+  const int* cnt = nullptr;   // [segments][max_len]
+  int seg_rows = 1, max_len = 0, t = 0;
+};
+__device__ __forceinline__ bool row_live(const Live& L, int r) {
+  return !L.cnt || L.t == 0 || L.cnt[(size_t)(r / L.seg_rows) * L.max_len + L.t - 1] > 0;
+}
+// any of the rows r0 .. r1 - 1: the same answer in every thread of a workgroup that asks about the same rows
+__device__ __forceinline__ bool rows_live(const Live& L, int r0, int r1) {
+  if (!L.cnt || L.t == 0) return true;
+  for (int sg = r0 / L.seg_rows; sg <= (r1 - 1) / L.seg_rows; ++sg)
+    if (L.cnt[(size_t)sg * L.max_len + L.t - 1] > 0) return true;
+  return false;
+}
+
 // ---------------------------------------------------------------------------------------------
 // x[r][:] = E[tok[r][t]] * sqrt(d) + pe[t]                     (transformer_decoder.py:89-91)
 // ---------------------------------------------------------------------------------------------
@@ -63,10 +86,10 @@ __global__ void embed_pe_kernel(const int* tok, long tok_stride, int t, const fl
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* x, const float* y, const float* w,
                                                             const float* b, float* out, int rows, int d,
-                                                            long ldx, long ldy, long ldo) {
+                                                            long ldx, long ldy, long ldo, Live live) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
+  if (row >= rows || !row_live(live, row)) return;   // per wave: the kernel has no barrier
   const float* xr = x + (size_t)row * ldx;
   const float* yr = y ? y + (size_t)row * ldy : nullptr;
   float v[16];  // d <= 1024
@@ -110,14 +133,18 @@ struct AttnParams {
   // wide route (csrc/decoder_wide.hip): the context rows leave as three bf16 planes in MFMA fragment order instead, the A
   // operand of the out-projection launch: pack[row / 32][k step of 16][plane][lane = row % 32 + 32 * (k % 16 / 8)][k % 8]
   unsigned char* out_pk = nullptr; int pk_kst = 0;
+  Live live;                              // rows of a finished segment are skipped (dec_row*_kernel take it from here too)
 };
 
 __global__ __launch_bounds__(64) DEC_CAP void attn_step_kernel(AttnParams p) {
   __shared__ float sc[MAX_KEYS];
   const int r = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+  if (!row_live(p.live, r)) return;   // one row per workgroup: uniform, before any load or barrier
   const int kr = r / p.row_div;
   const bool act = lane < p.hd;
   const size_t hoff = (size_t)h * p.hd;
+  // (A skipped step leaves its cache slot unwritten.  No later step reads it: a segment's count stays 0 once it is 0 - no
+  // pick of that segment runs again to raise it - so the rows of a skipped step are skipped at every later step too.)
   if (p.new_k && act) {
     const size_t dst = (size_t)kr * p.row_stride + (size_t)(p.nkeys - 1) * p.key_stride + hoff + lane;
     p.Kw[dst] = p.new_k[(size_t)r * p.ld_new + hoff + lane];
@@ -275,7 +302,10 @@ __device__ __forceinline__ void attn_issue_v(const AttnParams& p, int r, int h, 
   }
 #pragma unroll
   for (int j = 0; j < ATT_VPRE; ++j) vpre[j] = j < p.nkeys ? vpre[j] : 0.f;
-  if (p.new_k) {   // the cache rows of this step, for the steps to come (nobody in this launch reads them back)
+  // the cache rows of this step, for the steps to come (nobody in this launch reads them back).  A step skipped for a
+  // finished segment (Live) writes none - and none is missed: the segment's count stays 0 from then on, so every later
+  // step of these rows is skipped as well and never reads the slots a skipped step left unwritten.
+  if (p.new_k) {
     const size_t dst = (size_t)kr * p.row_stride + (size_t)newest * p.key_stride + hoff + lane;
     p.Kw[dst] = nk[lane];
     p.Vw[dst] = nv[lane];
@@ -444,6 +474,7 @@ __global__ DEC_ROW_BOUNDS void dec_row_kernel(RowParams p) {
   __shared__ __attribute__((aligned(16))) float part[4 * ROW_D];
   __shared__ float red[8];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (!row_live(p.a.live, r)) return;   // one row per workgroup: uniform, before any load or barrier
   const float resv = p.res[(size_t)r * p.ldres + tid];
   sx[tid] = attn_head_row(p.a, r, wave, lane, sc[wave], true);
   __syncthreads();
@@ -480,6 +511,7 @@ __global__ DEC_ROW_BOUNDS void dec_row2_kernel(RowParams p1, RowParams p2) {
   __shared__ float red[8];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float xn;
+  if (!row_live(p1.a.live, r)) return;   // one row per workgroup: uniform, before any load or barrier
   ROW_STAMP(0);
   const float resv = p1.res[(size_t)r * p1.ldres + tid];
   sx[tid] = attn_head_row(p1.a, r, wave, lane, sc[wave], true);
@@ -563,6 +595,8 @@ struct DecGemmParams {
   float* Y; long ldy;
   int M, N, K, relu;
   int ntb;  // consecutive 16-column tiles per block (1 unless K fits one chunk)
+  Live live;  // a block whose 16 rows all belong to finished segments returns at once; a tile across a segment boundary
+              // computes all its rows and stores the live ones
 };
 
 #ifdef AC_DEC_STAMPS  // development probe only (tools/dec_probe.hip): phase timestamps of block (0,0), wave 0
@@ -609,6 +643,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kq = lane >> 4;           // which 4 of the 16 k of a group this lane feeds
   const int m0 = blockIdx.y * DEC_T;
+  if (!rows_live(p.live, m0, m0 + DEC_T < p.M ? m0 + DEC_T : p.M)) return;   // block-uniform, before any load or barrier
   const int nt0 = blockIdx.x * p.ntb;  // first of the ntb consecutive column tiles of this block
   const int KC = p.K < DEC_KC ? p.K : DEC_KC;
   const int ldsx = KC + 4;
@@ -632,6 +667,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
     const int grp = lane >> 4, sub = lane & 15;
     const int row = wave * 4 + grp, r = m0 + row;
     const bool ok = r < p.M;
+    const bool keep = ok && row_live(p.live, r);
     f32x4 v[NF], gw[NF], gb[NF];
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     if (PRO == PRO_EMBED) {
@@ -670,7 +706,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
     for (int i = 0; i < NF; ++i)
       if (i < nf) {
         *(f32x4*)(sX + row * ldsx + (sub + 16 * i) * 4) = ok ? v[i] : zero4;
-        if (blockIdx.x == 0 && p.xout && ok) *(f32x4*)(p.xout + (size_t)r * p.ldxo + (sub + 16 * i) * 4) = v[i];
+        if (blockIdx.x == 0 && p.xout && keep) *(f32x4*)(p.xout + (size_t)r * p.ldxo + (sub + 16 * i) * 4) = v[i];
       }
   }
   DEC_STAMP(2);
@@ -735,7 +771,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
     {
       const int i = tid >> 4, jn = tid & 15;  // 256 threads = the 16 x 16 outputs
       const int gm = m0 + i, gn = n0 + jn;
-      if (gm < p.M && gn < p.N) {
+      if (gm < p.M && gn < p.N && row_live(p.live, gm)) {
         const int o = i * 17 + jn;
         float y = (red[o] + red[DEC_T * 17 + o]) + (red[2 * DEC_T * 17 + o] + red[3 * DEC_T * 17 + o]);
         if (p.bias) y += p.bias[gn];
@@ -771,7 +807,8 @@ struct PickParams {
   int64_t* seq; float* logprob;
   int* tok; unsigned char* mask;  // [B][max_len+1]
   int* unfinished;                // [B]
-  int* cnt;                       // [max_len]
+  int* cnt;                       // [segments][max_len], zeroed by greedy_init_kernel
+  int seg_rows;                   // rows per segment (struct Live)
 };
 
 __device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
@@ -785,7 +822,8 @@ __global__ __launch_bounds__(256) DEC_CAP void greedy_pick_kernel(PickParams p) 
   __shared__ int si[4];
   __shared__ float ssum[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (p.t > 0 && p.cnt[p.t - 1] == 0) return;  // the reference loop has already stopped (base.py:167)
+  int* const cnt = p.cnt + (size_t)(b / p.seg_rows) * p.max_len;   // of this row's segment
+  if (p.t > 0 && cnt[p.t - 1] == 0) return;  // the reference loop of this batch has already stopped (base.py:167)
   const float* row = p.logit + (size_t)b * p.ldl;
   // one pass over memory: all loads in flight at once, max / arg-max / exp-sum from registers
   float x[PICK_MAXV / 256];
@@ -826,12 +864,12 @@ __global__ __launch_bounds__(256) DEC_CAP void greedy_pick_kernel(PickParams p) 
     p.logprob[(size_t)b * p.max_len + p.t] = -logf(tot);
     p.tok[(size_t)b * (p.max_len + 1) + p.t + 1] = w;
     p.mask[(size_t)b * (p.max_len + 1) + p.t + 1] = (w == p.pad_idx) ? 1 : 0;
-    if (unf) atomicAdd(&p.cnt[p.t], 1);
+    if (unf) atomicAdd(&cnt[p.t], 1);
   }
 }
 
 __global__ void greedy_init_kernel(int64_t* seq, float* logprob, int* tok, unsigned char* mask, int* unfinished,
-                                   int* cnt, int B, int max_len, int start_idx, int end_idx, int pad_idx) {
+                                   int* cnt, int n_cnt, int B, int max_len, int start_idx, int end_idx, int pad_idx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * max_len) { seq[i] = end_idx; logprob[i] = 0.f; }
   if (i < B * (max_len + 1)) {
@@ -840,7 +878,31 @@ __global__ void greedy_init_kernel(int64_t* seq, float* logprob, int* tok, unsig
     mask[i] = c == 0 ? (start_idx == pad_idx) : 0;
   }
   if (i < B) unfinished[i] = 1;
-  if (i < max_len) cnt[i] = 0;
+  if (i < n_cnt) cnt[i] = 0;   // n_cnt = segments * max_len <= B * max_len: inside the grid
+}
+
+// The columns of the steps a segment did not run read as the reference leaves them - it never allocates them: logit and
+// embed 0 (seq = <end> and log-probability 0 are what greedy_init_kernel wrote and no pick touched).  The search works in
+// static buffers that still hold an earlier, longer search; one launch at the end of the chain, grid (rows, max_len - 1),
+// clears exactly the columns not run, also for the routes whose kernels do not skip (the generic-GEMM classifier, the wide
+// and hybrid routes).  It writes what the skipped steps would have written, at the memory system's speed, once.
+__global__ __launch_bounds__(256) void search_finalize_kernel(float* logit, float* embed, Live live, int V, int d) {
+  const int r = blockIdx.x;
+  live.t = blockIdx.y + 1;
+  if (row_live(live, r)) return;
+  float* lg = logit + ((size_t)r * live.max_len + live.t) * V;
+  float* em = embed + ((size_t)r * live.max_len + live.t) * d;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  if (V % 4 == 0 && !((uintptr_t)logit & 15)) {
+    for (int c = threadIdx.x; c < V / 4; c += 256) ((f32x4*)lg)[c] = zero4;
+  } else {
+    for (int c = threadIdx.x; c < V; c += 256) lg[c] = 0.f;
+  }
+  if (d % 4 == 0 && !((uintptr_t)embed & 15)) {
+    for (int c = threadIdx.x; c < d / 4; c += 256) ((f32x4*)em)[c] = zero4;
+  } else {
+    for (int c = threadIdx.x; c < d; c += 256) em[c] = 0.f;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1175,9 +1237,9 @@ int check_weights(const ac_trm_weights* w) {
 }
 
 int launch_ln(const float* x, const float* y, const float* w, const float* b, float* out, int rows, int d,
-              long ldx, long ldy, long ldo, hipStream_t s) {
+              long ldx, long ldy, long ldo, hipStream_t s, const Live& live = Live()) {
   hipLaunchKernelGGL(add_layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, y, w, b, out, rows, d, ldx,
-                     ldy, ldo);
+                     ldy, ldo, live);
   return ac_check_launch();
 }
 
@@ -1185,6 +1247,8 @@ int launch_ln(const float* x, const float* y, const float* w, const float* b, fl
 // cache: active KV cache set.  Returns through `fin` the operands of the LAST residual join
 // (embed = LayerNorm(fin.x + fin.y) with the last layer's norm3), which the caller fuses into the
 // classifier projection; 8 launches per layer: the residual joins and the embedding never run alone.
+// `live` (struct Live): the rows of finished segments of an on-device search are skipped by every kernel of the step
+// (Live() = every row runs; the wide route's kernels do not skip - the search clears what they wrote, search_finalize_kernel).
 // Offsets (in floats) of the fragment-packed step weights inside ac_trm_weights::step_pk, fixed order:
 // per layer sa_in, sa_out, ca_q, ca_out, l1, l2; then the classifier.
 struct PackLayout {
@@ -1256,7 +1320,7 @@ inline bool hybrid_route(const ac_trm_weights* w, int R) {
 
 int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
                  int max_len, int t, const int* tok, const unsigned char* mask, long tok_stride, float* cache,
-                 const Ws& ws, StepOut* fin, hipStream_t s) {
+                 const Ws& ws, StepOut* fin, hipStream_t s, const Live& live) {
   const int d = w->d_model, hd = d / w->nhead;
   const float scale = 1.0f / sqrtf((float)hd);
   if (t >= w->max_pos || d > DEC_MAX_D || d % 64 || w->dim_ff % 64 || !w->step_pk) return AC_ERR_ARG;
@@ -1268,6 +1332,7 @@ int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len
   float* xb = ws.x2;
   DecGemmParams g;
   g.tok = tok; g.tok_stride = tok_stride; g.t = t; g.emb = w->emb; g.pe = w->pe; g.emb_scale = sqrtf((float)d);
+  g.live = live;
   // column tiles per block of the single-chunk projections: two from 512 rows on (beam search over grouped batches: 768
   // rows - the A tile is staged once for both, EffB2-Trm 19.15 -> 19.40 k clips/s; at 256 rows and below no difference).  The
   // arithmetic of an output does not depend on it.  AUDIOCAPTION_DEC_NTB overrides (development).
@@ -1355,6 +1420,7 @@ int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len
     a.key_len = nullptr; a.key_mask = mask; a.mask_stride = tok_stride;
     a.new_k = ws.qkv + d; a.new_v = ws.qkv + 2 * d; a.ld_new = 3 * d;
     a.out = ws.att; a.ldo = d; a.hd = hd; a.scale = scale;
+    a.live = live;
     if (fused) {
       // ---- self attention + out-projection + LN1 + cross query projection: one launch, one row per workgroup ----
       RowParams rp;
@@ -1433,7 +1499,7 @@ int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len
 
 // logits[R, V] = LayerNorm(fin.x + fin.y) W_cls^T, the normalised rows also stored to xout (= `embed`)
 int classifier_step(const ac_trm_weights* w, const StepOut& fin, int R, float* xout, long ldxo, float* logit,
-                    long ldl, hipStream_t s, float* scratch = nullptr) {
+                    long ldl, hipStream_t s, const Live& live, float* scratch = nullptr) {
   // From 512 rows on (beam search over grouped batches: 768 rows x 4368 words) the 16 x 16-tile projection re-reads the
   // classifier once per 16 rows: 47 us per step; the residual join as its own launch + the tiled exact-f32 GEMM (ac_gemm)
   // take 4 + 30.  Another summation order than the projection's (last bits of the logits; not a precision change).
@@ -1451,13 +1517,14 @@ int classifier_step(const ac_trm_weights* w, const StepOut& fin, int R, float* x
   if (cls_gemm && R >= 512 && (xout || scratch) && w->cls_w) {
     float* nx = xout ? xout : scratch;
     const long ldn = xout ? ldxo : (long)w->d_model;
-    AC_TRY(launch_ln(fin.x, fin.y, fin.ln_w, fin.ln_b, nx, R, w->d_model, w->d_model, w->d_model, ldn, s));
+    AC_TRY(launch_ln(fin.x, fin.y, fin.ln_w, fin.ln_b, nx, R, w->d_model, w->d_model, w->d_model, ldn, s, live));
     return ac_gemm(nx, ldn, 1, w->cls_w, 1, w->d_model, logit, ldl, R, w->vocab, w->d_model, nullptr, 0, 0.f, 1, 0.f, 0,
                    nullptr, 0, nullptr, 0, (void*)s);
   }
   DecGemmParams g;
   g.tok = nullptr; g.tok_stride = 0; g.t = 0; g.emb = nullptr; g.pe = nullptr; g.emb_scale = 0.f;
   g.M = R; g.N = w->vocab; g.K = w->d_model; g.relu = 0;
+  g.live = live;
   static const int dev_cls_ntb = getenv("AUDIOCAPTION_DEC_CLS_NTB") ? atoi(getenv("AUDIOCAPTION_DEC_CLS_NTB")) : 4;   // development
   g.ntb = dev_cls_ntb;  // 1092 column tiles: four per block keep the grid near one resident wave of blocks
   g.X = fin.x; g.ldx = w->d_model; g.Y2 = fin.y; g.ldy2 = w->d_model; g.ln_w = fin.ln_w; g.ln_b = fin.ln_b;
@@ -1552,12 +1619,17 @@ extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int m
 
 // The on-device search of ac_trm_greedy / ac_trm_sample: `sp` null = the argmax pick, else the sampler with these
 // method parameters (its row / bookkeeping fields are filled per step here).
-static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm, int max_len,
-                      int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob, float* embed,
-                      int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream) {
+// The B rows are `segments` batches of B / segments rows, each searched as the reference searches a batch of its own: its
+// loop ends when every row of THAT batch has emitted <end> (base.py:167, :206-211).  The launch sequence is fixed - it is
+// captured into a graph - so the end is data: from then on every workgroup of every launch that holds only rows of ended
+// segments returns before its first load (struct Live), and a last launch clears the columns of the steps not run.
+static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments, int Tm,
+                      int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                      float* embed, int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !seq || !logit || !logprob || !embed || !unfinished_cnt || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || Tm <= 0 || Tm > MAX_KEYS || max_len <= 0 || max_len > w->max_pos) return AC_ERR_ARG;
+  if (segments <= 0 || B % segments) return AC_ERR_ARG;
   if (w->vocab > PICK_MAXV) return AC_ERR_ARG;
   if (sp && (ac_sample_check(w->vocab, sp->method, sp->k, sp->top_p, sp->temp) != AC_OK || !sp->seed)) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -1565,20 +1637,23 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
   const int d = w->d_model, V = w->vocab;
   const int n_init = B * (max_len + 1);
   hipLaunchKernelGGL(greedy_init_kernel, dim3((n_init + 255) / 256), dim3(256), 0, s, seq, logprob, ws.tok,
-                     ws.mask, ws.unfinished, unfinished_cnt, B, max_len, start_idx, end_idx, pad_idx);
+                     ws.mask, ws.unfinished, unfinished_cnt, segments * max_len, B, max_len, start_idx, end_idx, pad_idx);
   AC_TRY(ac_check_launch());
+  Live live;
+  live.cnt = unfinished_cnt; live.seg_rows = B / segments; live.max_len = max_len;
   for (int t = 0; t < max_len; ++t) {
     StepOut fin;
+    live.t = t;
     AC_TRY(decoder_step(w, memkv, mem_len, B, 1, Tm, max_len, t, ws.tok, ws.mask, max_len + 1, ws.cache[0], ws,
-                        &fin, s));
+                        &fin, s, live));
     AC_TRY(classifier_step(w, fin, B, embed + (size_t)t * d, (long)max_len * d, logit + (size_t)t * V,
-                           (long)max_len * V, s));
+                           (long)max_len * V, s, live));
     if (sp) {
       SampleParams q = *sp;
       q.logit = logit + (size_t)t * V; q.ldl = (long)max_len * V; q.rows = B; q.V = V; q.t = t; q.word = nullptr;
       q.logprob = logprob + t; q.ld_lp = max_len;
       q.seq = seq; q.max_len = max_len; q.end_idx = end_idx; q.pad_idx = pad_idx;
-      q.tok = ws.tok; q.mask = ws.mask; q.unfinished = ws.unfinished; q.cnt = unfinished_cnt;
+      q.tok = ws.tok; q.mask = ws.mask; q.unfinished = ws.unfinished; q.cnt = unfinished_cnt; q.seg_rows = live.seg_rows;
       AC_TRY(ac_sample_launch(q, s));
       continue;
     }
@@ -1586,8 +1661,12 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
     p.logit = logit + (size_t)t * V; p.ldl = (long)max_len * V;
     p.V = V; p.t = t; p.max_len = max_len; p.end_idx = end_idx; p.pad_idx = pad_idx;
     p.seq = seq; p.logprob = logprob; p.tok = ws.tok; p.mask = ws.mask; p.unfinished = ws.unfinished;
-    p.cnt = unfinished_cnt;
+    p.cnt = unfinished_cnt; p.seg_rows = live.seg_rows;
     hipLaunchKernelGGL(greedy_pick_kernel, dim3(B), dim3(256), 0, s, p);
+    AC_TRY(ac_check_launch());
+  }
+  if (max_len > 1) {
+    hipLaunchKernelGGL(search_finalize_kernel, dim3(B, max_len - 1), dim3(256), 0, s, logit, embed, live, V, d);
     AC_TRY(ac_check_launch());
   }
   return AC_OK;
@@ -1596,7 +1675,15 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
 extern "C" int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm,
                              int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
                              float* logprob, float* embed, int* unfinished_cnt, float* ws_base, void* stream) {
-  return trm_search(w, memkv, mem_len, B, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+  return trm_search(w, memkv, mem_len, B, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, nullptr, stream);
+}
+
+extern "C" int ac_trm_greedy_segments(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments,
+                                      int Tm, int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq,
+                                      float* logit, float* logprob, float* embed, int* unfinished_cnt, float* ws_base,
+                                      void* stream) {
+  return trm_search(w, memkv, mem_len, B, segments, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
                     unfinished_cnt, ws_base, nullptr, stream);
 }
 
@@ -1606,7 +1693,7 @@ extern "C" int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const 
                              const uint64_t* seed_dev, void* stream) {
   SampleParams sp = {};
   sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
-  return trm_search(w, memkv, mem_len, B, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+  return trm_search(w, memkv, mem_len, B, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
                     unfinished_cnt, ws_base, &sp, stream);
 }
 
@@ -1621,8 +1708,8 @@ extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv
   const int d = w->d_model, V = w->vocab;
   for (int t = 0; t < T; ++t) {
     StepOut fin;
-    AC_TRY(decoder_step(w, memkv, mem_len, N, 1, Tm, T, t, tokens, key_mask, T, ws.cache[0], ws, &fin, s));
-    AC_TRY(classifier_step(w, fin, N, embed + (size_t)t * d, (long)T * d, logit + (size_t)t * V, (long)T * V, s));
+    AC_TRY(decoder_step(w, memkv, mem_len, N, 1, Tm, T, t, tokens, key_mask, T, ws.cache[0], ws, &fin, s, Live()));
+    AC_TRY(classifier_step(w, fin, N, embed + (size_t)t * d, (long)T * d, logit + (size_t)t * V, (long)T * V, s, Live()));
   }
   return AC_OK;
 }
@@ -1640,8 +1727,8 @@ extern "C" int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, c
   const Ws ws = carve(w, R, max_len, ws_base);
   StepOut fin;
   AC_TRY(decoder_step(w, memkv, mem_len, R, row_div, Tm, max_len, t, tokens, key_mask, max_len + 1,
-                      ws.cache[cache_set], ws, &fin, s));
-  return classifier_step(w, fin, R, embed, ld_embed, logit, ldl, s, ws.att);   // ws.att: dead once the last layer has consumed it
+                      ws.cache[cache_set], ws, &fin, s, Live()));
+  return classifier_step(w, fin, R, embed, ld_embed, logit, ldl, s, Live(), ws.att);   // ws.att: dead once the last layer has consumed it
 }
 
 extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam,
@@ -1657,8 +1744,8 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
   const Ws ws = carve(w, R, max_len, ws_base);
   StepOut fin;
   AC_TRY(decoder_step(w, memkv, mem_len, R, beam, Tm, max_len, t, tokens, key_mask, max_len + 1,
-                      ws.cache[t & 1], ws, &fin, s));
-  AC_TRY(classifier_step(w, fin, R, nullptr, 0, ws.lg, V, s, ws.att));   // ws.att: dead once the last layer has consumed it
+                      ws.cache[t & 1], ws, &fin, s, Live()));
+  AC_TRY(classifier_step(w, fin, R, nullptr, 0, ws.lg, V, s, Live(), ws.att));   // ws.att: dead once the last layer has consumed it
   static const bool two_kernels = getenv("AUDIOCAPTION_BEAM_TOPK") && !strcmp(getenv("AUDIOCAPTION_BEAM_TOPK"), "scan");
   if (beam <= 8 && V <= 8192 && !two_kernels) {
     // scores + per-row candidates in one pass over registers, then a one-wave merge per clip; the candidates (2 x R x

@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __shared__ unsigned long long sel_ahead, sel_mass;
   __shared__ unsigned int sel_bin, sel_cnt;
   const int r = blockIdx.x, tid = threadIdx.x, c0 = tid * NPT;
-  if (p.seq && p.t > 0 && p.cnt[p.t - 1] == 0) return;   // the reference loop has already stopped (base.py:167)
+  int* const cnt = p.seq && p.seg_rows > 0 ? p.cnt + (size_t)(r / p.seg_rows) * p.max_len : p.cnt;   // of this row's segment
+  if (p.seq && p.t > 0 && cnt[p.t - 1] == 0) return;   // the reference loop of this batch has already stopped (base.py:167)
   float x[NPT];
   if (ENS) {
     ens_mean<NPT, false>(p.ens, r, p.V, x, sh_f);
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   p.seq[(size_t)r * p.max_len + p.t] = w;
   p.tok[(size_t)r * (p.max_len + 1) + p.t + 1] = w;
   p.mask[(size_t)r * (p.max_len + 1) + p.t + 1] = (w == p.pad_idx) ? 1 : 0;
-  if (unf) atomicAdd(&p.cnt[p.t], 1);
+  if (unf) atomicAdd(&cnt[p.t], 1);
 }
 
 }  // namespace

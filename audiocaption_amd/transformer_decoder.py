@@ -235,17 +235,18 @@ class TransformerDecoder(BaseDecoder):
                                             ptr(st["sampled_logprob"]), ptr(st["embed"]), ptr(st["unfinished_cnt"]),
                                             ptr(st["cluster_ws"]), int(st["early_stop"]), stream()), "ac_trm_greedy_cluster")
             return
-        check(lib.ac_trm_greedy(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx,
-                                pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
-                                ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()),
-              "ac_trm_greedy")
+        check(lib.ac_trm_greedy_segments(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm, max_length, start_idx,
+                                         end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
+                                         ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()),
+              "ac_trm_greedy_segments")
 
-    def _search_buffers(self, key, dev, B, Tm, A, max_length):
-        """Static buffers of an on-device search (greedy or sampled) over B rows: inputs, workspace, outputs."""
+    def _search_buffers(self, key, dev, B, Tm, A, max_length, segments=1):
+        """Static buffers of an on-device search (greedy or sampled) over B rows: inputs, workspace, outputs.  ``segments``
+        batches share the chain: one row of unfinished counts each (one segment: the plain ``(max_length,)`` vector)."""
         f32 = dict(device=dev, dtype=torch.float32)
         ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), B, max_length)
         return {
-            "key": key, "graph": None, "uses": 0,
+            "key": key, "graph": None, "uses": 0, "segments": segments,
             "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
             "memkv": torch.empty(self.nlayers, B * Tm, 2 * self.d_model, **f32),
             "tmp": torch.empty(B * Tm, self.d_model, **f32), "ws": torch.empty(ws_n, **f32),
@@ -253,12 +254,20 @@ class TransformerDecoder(BaseDecoder):
             "logit": torch.empty(B, max_length, self.vocab_size, **f32),
             "sampled_logprob": torch.empty(B, max_length, **f32),
             "embed": torch.empty(B, max_length, self.d_model, **f32),
-            "unfinished_cnt": torch.empty(max_length, device=dev, dtype=torch.int32),
+            "unfinished_cnt": torch.empty((segments, max_length) if segments > 1 else (max_length,), device=dev,
+                                          dtype=torch.int32),
         }
 
     def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None):
         """On-device greedy search.  Returns device tensors seq (int64), logit, logprob, embed, cnt.  ``attn_emb`` /
-        ``attn_emb_len``: one batch, or lists of batches of the same (frames, width) decoded as one chain.
+        ``attn_emb_len``: one batch, or lists of batches of the same (frames, width) decoded as one chain.  Batches of one
+        row count are the chain's segments: each stops when ITS rows have all emitted <end>, as the reference's loop over
+        that batch does (from then on the chain's launches skip its rows), and ``unfinished_cnt`` comes back per batch,
+        ``(batches, max_length)``.  Batches of different row counts are searched as one segment.  The logit / embed columns
+        of the steps a segment did not run are 0.  A batch decoded inside a shared chain gives the bits it gives alone as
+        long as the memory projection (``ac_linear`` over rows x frames) takes the same kernel on both sides: its skinny
+        kernel up to 128 rows, the tiled one beyond, which sum in different orders (~3e-6 on the logits) - e.g. 3 rows x 31
+        frames alone (93) against 6 rows grouped (186) do not; from 5 rows x 31 frames per batch on both sides are tiled.
 
         Two forms of the same search.  "chain": ten launches per step (csrc/decoder.hip) - ~90 us per step whatever the row
         count, the form that shares the GPU with the next batch's encoder (``forward_async``).  "cluster": ONE persistent
@@ -275,6 +284,7 @@ class TransformerDecoder(BaseDecoder):
         parts = list(attn_emb) if isinstance(attn_emb, (list, tuple)) else [attn_emb]   # several batches, one chain: each is
         dev = parts[0].device                                                           # copied into its rows of the static buffer
         B, (Tm, A) = sum(p_.shape[0] for p_ in parts), parts[0].shape[1:]
+        segments = len(parts) if len({p_.shape[0] for p_ in parts}) == 1 else 1
         use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
         mode = mode or os.environ.get("AUDIOCAPTION_GREEDY", "auto")
         if mode not in ("auto", "chain", "cluster"):
@@ -284,16 +294,18 @@ class TransformerDecoder(BaseDecoder):
         if mode == "cluster" and not covered:
             raise _lib.HipLibraryError("the one-launch greedy search does not cover this decoder shape / row count")
         cluster = wanted and covered
+        if cluster:
+            segments = 1   # the one-launch form stops on the whole row set
         # AUDIOCAPTION_CLUSTER_EARLY_STOP=0: the one-launch form runs all max_length steps like the launch chain (benchmarks that
         # compare the two at equal work; the outputs are the same either way)
         early = os.environ.get("AUDIOCAPTION_CLUSTER_EARLY_STOP", "1") != "0"
-        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, cluster, early, self._weights_key())
+        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, cluster, early, self._weights_key(), segments)
         if self._greedy_state is None:
             self._greedy_state = {}
         states = self._greedy_state
         st = states.pop(key, None)
         if st is None:
-            st = self._search_buffers(key, dev, B, Tm, A, max_length)
+            st = self._search_buffers(key, dev, B, Tm, A, max_length, segments)
             if cluster:
                 nb = _lib.load().ac_trm_cluster_workspace_bytes(B)
                 st["cluster_ws"] = torch.zeros((nb + 7) // 8, device=dev, dtype=torch.int64)   # (the error word is reset by every call)

@@ -226,8 +226,9 @@ class PendingCaption:
         out["seq"] = self._seq.clone()
         out["sampled_logprob"] = self._lp.clone()
         if getattr(self, "_cnt", None) is not None:
-            # A chain shared with other batches runs until ALL of them have finished; the reference stops a batch when its own
-            # rows have (base.py:167) and leaves the later columns at their initial 0: step t ran iff rows were unfinished after t - 1
+            # A chain shared with batches of ANOTHER row count runs until all of them have finished (equal row counts: the
+            # chain stops each batch on its own and this is a no-op); the reference stops a batch when its own rows have
+            # (base.py:167) and leaves the later columns at their initial 0: step t ran iff rows were unfinished after t - 1
             ran = torch.ones(self._cnt.shape[0], dtype=torch.bool)
             ran[1:] = self._cnt[:-1] > 0
             out["sampled_logprob"][:, ~ran] = 0
@@ -493,9 +494,7 @@ class TransformerModel(CaptionModel):
             else:   # the decoder copies every batch into its rows of the chain's static buffer: no concatenation launch
                 attn, lens = [it[1]["attn_emb"] for it in items], [it[1]["attn_emb_len"] for it in items]
             res = self.decoder.greedy(attn, lens, max_length, self.start_idx, self.end_idx, self.pad_idx)
-            same_b = len({it[1]["attn_emb"].shape[0] for it in items}) == 1
-            if len(items) > 1 and same_b:   # rows still unfinished after step t, per batch: one reduction for the whole chain
-                cnts = (res["seq"].view(len(items), -1, max_length) != self.end_idx).sum(1).to(torch.int32)
+            per_batch = res["unfinished_cnt"].dim() == 2   # batches of one row count: the chain counted (and stopped) each on its own
             r0 = 0
             staged = []
             for pending, enc, _, _ in items:
@@ -518,8 +517,8 @@ class TransformerModel(CaptionModel):
                     host_flag.zero_()
                 if len(items) == 1:
                     cnt = res["unfinished_cnt"]
-                elif same_b:
-                    cnt = cnts[len(staged)]
+                elif per_batch:
+                    cnt = res["unfinished_cnt"][len(staged)]
                 else:   # rows still unfinished after step t: finished rows hold end_idx (csrc/decoder.hip greedy_pick)
                     cnt = (res["seq"][rows] != self.end_idx).sum(0).to(torch.int32)
                 if len(items) > 1:

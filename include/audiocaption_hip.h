@@ -317,10 +317,21 @@ long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int max_len);
  *   seq [B][max_len] int64, logit [B][max_len][V], logprob [B][max_len], embed [B][max_len][d];
  *   unfinished_cnt [max_len] int32: rows still unfinished after step t (step t+1.. are the steps the
  *   reference would not have executed once this reaches 0; their seq/logprob columns keep the
- *   reference's initial values end_idx / 0).  ws: ac_trm_workspace_floats(w, B, max_len) floats. */
+ *   reference's initial values end_idx / 0, their logit/embed columns read 0).  ws: ac_trm_workspace_floats(w, B, max_len) floats. */
 int ac_trm_greedy(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int Tm, int max_len,
                   int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
                   float* embed, int* unfinished_cnt, float* ws, void* stream);
+
+/* ac_trm_greedy over `segments` batches of B / segments rows each in one launch chain (B % segments == 0; rows
+ * [i * B / segments, (i + 1) * B / segments) are batch i).  Every batch is searched as if alone: its loop ends when all
+ * of ITS rows have emitted <end>, whatever the other batches do.  unfinished_cnt [segments][max_len] int32, row i as
+ * ac_trm_greedy's for batch i.  The launch sequence does not depend on the data; once a batch has ended, the workgroups
+ * that hold only its rows return at once in every launch of the remaining steps, and the logit / embed columns of the
+ * steps a batch did not run read 0 (seq end_idx, logprob 0) - also in ac_trm_greedy and ac_trm_sample, which are this
+ * search over one segment. */
+int ac_trm_greedy_segments(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments, int Tm,
+                           int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
+                           float* logprob, float* embed, int* unfinished_cnt, float* ws, void* stream);
 
 /* The same greedy search (same arguments, same outputs; base.py:152-218, transformer_decoder.py:80-103) as ONE persistent
  * launch for the case that nothing else runs on the GPU (the blocking model() call, single clips): a row is decoded by a
