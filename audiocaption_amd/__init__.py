@@ -8,6 +8,7 @@ from .rnn_encoder import RnnEncoder
 from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionModel, TransformerModel
 from .ensemble import EnsembleModel
+from .rl_model import ScstWrapper
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
-           "CaptionModel", "TransformerModel", "EnsembleModel", "init_model_from_config", "cnn14rnn_trm_config"]
+           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "init_model_from_config", "cnn14rnn_trm_config"]

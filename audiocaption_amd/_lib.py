@@ -118,6 +118,9 @@ SIGNATURES = {
     "ac_colsum": (_I, [_P, _L, _P, _L, _I, _P]),
     "ac_argmax_rows": (_I, [_P, _L, _I, _I, _P, _L, _P]),
     "ac_label_smoothing_loss": (_I, [_P, _P, _L, _P, _I, _I, _I, _F, _F, _P, _P, _P, _F, _P, _P]),
+    # self-critical sequence training (csrc/scst.hip)
+    "ac_scst_pick": (_I, [_P, _L, _I, _I, _F, _P, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P]),
+    "ac_scst_loss": (_I, [_P, _P, _L, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "ac_gru_layer_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_gru_layer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_swa_update": (_I, [_P, _P, _L, _I, _P]),

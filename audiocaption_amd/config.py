@@ -21,6 +21,7 @@ ALIASES = {
     "captioning.models.cnn_encoder.EfficientNetB2": "audiocaption_amd.effnet_encoder.EfficientNetB2",
     "captioning.models.transformer_encoder.TransformerEncoder": "audiocaption_amd.transformer_encoder.TransformerEncoder",
     "captioning.models.crnn_trm_encoder.Cnn14TransformerEncoder": "audiocaption_amd.crnn_trm_encoder.Cnn14TransformerEncoder",
+    "captioning.models.rl_model.ScstWrapper": "audiocaption_amd.rl_model.ScstWrapper",
     "captioning.losses.loss.LabelSmoothingLoss": "audiocaption_amd.loss.LabelSmoothingLoss",
     "captioning.utils.lr_scheduler.ExponentialDecayScheduler": "audiocaption_amd.lr_scheduler.ExponentialDecayScheduler",
 }

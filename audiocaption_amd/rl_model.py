@@ -1,0 +1,166 @@
+"""Self-critical sequence training (SCST) on the MI355X path.  Plugin-compatible with the reference class
+``captioning.models.rl_model.ScstWrapper`` (rl_model.py:11-85) as its runner drives it (run.py:35-41,67-72,118-119: the
+wrapper gets ``keys``, ``key2refs``, ``vocabulary`` and ``scorer`` and returns the loss itself).
+
+The reference file is stale: it reads ``"seqs"``, ``"sampled_logprobs"`` and ``"raw_feats"``, which its ``CaptionModel`` no
+longer produces (base.py:122-128 has ``"seq"`` and ``"sampled_logprob"``).  What it computes is restated here with the
+current keys.  For ``mode == "train"``:
+
+1. baseline: ``model.eval()``, no gradients, ``sample_method="greedy"`` - the inference path as it is - -> ``greedy_seqs``;
+2. rollout: ``model.train()``, ``sample_method="sample"``: the train-mode encoder and ``max_length`` decoder passes on the
+   words drawn so far (``TrainEngine.rollout``); a clip that has drawn ``<end>`` keeps emitting ``<end>``;
+   ``sampled_logprob[n, t] = log_softmax(logit[n, t])[w] / temp``;
+3. reward: ``score(sampled) - score(greedy)`` per clip through ``compute_batch_score`` and the CALLER's scorer
+   (``scorer.compute_score(references, hypothesis) -> (mean, per-key list)``; no scorer is built in);
+4. ``mask[n, 0] = 1``, ``mask[n, t] = (seq[n, t-1] != end_idx)``; ``loss = mean_n sum_t -(sampled_logprob * reward[n] *
+   mask)`` - one kernel (csrc/scst.hip ac_scst_loss), whose backward hands d(loss)/d(logit) to the training engine's
+   bridge node, so ``loss.backward()`` fills ``.grad`` of every trainable parameter;
+5. output ``{"greedy_seqs", "sampled_seqs", "reward", "score", "loss"}``; the model is left in ``train()`` mode.
+
+Any other mode is forwarded to the wrapped model.  The caller's ``input_dict`` is not modified (the reference overwrites
+its ``mode`` and ``sample_method``).
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import check, ptr, stream
+from .transformer_model import CaptionMetaMixin, TransformerModel
+
+
+def compute_batch_score(decode_res, key2refs, keys, start_idx, end_idx, vocabulary, scorer):
+    """Per-clip scores (N,) of the decoded words ``decode_res`` (N, max_length) - model_util.py:117-164.  A clip's
+    sentence is its words up to the first ``end_idx`` (``start_idx`` skipped) joined through ``vocabulary.idx2word``; clips
+    that share a key are scored once, with the first one's sentence."""
+    if scorer is None:
+        raise ValueError("compute_batch_score: a scorer is required (no CIDEr scorer is built in)")
+    decode_res = np.asarray(decode_res)
+    hypothesis, references = {}, {}
+    for row, key in zip(decode_res, keys):
+        if key in hypothesis:
+            continue
+        words = []
+        for w in row.tolist():
+            if w == end_idx:
+                break
+            if w != start_idx:
+                words.append(vocabulary.idx2word[w])
+        hypothesis[key] = [" ".join(words)]
+        references[key] = key2refs[key]
+    _, per_key = scorer.compute_score(references, hypothesis)
+    by_key = dict(zip(references.keys(), per_key))
+    return np.array([by_key[key] for key in keys[:decode_res.shape[0]]], dtype=np.float64)
+
+
+def _launch(logit, seq, reward, temp, end_idx, dlogit, gscale_dev):
+    N, T, V = logit.shape
+    row_loss = torch.empty(N * T, device=logit.device, dtype=torch.float32)
+    loss = torch.empty(1, device=logit.device, dtype=torch.float32)
+    check(_lib.load().ac_scst_loss(ptr(logit), ptr(seq), seq.stride(0), ptr(reward), float(temp), int(end_idx), N, T, V,
+                                   ptr(row_loss), ptr(loss), ptr(dlogit), ptr(gscale_dev), stream()), "ac_scst_loss")
+    return loss, row_loss
+
+
+class _ScstLossFn(torch.autograd.Function):
+    """loss = mean_n sum_t -(log_softmax(logit)[seq] / temp * reward[n] * mask) and its gradient, both by ac_scst_loss."""
+
+    @staticmethod
+    def forward(ctx, logit, seq, reward, temp, end_idx):
+        loss, _ = _launch(logit, seq, reward, temp, end_idx, None, None)
+        ctx.save_for_backward(logit, seq, reward)
+        ctx.args = (temp, end_idx)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        logit, seq, reward = ctx.saved_tensors
+        dlogit = torch.empty_like(logit)
+        g = grad_out.reshape(1).to(device=logit.device, dtype=torch.float32)
+        _launch(logit, seq, reward, *ctx.args, dlogit, g)
+        return dlogit, None, None, None, None
+
+
+def scst_loss(logit, seq, reward, temp, end_idx):
+    """The SCST loss of sampled words ``seq`` (N, T) int32 under ``logit`` (N, T, V) and per-clip ``reward`` (N,)."""
+    if logit.dim() != 3:
+        raise ValueError("logit must be (batch, length, classes)")
+    if logit.dtype != torch.float32 or not logit.is_contiguous():
+        logit = logit.float().contiguous()
+    seq = seq.to(device=logit.device, dtype=torch.int32)
+    if seq.stride(1) != 1:
+        seq = seq.contiguous()
+    reward = torch.as_tensor(reward).to(device=logit.device, dtype=torch.float32).contiguous()
+    return _ScstLossFn.apply(logit, seq, reward, float(temp), int(end_idx))
+
+
+class ScstWrapper(nn.Module, CaptionMetaMixin):
+
+    def __init__(self, model):
+        super().__init__()
+        if not isinstance(model, TransformerModel):
+            raise NotImplementedError(f"ScstWrapper: the wrapped model must be a TransformerModel (the HIP training "
+                                      f"engine's rollout), got {model.__class__.__name__}")
+        self.model = model
+
+    def forward(self, input_dict):
+        if input_dict["mode"] == "train":
+            return self.scst(input_dict)
+        return self.model(input_dict)
+
+    def _baseline(self, input_dict, max_length):
+        """The greedy baseline: the inference path in eval mode without gradients."""
+        model = self.model
+        d = {k: v for k, v in input_dict.items() if k not in ("seed", "dropout_seed", "_scst_words", "_cnn_attn")}
+        d.update(mode="inference", sample_method="greedy", max_length=max_length)
+        model.eval()
+        with torch.no_grad():
+            hook = input_dict.get("_cnn_attn")
+            if hook is None:
+                return model(d)["seq"]
+            # parity hook (see TrainEngine._prepare): start downstream of the mel front-end and the Cnn14
+            from .cnn_encoder import cnn14_feat_len
+            enc = model.encoder
+            lens = cnn14_feat_len(input_dict["wav_len"], enc.cnn.hop_length, enc.cnn.downsample_ratio)
+            back = enc.rnn if hasattr(enc, "rnn") else enc.trm
+            return model.forward_decoder(d, back({"attn": hook, "attn_len": lens}))["seq"]
+
+    def scst(self, input_dict):
+        from .train import TrainEngine, _TrainBridge
+        model = self.model
+        for k in ("keys", "key2refs", "vocabulary", "scorer"):
+            if input_dict.get(k) is None:
+                raise ValueError(f"ScstWrapper: input_dict[{k!r}] is required for mode 'train' (run.py:35-41)")
+        temp = float(input_dict.get("temp", 1.0))
+        if not (math.isfinite(temp) and temp > 0):
+            raise ValueError(f"ScstWrapper: temp must be finite and > 0, got {temp}")
+        method = input_dict.get("sample_method", "sample")
+        if method != "sample":
+            raise NotImplementedError(f"ScstWrapper: the rollout draws with plain sampling ('sample'), not {method!r}")
+        max_length = int(input_dict.get("max_length", model.max_length))
+        engine = getattr(model, "_train_engine", None)
+        if engine is None:
+            engine = model._train_engine = TrainEngine(model)     # (raises for an encoder the engine is not built for)
+        keys = list(input_dict["keys"])
+
+        greedy = self._baseline(input_dict, max_length)
+        model.train()
+        out = engine.rollout(dict(input_dict, max_length=max_length, temp=temp))
+        sampled = out["seq"].cpu()
+        greedy = torch.as_tensor(greedy).cpu()
+
+        score = {}
+        for name, seqs in (("sampled", sampled), ("greedy", greedy)):
+            score[name] = compute_batch_score(seqs.numpy(), input_dict["key2refs"], keys, model.start_idx, model.end_idx,
+                                              input_dict["vocabulary"], input_dict["scorer"])
+        reward = score["sampled"] - score["greedy"]
+        reward_dev = torch.from_numpy(reward.astype(np.float32)).to(out["logit"].device)     # the one upload
+
+        logit = out["logit"]
+        if torch.is_grad_enabled():
+            logit = _TrainBridge.apply(engine, logit, *engine.flat.params)
+        loss = scst_loss(logit, out["seq_i32"], reward_dev, temp, model.end_idx)
+        return {"greedy_seqs": greedy, "sampled_seqs": sampled, "reward": torch.as_tensor(reward),
+                "score": torch.as_tensor(score["sampled"]), "loss": loss}

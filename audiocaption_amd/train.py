@@ -17,6 +17,9 @@ Here the whole step is HIP kernels driven from this file through the C ABI (csrc
 * dropout masks come from a counter hash, regenerated in the backward (nothing stored) and reproducible by the CPU
   oracle; the per-step seed lives in device memory so that a captured HIP graph draws fresh masks when replayed.
 
+``TrainEngine.rollout`` is the sampled rollout of self-critical sequence training (audiocaption_amd/rl_model.py): the same
+row space with every pass run on the words drawn so far, feeding the same backward.
+
 ``TrainEngine`` is the fast path (``engine.step(batch)``); ``TransformerModel.forward`` with ``mode="train"`` goes
 through the same engine and returns ``logit`` attached to torch.autograd by ONE bridge node, so the reference's
 runner (``loss.backward()``, any torch optimizer) works unchanged.
@@ -545,7 +548,7 @@ class TrainEngine:
         return lay
 
     # ---- host side of one iteration: shapes, static input buffers, scheduled-sampling draws, seed -------------
-    def _prepare(self, input_dict):
+    def _prepare(self, input_dict, rollout=False):
         model = self.model
         enc, dec = model.encoder, model.decoder
         if not model.training:
@@ -582,6 +585,8 @@ class TrainEngine:
         Tm = Tq + 1 if trm else Tq      # decoder memory rows per clip (the Transformer encoder prepends cls_token)
         key = (dev, N, Tc, tuple(wav.shape) if hook is None else ("hook", Tq), teacher_forcing, p_dec, p_rnn, p_cnn,
                model.start_idx, model.pad_idx, specaug and hook is None)
+        if rollout:
+            key += ("rollout",)     # the SCST rollout's states never collide with the cross-entropy step's of the same shape
         st = self._states.get(key)
         if st is None:
             lay = self._layout(N, T, Tm, teacher_forcing, dev)
@@ -729,7 +734,12 @@ class TrainEngine:
         # over 7 392 rows instead of 21 x 26 over 32 ... 704), and only the free-running passes (15 % at ss_ratio 0.85)
         # are then re-run in order on their own predictions, overwriting their rows.  Same results: a pass reads earlier
         # passes only through `seq`, and the dropout masks are a function of (seed, row), not of the launch.
-        if teacher_forcing:
+        if st.get("rollout") is not None:
+            # SCST rollout: every pass runs on the words the passes before it drew (``_decoder_passes`` picks with
+            # ac_scst_pick); all T passes always run, the rows of a finished clip get a zero gradient from the loss
+            for t in range(NP):
+                self._decoder_passes(st, t, t + 1, ucap)
+        elif teacher_forcing:
             self._decoder_passes(st, 0, 1, ucap)
         else:
             self._decoder_passes(st, 0, NP, lay["ones"].data_ptr())
@@ -848,7 +858,7 @@ class TrainEngine:
     def _decoder_passes(self, st, ta, tb, ucap_ptr):
         """Decoder passes [ta, tb) of the row space as one batch: prefixes (teacher tokens where ``ucap_ptr[t]`` is set,
         else the model's own earlier predictions), embedding, the decoder layers, the classifier on the last position of
-        every sequence -> logit[:, t], arg-max -> seq[:, t]."""
+        every sequence -> logit[:, t], arg-max -> seq[:, t] (SCST rollout: the sampled or forced word, ac_scst_pick)."""
         model, lib, fp = self.model, self.lib, self.flat
         dec = model.decoder
         s = _lib.stream()
@@ -892,7 +902,7 @@ class TrainEngine:
         logit, seq, cls = c["logit"], c["seq"], c["cls"]
         if teacher_forcing:
             self._lin(s, x, cls, None, logit, N * T, V, D)
-        elif tb - ta == NP:
+        elif tb - ta == NP and st.get("rollout") is None:
             # every pass at once: the last position of every sequence, gathered in (clip, step) order = logit's layout
             xlast = ws.f("xlast", N * T, D)
             check(lib.ac_gather_rows(x, lay["cls_rows"].data_ptr(), xlast, N * T, D, s), "ac_gather_rows")
@@ -903,7 +913,15 @@ class TrainEngine:
                 L, off_t = passes[t]
                 # classifier on the last position of every sequence of this pass -> logit[:, t]
                 self._lin(s, x + 4 * off_t * D + 4 * t * D, cls, None, logit + 4 * t * V, N, V, D, ldx=L * D, ldy=T * V)
-                check(lib.ac_argmax_rows(logit + 4 * t * V, T * V, N, V, seq + 4 * t, T, s), "ac_argmax_rows")
+                ro = st.get("rollout")
+                if ro is None:
+                    check(lib.ac_argmax_rows(logit + 4 * t * V, T * V, N, V, seq + 4 * t, T, s), "ac_argmax_rows")
+                else:
+                    forced = ro["forced"]
+                    check(lib.ac_scst_pick(logit + 4 * t * V, T * V, N, V, ro["temp"], ro["seed"].data_ptr(), t,
+                                           model.end_idx, None if forced is None else forced.data_ptr(), T,
+                                           ws.i("scst_done", N), ws.i("scst_drawn", N), seq, T, ws.f("scst_logprob", N * T), T,
+                                           s), "ac_scst_pick")
 
     def _outputs(self, st):
         N, T, V = st["N"], st["T"], st["V"]
@@ -922,6 +940,57 @@ class TrainEngine:
         out["logit"] = out["logit"].clone()
         if "seq" in out:
             out["seq"] = out["seq"].to(torch.int64)
+        return out
+
+    # ---- SCST rollout (rl_model.py:35-38: the model in train() mode, sample_method "sample") --------------------------
+    def rollout(self, input_dict):
+        """The sampled rollout of self-critical sequence training: the train-mode encoder, then ``max_length`` decoder passes,
+        pass t on <start> plus the words drawn so far with the train-mode dropout masks of that pass (base.py:152-170); the
+        word of step t is drawn on the device from softmax(log_softmax(logit_t) / temp) and a clip that has drawn <end>
+        keeps emitting <end>.  Needs no ``cap``.  Same row space and dropout-mask indexing as the scheduled-sampling
+        forward with every pass present, so the state it keeps feeds ``backward(dlogit)`` unchanged.  All passes always run
+        (no early exit, no graph capture).
+
+        ``input_dict``: wav / wav_len / specaug as for mode "train"; ``max_length`` (default the model's), ``temp`` (1.0);
+        ``dropout_seed`` as in ``forward``; ``seed``: the sampler's 64-bit seed (default: the dropout seed of this call);
+        ``_scst_words`` (parity hook, int64 N x T): these words instead of the draws, the finished-row rule still applies.
+        Returns ``logit`` (N, T, V), ``seq`` (int64) and ``seq_i32`` (N, T), ``sampled_logprob`` (N, T), all on the device."""
+        import math
+        model = self.model
+        T = int(input_dict.get("max_length", model.max_length))
+        temp = float(input_dict.get("temp", 1.0))
+        if T < 1:
+            raise ValueError("rollout: max_length must be at least 1")
+        if not (math.isfinite(temp) and temp > 0):
+            raise ValueError(f"rollout: temp must be finite and > 0, got {temp}")
+        wav = input_dict["wav"]
+        if not wav.is_cuda:
+            raise _lib.HipLibraryError("the training step needs tensors on a ROCm device; there is no CPU fallback")
+        N = wav.shape[0]
+        cap = torch.zeros(N, T + 1, device=wav.device, dtype=torch.int64)    # never read: no pass is teacher forced
+        d = {k: v for k, v in input_dict.items() if k not in ("cap_len",)}
+        d.update(cap=cap, ss_ratio=0.0, _use_cap=[0] * T)
+        base_seed = int(input_dict.get("dropout_seed", self.seed))
+        st = self._prepare(d, rollout=True)
+        seed = int(input_dict["seed"]) if input_dict.get("seed") is not None else base_seed
+        forced = input_dict.get("_scst_words")
+        if forced is not None:
+            forced = torch.as_tensor(forced).to(device=wav.device, dtype=torch.int32).contiguous()
+            if tuple(forced.shape) != (N, T):
+                raise ValueError(f"_scst_words must be ({N}, {T})")
+        ro = st.get("rollout")
+        if ro is None:
+            ro = st["rollout"] = {"seed": torch.zeros(1, device=wav.device, dtype=torch.int64)}
+        from .sampling import seed_word
+        ro["seed"].copy_(torch.tensor([seed_word(seed & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))   # read on the device
+        ro.update(temp=temp, forced=forced)
+        self._launch_forward(st)
+        self._saved = st
+        out = self._outputs(st)
+        out["logit"] = out["logit"].clone()
+        out["seq_i32"] = out["seq"].clone()
+        out["seq"] = out["seq_i32"].to(torch.int64)
+        out["sampled_logprob"] = st["ws"].tensor("scst_logprob")[:N * T].view(N, T).clone()
         return out
 
     # ---- backward -----------------------------------------------------------------------------------------

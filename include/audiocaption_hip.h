@@ -582,6 +582,22 @@ int ac_argmax_rows(const float* logit, long ld, int rows, int V, int* out, long 
 int ac_label_smoothing_loss(const float* logit, const long long* tgt, long tgt_ld, const int* tgt_len, int N, int T, int V,
                             float smoothing, float inv_count, float* row_loss, float* loss, float* dlogit, float gscale,
                             const float* gscale_dev, void* stream);
+/* ---- self-critical sequence training (rl_model.py:24-62; csrc/scst.hip) --------------------------
+ * ac_scst_pick: pass t of the training engine's rollout.  Clip n (row n of logit, at logit + n * ld, V <= 16384 words)
+ * draws a word with the sampler of ac_sample_rows - AC_SAMPLE_PLAIN, temp, Philox counter (t, n), seed_dev one uint64 in
+ * device memory: the draw depends on (seed, n, t) only and equals ac_sample_rows' on the same row - or, with `forced`
+ * (int32 [N][forced_ld]), takes forced[n][t].  done [N] (written at t == 0, no need to clear it) carries the finished-row
+ * rule (base.py:161-166): once a clip has emitted end_idx every later word is end_idx.  seq[n * seq_ld + t] (int32) gets
+ * the word, logprob[n * lp_ld + t] = log_softmax(logit[n])[word before the rule] / temp (base.py:249).  drawn [N]: scratch. */
+int ac_scst_pick(const float* logit, long ld, int N, int V, float temp, const uint64_t* seed_dev, int t, int end_idx,
+                 const int* forced, long forced_ld, int* done, int* drawn, int* seq, long seq_ld, float* logprob, long lp_ld,
+                 void* stream);
+/* ac_scst_loss: logit [N][T][V], seq int32 [N][seq_ld], reward f32 [N] in device memory.  mask[n][t] = (t == 0 or
+ * seq[n][t-1] != end_idx); row_loss[n*T + t] = -(log_softmax(logit[n][t])[seq[n][t]] / temp) * reward[n] * mask;
+ * loss[0] = (1 / N) sum row_loss; dlogit (optional) = [gscale_dev[0] *] (reward[n] * mask / (N * temp)) *
+ * (softmax(logit[n][t]) - onehot(seq[n][t])), exactly 0 on masked rows.  V <= 16384, temp > 0 (AC_ERR_ARG otherwise). */
+int ac_scst_loss(const float* logit, const int* seq, long seq_ld, const float* reward, float temp, int end_idx, int N, int T,
+                 int V, float* row_loss, float* loss, float* dlogit, const float* gscale_dev, void* stream);
 /* ac_gru_layer that also keeps (r, z, n, W_hn h + b_hn) per (clip, step, direction): save [B][T][2][4H]. */
 int ac_gru_layer_train(const float* gx, const float* whhT, const float* bhh, const int* lens, float* out, float* save,
                        int B, int T, int hidden, void* stream);
