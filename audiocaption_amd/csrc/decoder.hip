@@ -1229,10 +1229,22 @@ Ws carve(const ac_trm_weights* w, int R, int max_len, float* base) {
     if (_e != AC_OK) return _e; \
   } while (0)
 
+// The shapes a decoder step runs (decoder_step, launch_dec_gemm, attn_step_kernel), in one place: the A tile of a projection
+// with a fused producer holds a whole d_model row (64 | d_model <= DEC_MAX_D), the four waves of dec_gemm_kernel split a K
+// chunk into groups of 16 (64 | K) and a K beyond one chunk runs whole chunks (dim_ff <= DEC_KC or DEC_KC | dim_ff), a head
+// is one wave with a lane per channel (head width <= 64).
+inline bool step_shape_ok(int d_model, int nhead, int dim_ff) {
+  if (d_model < 64 || d_model % 64 || d_model > DEC_MAX_D) return false;
+  if (dim_ff < 64 || dim_ff % 64 || (dim_ff > DEC_KC && dim_ff % DEC_KC)) return false;
+  return nhead >= 1 && d_model % nhead == 0 && d_model / nhead <= 64;
+}
+
+// Every entry point that takes an ac_trm_weights asks this first - the size queries, the weight pack, the memory projection
+// and the searches refuse the same set, before anything is launched.
 int check_weights(const ac_trm_weights* w) {
   if (!w || w->nlayers < 1 || w->nlayers > AC_MAX_LAYERS) return AC_ERR_ARG;
-  if (w->d_model % 32 || w->d_model > 1024 || w->dim_ff % 32 || w->attn_emb_dim % 32) return AC_ERR_ARG;
-  if (w->nhead < 1 || w->d_model % w->nhead || w->d_model / w->nhead > 64) return AC_ERR_ARG;
+  if (!step_shape_ok(w->d_model, w->nhead, w->dim_ff)) return AC_ERR_ARG;
+  if (w->attn_emb_dim < 32 || w->attn_emb_dim % 32) return AC_ERR_ARG;
   return AC_OK;
 }
 

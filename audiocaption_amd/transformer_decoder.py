@@ -97,6 +97,34 @@ class TransformerDecoder(BaseDecoder):
     def _weights_key(self):
         return tuple((t.data_ptr(), t._version, t.dtype) for t in self.parameters()) + (_lib.param_generation(),)
 
+    # What the decode step runs (csrc/decoder.hip step_shape_ok / check_weights; INTEGRATION.md "Decoder shapes")
+    SUPPORTED = ("emb_dim a multiple of 64 up to 512; head width emb_dim / nhead at most 64; dim_feedforward a multiple of 64 "
+                 "up to 512, or a multiple of 512; attn_emb_dim a multiple of 32; 1 to %d layers" % _lib.AC_MAX_LAYERS)
+
+    def check_supported(self):
+        """Raise HipLibraryError, naming the limit, for a shape the HIP decoder does not run.  Host arithmetic only: asked by
+        ``weights()`` before a device pointer is taken, so a refusal precedes every buffer, projection and capture."""
+        d, h, ff, A_, n = self.d_model, self.nhead, self.dim_feedforward, self.attn_emb_dim, self.nlayers
+        why = None
+        if d < 64 or d % 64:
+            why = f"emb_dim {d} is not a multiple of 64"
+        elif d > 512:
+            why = f"emb_dim {d} exceeds 512"
+        elif h < 1 or d % h:
+            why = f"emb_dim {d} does not divide into nhead {h} heads"
+        elif d // h > 64:
+            why = f"head width emb_dim / nhead = {d // h} exceeds 64"
+        elif ff < 64 or ff % 64:
+            why = f"dim_feedforward {ff} is not a multiple of 64"
+        elif ff > 512 and ff % 512:
+            why = f"dim_feedforward {ff} is above 512 and not a multiple of 512"
+        elif A_ < 32 or A_ % 32:
+            why = f"attn_emb_dim {A_} is not a multiple of 32"
+        elif n < 1 or n > _lib.AC_MAX_LAYERS:
+            why = f"nlayers {n} is outside 1..{_lib.AC_MAX_LAYERS}"
+        if why is not None:
+            raise _lib.HipLibraryError(f"TransformerDecoder (HIP path): {why}.  Supported: {self.SUPPORTED}")
+
     def weights(self):
         """ac_trm_weights struct of device pointers (rebuilt when a parameter changes)."""
         key = self._weights_key()
@@ -109,8 +137,7 @@ class TransformerDecoder(BaseDecoder):
             keep.append(t)
             return ctypes.c_void_p(ptr(t).value)
 
-        if self.nlayers > _lib.AC_MAX_LAYERS:
-            raise ValueError("too many decoder layers for the HIP path")
+        self.check_supported()
         w = _lib.AcTrmWeights()
         w.d_model, w.nhead, w.nlayers, w.dim_ff = self.d_model, self.nhead, self.nlayers, self.dim_feedforward
         w.vocab, w.max_pos, w.attn_emb_dim = self.vocab_size, self.pos_encoder.pe.shape[0], self.attn_emb_dim
@@ -190,12 +217,12 @@ class TransformerDecoder(BaseDecoder):
     def memory(self, attn_emb):
         """attn_emb (R, Tm, attn_emb_dim) -> memkv (nlayers, R*Tm, 2*d): attn_proj + cross-attn K/V."""
         lib = _lib.load()
+        w = self.weights()   # first: an unsupported shape is refused before any buffer exists
         attn_emb = f32c(attn_emb)
         R, Tm, _ = attn_emb.shape
         memkv = torch.empty(self.nlayers, R * Tm, 2 * self.d_model, device=attn_emb.device, dtype=torch.float32)
         tmp = torch.empty(R * Tm, self.d_model, device=attn_emb.device, dtype=torch.float32)
-        check(lib.ac_trm_memory(ctypes.byref(self.weights()), ptr(attn_emb), R, Tm, ptr(memkv), ptr(tmp), stream()),
-              "ac_trm_memory")
+        check(lib.ac_trm_memory(ctypes.byref(w), ptr(attn_emb), R, Tm, ptr(memkv), ptr(tmp), stream()), "ac_trm_memory")
         return memkv
 
     def forward(self, input_dict):
@@ -204,6 +231,7 @@ class TransformerDecoder(BaseDecoder):
                 "TransformerDecoder (HIP path): in train mode the decoder only runs inside the whole-model training "
                 "step (audiocaption_amd.train.TrainEngine / TransformerModel.forward with mode='train')")
         lib = _lib.load()
+        self.weights()       # first: an unsupported shape is refused before any buffer exists
         attn_emb = input_dict["attn_emb"]
         dev = attn_emb.device
         word = input_dict["word"].to(dev)

@@ -606,6 +606,7 @@ class TransformerModel(CaptionModel):
         # shape (second use) into HIP graphs over static buffers and replayed - a host-launched chain of ~280 small
         # dependent kernels cannot keep up once it shares the device with the next batches' encoders.
         lib = _lib.load()
+        dec.weights()                              # first: an unsupported decoder shape is refused before any buffer exists
         ld = max_length + 1
         cap = beam * max_length                    # upper bound of finished beams per clip
         use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"

@@ -247,7 +247,10 @@ int ac_gru_layer_split(const float* gx, const float* whh, const float* bhh, cons
 int ac_mean_with_lens(const float* x, const int* lens, float* out, int B, int T, int C, int add_max,
                       void* stream);
 
-/* ---- Transformer decoder ------------------------------------------------------------------------ */
+/* ---- Transformer decoder ------------------------------------------------------------------------
+ * Shapes: d_model a multiple of 64 up to 512; nhead divides d_model, head width d_model / nhead <= 64; dim_ff a multiple of
+ * 64 up to 512, or a multiple of 512; attn_emb_dim a multiple of 32; 1 <= nlayers <= AC_MAX_LAYERS.  Every entry point below
+ * that takes an ac_trm_weights refuses any other shape before it launches anything (AC_ERR_ARG; the size queries: -1). */
 #define AC_MAX_LAYERS 8
 typedef struct {
   const float *sa_in_w, *sa_in_b, *sa_out_w, *sa_out_b; /* self_attn.in_proj / out_proj       */

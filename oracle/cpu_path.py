@@ -255,7 +255,7 @@ def transformer_encoder_forward(state, attn, attn_len, prefix="", nlayers=2, nhe
 # greedy decoding (base.py:152-218, transformer_model.py:34-57)
 # ----------------------------------------------------------------------------------------
 def greedy_decode(state, attn_emb, attn_emb_len, max_length=20, prefix="decoder.",
-                  start_idx=START_IDX, end_idx=END_IDX, pad_idx=PAD_IDX, force_steps=False):
+                  start_idx=START_IDX, end_idx=END_IDX, pad_idx=PAD_IDX, force_steps=False, nlayers=2, nhead=4):
     """Returns seq (B, max_length) int64 (end_idx after a clip finishes), logit (B, L, V),
     sampled_logprob (B, L), embed (B, L, d) and ``steps`` = decoder calls executed.  Columns after
     the early stop are left at their init (logit/embed there are unspecified in the reference,
@@ -263,14 +263,15 @@ def greedy_decode(state, attn_emb, attn_emb_len, max_length=20, prefix="decoder.
     B = attn_emb.shape[0]
     V, d = state[prefix + "classifier.weight"].shape
     seq = torch.full((B, max_length), end_idx, dtype=torch.long)
-    logit = torch.zeros(B, max_length, V)
-    logprob = torch.zeros(B, max_length)
-    embed = torch.zeros(B, max_length, d)
+    dt = state[prefix + "classifier.weight"].dtype   # float32 as the reference; a float64 state is evaluated in float64
+    logit = torch.zeros(B, max_length, V, dtype=dt)
+    logprob = torch.zeros(B, max_length, dtype=dt)
+    embed = torch.zeros(B, max_length, d, dtype=dt)
     unfinished = None
     steps = 0
     for t in range(max_length):
         word = torch.cat([torch.full((B, 1), start_idx, dtype=torch.long), seq[:, :t]], dim=1)
-        out = decoder_forward(state, word, attn_emb, attn_emb_len, word == pad_idx, prefix)
+        out = decoder_forward(state, word, attn_emb, attn_emb_len, word == pad_idx, prefix, nlayers, nhead)
         logit_t = out["logit"][:, -1]
         lp, w = torch.max(torch.log_softmax(logit_t, dim=1), 1)
         logit[:, t], seq[:, t], logprob[:, t], embed[:, t] = logit_t, w, lp, out["embed"][:, -1]
@@ -287,7 +288,8 @@ def greedy_decode(state, attn_emb, attn_emb_len, max_length=20, prefix="decoder.
 # beam search (base.py:254-361, transformer_model.py:59-86)
 # ----------------------------------------------------------------------------------------
 def beam_search(state, attn_emb, attn_emb_len, beam_size=3, max_length=20, temp=1.0, prefix="decoder.",
-                start_idx=START_IDX, end_idx=END_IDX, pad_idx=PAD_IDX, n_best=False, n_best_size=None, trace=None):
+                start_idx=START_IDX, end_idx=END_IDX, pad_idx=PAD_IDX, n_best=False, n_best_size=None, trace=None,
+                nlayers=2, nhead=4):
     """base.py:254-361.  n_best: "seq" is (B, n_best_size, max_length), the finished beams of a clip by descending
     length-normalised score (base.py:258-263,354-358).  trace (a list, fixtures only): receives one record per (clip,
     step) - the parent beam of every kept candidate and which of them ended."""
@@ -307,7 +309,7 @@ def beam_search(state, attn_emb, attn_emb_len, beam_size=3, max_length=20, temp=
         for t in range(max_length):
             start = torch.full((beam_size, 1), start_idx, dtype=torch.long)
             word = start if t == 0 else torch.cat([start, seq], dim=1)
-            logit_t = decoder_forward(state, word, mem_i, len_i, word == pad_idx, prefix)["logit"][:, -1]
+            logit_t = decoder_forward(state, word, mem_i, len_i, word == pad_idx, prefix, nlayers, nhead)["logit"][:, -1]
             lp = torch.log_softmax(torch.log_softmax(logit_t, dim=1) / temp, dim=1)
             lp = topk_logprob.unsqueeze(1) + lp
             if t == 0:
