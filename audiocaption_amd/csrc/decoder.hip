@@ -71,17 +71,6 @@ __device__ __forceinline__ bool rows_live(const Live& L, int r0, int r1) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// x[r][:] = E[tok[r][t]] * sqrt(d) + pe[t]                     (transformer_decoder.py:89-91)
-// ---------------------------------------------------------------------------------------------
-__global__ void embed_pe_kernel(const int* tok, long tok_stride, int t, const float* emb, const float* pe,
-                                float scale, float* x, int d) {
-  const int r = blockIdx.x;
-  const int w = tok[(size_t)r * tok_stride + t];
-  for (int c = threadIdx.x; c < d; c += blockDim.x)
-    x[(size_t)r * d + c] = emb[(size_t)w * d + c] * scale + pe[(size_t)t * d + c];
-}
-
-// ---------------------------------------------------------------------------------------------
 // out = LayerNorm(x + y) * w + b, one wave per row
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* x, const float* y, const float* w,
@@ -1255,295 +1244,305 @@ int launch_ln(const float* x, const float* y, const float* w, const float* b, fl
   return ac_check_launch();
 }
 
-// One decoder position for R rows.  tokens/mask: [R][tok_stride]; the input token is column t.
-// cache: active KV cache set.  Returns through `fin` the operands of the LAST residual join
-// (embed = LayerNorm(fin.x + fin.y) with the last layer's norm3), which the caller fuses into the
-// classifier projection; 8 launches per layer: the residual joins and the embedding never run alone.
-// `live` (struct Live): the rows of finished segments of an on-device search are skipped by every kernel of the step
-// (Live() = every row runs; the wide route's kernels do not skip - the search clears what they wrote, search_finalize_kernel).
-// Offsets (in floats) of the fragment-packed step weights inside ac_trm_weights::step_pk, fixed order:
-// per layer sa_in, sa_out, ca_q, ca_out, l1, l2; then the classifier.
+// Offsets (in floats) of the fragment-packed step weights inside ac_trm_weights::step_pk, fixed order: per layer the six
+// projections, three transposed copies, the six wide packs; then the classifier and its wide pack.
+struct ProjOffsets { size_t sa_in, sa_out, ca_q, ca_out, l1, l2; };
 struct PackLayout {
-  size_t sa_in, sa_out, ca_q, ca_out, l1, l2;
+  ProjOffsets n;                    // dec_gemm_kernel's fragment order
   size_t sa_outT, ca_qT, ca_outT;   // transposed [k][n] copies for the fused per-row sub-layer kernel
-  size_t w_sa_in, w_sa_out, w_ca_q, w_ca_out, w_l1, w_l2;   // three-plane bf16 packs of the wide route (csrc/decoder_wide.hip)
+  ProjOffsets w;                    // three-plane bf16 packs of the wide route (csrc/decoder_wide.hip)
 };
+struct PackOffsets { PackLayout layer[AC_MAX_LAYERS]; size_t cls, wcls, total; };   // cls / wcls: the classifier's two packs
 inline size_t packed_floats(int N, int K) { return (size_t)((N + DEC_T - 1) / DEC_T) * DEC_T * K; }
-inline size_t pack_layout(const ac_trm_weights* w, PackLayout* L /* [nlayers] or null */, size_t* cls_off,
-                          size_t* wcls_off = nullptr) {
+inline PackOffsets pack_layout(const ac_trm_weights* w) {
   const int d = w->d_model, ff = w->dim_ff;
   const bool wide = wide_shape_ok(w);
   auto wf = [&](int N, int K) { return wide ? (size_t)ac_dec_wide_packed_floats(N, K) : (size_t)0; };
+  PackOffsets po = {};
   size_t off = 0;
   for (int l = 0; l < w->nlayers; ++l) {
-    PackLayout t;
-    t.sa_in = off; off += packed_floats(3 * d, d);
-    t.sa_out = off; off += packed_floats(d, d);
-    t.ca_q = off; off += packed_floats(d, d);
-    t.ca_out = off; off += packed_floats(d, d);
-    t.l1 = off; off += packed_floats(ff, d);
-    t.l2 = off; off += packed_floats(d, ff);
+    PackLayout& t = po.layer[l];
+    t.n.sa_in = off; off += packed_floats(3 * d, d);
+    t.n.sa_out = off; off += packed_floats(d, d);
+    t.n.ca_q = off; off += packed_floats(d, d);
+    t.n.ca_out = off; off += packed_floats(d, d);
+    t.n.l1 = off; off += packed_floats(ff, d);
+    t.n.l2 = off; off += packed_floats(d, ff);
     t.sa_outT = off; off += (size_t)d * d;
     t.ca_qT = off; off += (size_t)d * d;
     t.ca_outT = off; off += (size_t)d * d;
-    t.w_sa_in = off; off += wf(3 * d, d);
-    t.w_sa_out = off; off += wf(d, d);
-    t.w_ca_q = off; off += wf(d, d);
-    t.w_ca_out = off; off += wf(d, d);
-    t.w_l1 = off; off += wf(ff, d);
-    t.w_l2 = off; off += wf(d, ff);
-    if (L) L[l] = t;
+    t.w.sa_in = off; off += wf(3 * d, d);
+    t.w.sa_out = off; off += wf(d, d);
+    t.w.ca_q = off; off += wf(d, d);
+    t.w.ca_out = off; off += wf(d, d);
+    t.w.l1 = off; off += wf(ff, d);
+    t.w.l2 = off; off += wf(d, ff);
   }
-  if (cls_off) *cls_off = off;
-  off += packed_floats(w->vocab, d);
-  if (wcls_off) *wcls_off = off;
-  off += wf(w->vocab, d);
-  return off;
+  po.cls = off; off += packed_floats(w->vocab, d);
+  po.wcls = off; off += wf(w->vocab, d);
+  po.total = off;
+  return po;
 }
 
-struct StepOut {
-  const float* x;
-  const float* y;
-  const float* ln_w;
-  const float* ln_b;
+// Which launches make up a decode position over R rows: decided ONCE per step (decoder_step) and handed to classifier_step
+// with the step's result.  Every AUDIOCAPTION_DEC_* switch of this file is read here, and not all at the same time:
+//   on every call (tests switch them; a captured graph keeps what it was captured with):
+//     AUDIOCAPTION_DEC_WIDE_MIN, AUDIOCAPTION_DEC_HYBRID, AUDIOCAPTION_DEC_ROW=gemm, AUDIOCAPTION_DEC_WIDE_CLS_NTB
+//   latched by the first step of the process (development switches; so is AUDIOCAPTION_BEAM_TOPK in ac_trm_beam_step):
+//     AUDIOCAPTION_DEC_ROW=split, AUDIOCAPTION_DEC_NTB, AUDIOCAPTION_DEC_CLS_GEMM, AUDIOCAPTION_DEC_CLS_NTB
+struct Route {
+  bool wide = false;                       // the wide route; else the fused per-row route (rows) or the general one
+  bool rows = false, rows_split = false;   // rows_split: the two per-row sub-layers as a launch each
+  bool hybrid = false;                     // narrow, but the joined QKV projections and the classifier on their wide twins
+  int ntb = 1;                             // column tiles per block of the single-chunk projections
+  bool cls_ln_gemm = false;                // the classifier as LayerNorm + ac_gemm (where it has room for the normalised rows)
+  int cls_ntb = 4, wide_cls_ntb = 2;       // column tiles per block of the classifier projection / of its wide twin
 };
 
-// AUDIOCAPTION_DEC_WIDE_MIN=n (default 0 = never): a step over n rows or more takes the wide route.  Opt-in, because it does
-// not pay on this part: stand-alone it is 145 / 202 us per step at 256 / 768 rows against 115 / 193 for the narrow route
-// (22 launches per step instead of 10, each ~3 us of launch overhead + a 3-5 us critical path, although a projection
-// occupies 32-128 workgroups for 3-5 us instead of every CU for 7-18), and beside the next batches' encoders the step
-// costs what its DURATION is, not its CU time: headline 13.85 k vs 14.10 k clips/s, EffB2-Trm 20.65 k vs 20.55 k
-// (EXPERIMENTS.md, round 6).
-inline bool wide_route(const ac_trm_weights* w, int R) {
-  const char* e = getenv("AUDIOCAPTION_DEC_WIDE_MIN");   // read per call (tests switch it); a captured graph keeps its route
+Route resolve_route(const ac_trm_weights* w, int R, int Tm, int t) {
+  auto is = [](const char* v, const char* want) { return v && !strcmp(v, want); };
+  Route rt;
+  // AUDIOCAPTION_DEC_WIDE_MIN=n (default 0 = never): a step over n rows or more takes the wide route.  Opt-in, because it does
+  // not pay on this part: stand-alone it is 145 / 202 us per step at 256 / 768 rows against 115 / 193 for the narrow route
+  // (22 launches per step instead of 10, each ~3 us of launch overhead + a 3-5 us critical path, although a projection
+  // occupies 32-128 workgroups for 3-5 us instead of every CU for 7-18), and beside the next batches' encoders the step
+  // costs what its DURATION is, not its CU time: headline 13.85 k vs 14.10 k clips/s, EffB2-Trm 20.65 k vs 20.55 k
+  // (EXPERIMENTS.md, round 6).
+  const char* e = getenv("AUDIOCAPTION_DEC_WIDE_MIN");
   const int wide_min = e ? atoi(e) : 0;
-  return wide_min > 0 && R >= wide_min && wide_shape_ok(w) && w->d_model / w->nhead <= 64 && w->d_model % w->nhead == 0;
-}
-
-// AUDIOCAPTION_DEC_HYBRID=1 (default off): from 512 rows on (a beam search over grouped batches) the QKV projection with the
-// residual join in its prologue and the classifier take their wide twins (csrc/decoder_wide.hip).  Stand-alone those are the
-// two launches of the narrow route furthest from their arithmetic (20 and 30 + 5 us at 768 rows against 11 and 27); inside the
-// EffB2-Trm pipeline the wide classifier's one-workgroup-per-CU blocks take 43 us beside the encoder and the step does not move
-// (20.41 vs 20.41 k clips/s, 30 s / beam 4: 7.70 vs 7.70 k): opt-in, kept for the record.
-inline bool hybrid_route(const ac_trm_weights* w, int R) {
-  const char* e = getenv("AUDIOCAPTION_DEC_HYBRID");
-  return e && !strcmp(e, "1") && R >= 512 && wide_shape_ok(w);
-}
-
-int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
-                 int max_len, int t, const int* tok, const unsigned char* mask, long tok_stride, float* cache,
-                 const Ws& ws, StepOut* fin, hipStream_t s, const Live& live) {
-  const int d = w->d_model, hd = d / w->nhead;
-  const float scale = 1.0f / sqrtf((float)hd);
-  if (t >= w->max_pos || d > DEC_MAX_D || d % 64 || w->dim_ff % 64 || !w->step_pk) return AC_ERR_ARG;
-  PackLayout PL[AC_MAX_LAYERS];
-  pack_layout(w, PL, nullptr);
-  const float* pk = w->step_pk;
-  const size_t Rm = (size_t)(R / row_div) * Tm;  // memory rows
-  float* xa = ws.x;    // residual stream, ping-pong: a join reads one and writes the other
-  float* xb = ws.x2;
-  DecGemmParams g;
-  g.tok = tok; g.tok_stride = tok_stride; g.t = t; g.emb = w->emb; g.pe = w->pe; g.emb_scale = sqrtf((float)d);
-  g.live = live;
-  // column tiles per block of the single-chunk projections: two from 512 rows on (beam search over grouped batches: 768
-  // rows - the A tile is staged once for both, EffB2-Trm 19.15 -> 19.40 k clips/s; at 256 rows and below no difference).  The
-  // arithmetic of an output does not depend on it.  AUDIOCAPTION_DEC_NTB overrides (development).
-  static const int dev_ntb = getenv("AUDIOCAPTION_DEC_NTB") ? atoi(getenv("AUDIOCAPTION_DEC_NTB")) : 0;
-  g.M = R; g.ntb = dev_ntb > 0 ? dev_ntb : (R >= 512 ? 2 : 1);
-  // pending join carried into the next projection: x_next = LayerNorm(jx + jy) * jw + jb
-  const float *jx = nullptr, *jy = nullptr, *jw = nullptr, *jb = nullptr;
-  // the reference's decoder shape (d_model 256 = 4 heads of 64) takes the fused per-row sub-layer kernel: 5 launches per
+  rt.wide = wide_min > 0 && R >= wide_min && wide_shape_ok(w) && w->d_model / w->nhead <= 64 && w->d_model % w->nhead == 0;
+  // AUDIOCAPTION_DEC_HYBRID=1 (default off): from 512 rows on (a beam search over grouped batches) the QKV projection with the
+  // residual join in its prologue and the classifier take their wide twins (csrc/decoder_wide.hip).  Stand-alone those are the
+  // two launches of the narrow route furthest from their arithmetic (20 and 30 + 5 us at 768 rows against 11 and 27); inside the
+  // EffB2-Trm pipeline the wide classifier's one-workgroup-per-CU blocks take 43 us beside the encoder and the step does not move
+  // (20.41 vs 20.41 k clips/s, 30 s / beam 4: 7.70 vs 7.70 k): opt-in, kept for the record.
+  rt.hybrid = !rt.wide && is(getenv("AUDIOCAPTION_DEC_HYBRID"), "1") && R >= 512 && wide_shape_ok(w);
+  // the reference's decoder shape (d_model 256 = 4 heads of 64) takes the fused per-row sub-layer kernel: 4 launches per
   // layer instead of 8; any other shape the general 8-launch sequence
   // AUDIOCAPTION_DEC_ROW=gemm: the general 18-launch sequence (attn_step_kernel + dec_gemm_kernel) instead of the per-row
   // kernels.  (The row kernels once gave co-runner-dependent results: built with packed-f32 VALU instructions their
   // matrix-vector products broke beside MFMA-heavy kernels of another stream - see audiocaption_amd/build.py; every mode is
   // now held to tests/test_gpu_model.py::test_decode_is_bit_stable_beside_matrix_heavy_kernels.)
-  const char* dec_row = getenv("AUDIOCAPTION_DEC_ROW");   // read per call (tests compare the sequences; a captured graph keeps its own)
-  const bool no_rows = dec_row && !strcmp(dec_row, "gemm");
-  const bool fused = d == ROW_D && w->nhead == ROW_H && t + 1 <= MAX_KEYS && Tm <= MAX_KEYS && !no_rows;
-  if (wide_route(w, R)) {
-    // ---- the wide route: 8 launches per layer, every projection a few dozen 32-row workgroups on the bf16 matrix cores
-    // (csrc/decoder_wide.hip), the attention sub-layers one wave per (row, head).  Rows that feed a projection without a
-    // residual join in front (attention contexts, feed-forward hidden rows) travel as bf16-plane fragment packs ----
-    const float emb_scale = sqrtf((float)d);
-    auto fused = [&](int pro, const float* X, const float* Y2, const float* lw, const float* lb, float* xout, size_t wp,
-                     const float* bias, float* Y, long ldy, int N, int relu, int split_out) {
-      return ac_dec_wide_gemm(pro, X, d, Y2, d, lw, lb, tok, tok_stride, t, w->emb, w->pe, emb_scale, xout, d, pk + wp, bias, Y,
-                              ldy, R, N, d, relu, 1, split_out, (void*)s);
-    };
-    auto packed = [&](const float* Xs, size_t wp, const float* bias, float* Y, int N, int K) {
-      return ac_dec_wide_gemm(0, Xs, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0.f, nullptr, 0, pk + wp,
-                              bias, Y, N, R, N, K, 0, 1, 0, (void*)s);
-    };
-    for (int l = 0; l < w->nlayers; ++l) {
-      const ac_trm_layer& L = w->layer[l];
-      AC_TRY(fused(l == 0 ? 1 : 2, jx, jy, jw, jb, xa, PL[l].w_sa_in, L.sa_in_b, ws.qkv, 3 * d, 3 * d, 0, 0));
-      AttnParams a;
-      float* Kc = cache + (size_t)(2 * l) * ws.cache_set_stride;
-      float* Vc = cache + (size_t)(2 * l + 1) * ws.cache_set_stride;
-      a.q = ws.qkv; a.ldq = 3 * d;
-      a.K = Kc; a.V = Vc; a.Kw = Kc; a.Vw = Vc;
-      a.row_stride = (long)max_len * d; a.key_stride = d; a.row_div = 1; a.nkeys = t + 1;
-      a.key_len = nullptr; a.key_mask = mask; a.mask_stride = tok_stride;
-      a.new_k = ws.qkv + d; a.new_v = ws.qkv + 2 * d; a.ld_new = 3 * d;
-      a.out = nullptr; a.ldo = 0; a.hd = hd; a.scale = scale;
-      a.out_pk = (unsigned char*)ws.attp; a.pk_kst = d / 16;
-      hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
-      AC_TRY(ac_check_launch());
-      AC_TRY(packed(ws.attp, PL[l].w_sa_out, L.sa_out_b, ws.tmp, d, d));
-      AC_TRY(fused(2, xa, ws.tmp, L.n1_w, L.n1_b, xb, PL[l].w_ca_q, L.ca_in_b, ws.q2, d, d, 0, 0));
-      const float* mk = memkv + (size_t)l * Rm * 2 * d;
-      a.q = ws.q2; a.ldq = d;
-      a.K = mk; a.V = mk + d; a.Kw = nullptr; a.Vw = nullptr;
-      a.row_stride = (long)Tm * 2 * d; a.key_stride = 2 * d; a.row_div = row_div; a.nkeys = Tm;
-      a.key_len = mem_len; a.key_mask = nullptr; a.mask_stride = 0;
-      a.new_k = nullptr; a.new_v = nullptr; a.ld_new = 0;
-      hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
-      AC_TRY(ac_check_launch());
-      AC_TRY(packed(ws.attp, PL[l].w_ca_out, L.ca_out_b, ws.tmp, d, d));
-      AC_TRY(fused(2, xb, ws.tmp, L.n2_w, L.n2_b, xa, PL[l].w_l1, L.l1_b, ws.ffp, 0, w->dim_ff, 1, 1));
-      AC_TRY(packed(ws.ffp, PL[l].w_l2, L.l2_b, ws.tmp, d, w->dim_ff));
-      jx = xa; jy = ws.tmp; jw = L.n3_w; jb = L.n3_b;
-      float* tsw = xa; xa = xb; xb = tsw;
-    }
-    fin->x = jx; fin->y = jy; fin->ln_w = jw; fin->ln_b = jb;
-    return AC_OK;
-  }
-  for (int l = 0; l < w->nlayers; ++l) {
-    const ac_trm_layer& L = w->layer[l];
-    // ---- self attention: QKV projection with the layer input produced in its prologue ----
-    g.Wp = pk + PL[l].sa_in; g.bias = L.sa_in_b; g.Y = ws.qkv; g.ldy = 3 * d; g.N = 3 * d; g.K = d; g.relu = 0;
-    g.xout = xa; g.ldxo = d;
-    if (l == 0) {
-      AC_TRY(launch_dec_gemm<PRO_EMBED>(g, s));
-    } else if (hybrid_route(w, R)) {
-      AC_TRY(ac_dec_wide_gemm(2, jx, d, jy, d, jw, jb, nullptr, 0, 0, nullptr, nullptr, 0.f, xa, d, pk + PL[l].w_sa_in, L.sa_in_b,
-                              ws.qkv, 3 * d, R, 3 * d, d, 0, 1, 0, (void*)s));
-    } else {
-      g.X = jx; g.ldx = d; g.Y2 = jy; g.ldy2 = d; g.ln_w = jw; g.ln_b = jb;
-      AC_TRY(launch_dec_gemm<PRO_ADDLN>(g, s));
-    }
-    AttnParams a;
-    float* Kc = cache + (size_t)(2 * l) * ws.cache_set_stride;
-    float* Vc = cache + (size_t)(2 * l + 1) * ws.cache_set_stride;
-    a.q = ws.qkv; a.ldq = 3 * d;
-    a.K = Kc; a.V = Vc; a.Kw = Kc; a.Vw = Vc;
-    a.row_stride = (long)max_len * d; a.key_stride = d; a.row_div = 1; a.nkeys = t + 1;
-    a.key_len = nullptr; a.key_mask = mask; a.mask_stride = tok_stride;
-    a.new_k = ws.qkv + d; a.new_v = ws.qkv + 2 * d; a.ld_new = 3 * d;
-    a.out = ws.att; a.ldo = d; a.hd = hd; a.scale = scale;
-    a.live = live;
-    if (fused) {
-      // ---- self attention + out-projection + LN1 + cross query projection: one launch, one row per workgroup ----
-      RowParams rp;
-      rp.a = a;
-      rp.res = xa; rp.ldres = d;
-      rp.WoT = pk + PL[l].sa_outT; rp.bo = L.sa_out_b; rp.ln_w = L.n1_w; rp.ln_b = L.n1_b;
-      rp.xout = xb; rp.ldxo = d;
-      rp.WqT = pk + PL[l].ca_qT; rp.bq = L.ca_in_b; rp.qout = ws.q2; rp.ldqo = d;
-      static const bool two_launches = getenv("AUDIOCAPTION_DEC_ROW") && !strcmp(getenv("AUDIOCAPTION_DEC_ROW"), "split");
-      const RowParams rp_self = rp;
-      if (two_launches) {
-        hipLaunchKernelGGL(dec_row_kernel, dim3(R), dim3(256), 0, s, rp);
-        AC_TRY(ac_check_launch());
-      }
-      // ---- cross attention + out-projection + LN2 ----
-      const float* mkf = memkv + (size_t)l * Rm * 2 * d;
-      rp.a.q = ws.q2; rp.a.ldq = d;
-      rp.a.K = mkf; rp.a.V = mkf + d; rp.a.Kw = nullptr; rp.a.Vw = nullptr;
-      rp.a.row_stride = (long)Tm * 2 * d; rp.a.key_stride = 2 * d; rp.a.row_div = row_div; rp.a.nkeys = Tm;
-      rp.a.key_len = mem_len; rp.a.key_mask = nullptr; rp.a.mask_stride = 0;
-      rp.a.new_k = nullptr; rp.a.new_v = nullptr; rp.a.ld_new = 0;
-      rp.res = xb; rp.ldres = d;
-      rp.WoT = pk + PL[l].ca_outT; rp.bo = L.ca_out_b; rp.ln_w = L.n2_w; rp.ln_b = L.n2_b;
-      rp.xout = xa; rp.ldxo = d;
-      rp.WqT = nullptr; rp.bq = nullptr; rp.qout = nullptr; rp.ldqo = 0;
-      if (two_launches) hipLaunchKernelGGL(dec_row_kernel, dim3(R), dim3(256), 0, s, rp);
-      else hipLaunchKernelGGL(dec_row2_kernel, dim3(R), dim3(256), 0, s, rp_self, rp);   // both sub-layers, one launch
-      AC_TRY(ac_check_launch());
-      // ---- feed forward on the materialised x2 ----
-      g.X = xa; g.ldx = d; g.Wp = pk + PL[l].l1; g.bias = L.l1_b; g.Y = ws.ff; g.ldy = w->dim_ff; g.N = w->dim_ff;
-      g.K = d; g.relu = 1; g.xout = nullptr;
-      AC_TRY(launch_dec_gemm<PRO_PLAIN>(g, s));
-      g.X = ws.ff; g.ldx = w->dim_ff; g.Wp = pk + PL[l].l2; g.bias = L.l2_b; g.Y = ws.tmp; g.ldy = d;
-      g.N = d; g.K = w->dim_ff; g.relu = 0; g.xout = nullptr;
-      AC_TRY(launch_dec_gemm<PRO_PLAIN>(g, s));   // K = dim_ff may exceed one chunk: the launcher then takes one tile per block
-      jx = xa; jy = ws.tmp; jw = L.n3_w; jb = L.n3_b;
-      float* tsw = xa; xa = xb; xb = tsw;
-      continue;
-    }
-    hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
-    AC_TRY(ac_check_launch());
-    g.X = ws.att; g.ldx = d; g.Wp = pk + PL[l].sa_out; g.bias = L.sa_out_b; g.Y = ws.tmp; g.ldy = d;
-    g.N = d; g.K = d; g.relu = 0; g.xout = nullptr;
-    AC_TRY(launch_dec_gemm<PRO_PLAIN>(g, s));
-    // ---- cross attention: query projection of x1 = LN1(x + self_attn) ----
-    g.X = xa; g.ldx = d; g.Y2 = ws.tmp; g.ldy2 = d; g.ln_w = L.n1_w; g.ln_b = L.n1_b;
-    g.Wp = pk + PL[l].ca_q; g.bias = L.ca_in_b; g.Y = ws.q2; g.ldy = d; g.N = d; g.K = d; g.relu = 0;
-    g.xout = xb; g.ldxo = d;
-    AC_TRY(launch_dec_gemm<PRO_ADDLN>(g, s));
-    const float* mk = memkv + (size_t)l * Rm * 2 * d;
-    a.q = ws.q2; a.ldq = d;
-    a.K = mk; a.V = mk + d; a.Kw = nullptr; a.Vw = nullptr;
-    a.row_stride = (long)Tm * 2 * d; a.key_stride = 2 * d; a.row_div = row_div; a.nkeys = Tm;
-    a.key_len = mem_len; a.key_mask = nullptr; a.mask_stride = 0;
-    a.new_k = nullptr; a.new_v = nullptr; a.ld_new = 0;
-    hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
-    AC_TRY(ac_check_launch());
-    g.X = ws.att; g.ldx = d; g.Wp = pk + PL[l].ca_out; g.bias = L.ca_out_b; g.Y = ws.tmp; g.ldy = d;
-    g.N = d; g.K = d; g.relu = 0; g.xout = nullptr;
-    AC_TRY(launch_dec_gemm<PRO_PLAIN>(g, s));
-    // ---- feed forward on x2 = LN2(x1 + cross_attn) ----
-    g.X = xb; g.ldx = d; g.Y2 = ws.tmp; g.ldy2 = d; g.ln_w = L.n2_w; g.ln_b = L.n2_b;
-    g.Wp = pk + PL[l].l1; g.bias = L.l1_b; g.Y = ws.ff; g.ldy = w->dim_ff; g.N = w->dim_ff; g.K = d; g.relu = 1;
-    g.xout = xa; g.ldxo = d;
-    AC_TRY(launch_dec_gemm<PRO_ADDLN>(g, s));
-    g.X = ws.ff; g.ldx = w->dim_ff; g.Wp = pk + PL[l].l2; g.bias = L.l2_b; g.Y = ws.tmp; g.ldy = d;
-    g.N = d; g.K = w->dim_ff; g.relu = 0; g.xout = nullptr;
-    AC_TRY(launch_dec_gemm<PRO_PLAIN>(g, s));
-    // x3 = LN3(x2 + ff) is produced by the next consumer (next layer's QKV or the caller's projection)
-    jx = xa; jy = ws.tmp; jw = L.n3_w; jb = L.n3_b;
-    float* tswap = xa; xa = xb; xb = tswap;  // next layer writes its input into the other buffer
-  }
-  fin->x = jx; fin->y = jy; fin->ln_w = jw; fin->ln_b = jb;
-  return AC_OK;
-}
-
-// logits[R, V] = LayerNorm(fin.x + fin.y) W_cls^T, the normalised rows also stored to xout (= `embed`)
-int classifier_step(const ac_trm_weights* w, const StepOut& fin, int R, float* xout, long ldxo, float* logit,
-                    long ldl, hipStream_t s, const Live& live, float* scratch = nullptr) {
+  // AUDIOCAPTION_DEC_ROW=split: dec_row_kernel per sub-layer (5 launches per layer) instead of one dec_row2_kernel.
+  static const bool split = is(getenv("AUDIOCAPTION_DEC_ROW"), "split");
+  rt.rows = !rt.wide && w->d_model == ROW_D && w->nhead == ROW_H && t + 1 <= MAX_KEYS && Tm <= MAX_KEYS &&
+            !is(getenv("AUDIOCAPTION_DEC_ROW"), "gemm");
+  rt.rows_split = rt.rows && split;
+  // column tiles per block of the single-chunk projections: two from 512 rows on (beam search over grouped batches: 768
+  // rows - the A tile is staged once for both, EffB2-Trm 19.15 -> 19.40 k clips/s; at 256 rows and below no difference).  The
+  // arithmetic of an output does not depend on it.  AUDIOCAPTION_DEC_NTB overrides (development).
+  static const int dev_ntb = getenv("AUDIOCAPTION_DEC_NTB") ? atoi(getenv("AUDIOCAPTION_DEC_NTB")) : 0;
+  rt.ntb = dev_ntb > 0 ? dev_ntb : (R >= 512 ? 2 : 1);
   // From 512 rows on (beam search over grouped batches: 768 rows x 4368 words) the 16 x 16-tile projection re-reads the
   // classifier once per 16 rows: 47 us per step; the residual join as its own launch + the tiled exact-f32 GEMM (ac_gemm)
   // take 4 + 30.  Another summation order than the projection's (last bits of the logits; not a precision change).
   // AUDIOCAPTION_DEC_CLS_GEMM=0: the projection at every row count.
-  if ((wide_route(w, R) || hybrid_route(w, R)) && (!xout || (ldxo % 4 == 0 && !((uintptr_t)xout & 15)))) {
-    size_t wcls;
-    pack_layout(w, nullptr, nullptr, &wcls);
-    const char* e = getenv("AUDIOCAPTION_DEC_WIDE_CLS_NTB");
-    const int cls_ntb = e ? atoi(e) : (R >= 512 ? 4 : 2);   // 64-column groups per workgroup: the LayerNorm of a 32-row tile is redone once per group block
-    return ac_dec_wide_gemm(2, fin.x, w->d_model, fin.y, w->d_model, fin.ln_w, fin.ln_b, nullptr, 0, 0, nullptr, nullptr, 0.f,
-                            xout, ldxo, w->step_pk + wcls, nullptr, logit, ldl, R, w->vocab, w->d_model, 0,
-                            cls_ntb > 0 ? cls_ntb : 1, 0, (void*)s);
+  static const bool cls_gemm = !is(getenv("AUDIOCAPTION_DEC_CLS_GEMM"), "0");
+  rt.cls_ln_gemm = cls_gemm && R >= 512;
+  // 1092 column tiles: four per block keep the grid near one resident wave of blocks.  AUDIOCAPTION_DEC_CLS_NTB: development
+  static const int dev_cls_ntb = getenv("AUDIOCAPTION_DEC_CLS_NTB") ? atoi(getenv("AUDIOCAPTION_DEC_CLS_NTB")) : 4;
+  rt.cls_ntb = dev_cls_ntb;
+  // 64-column groups per workgroup of the wide classifier: the LayerNorm of a 32-row tile is redone once per group block
+  e = getenv("AUDIOCAPTION_DEC_WIDE_CLS_NTB");
+  rt.wide_cls_ntb = e ? atoi(e) : (R >= 512 ? 4 : 2);
+  if (rt.wide_cls_ntb < 1) rt.wide_cls_ntb = 1;
+  return rt;
+}
+
+// A residual join that has not run: LayerNorm(x + y) * ln_w + ln_b is produced in the prologue of the next projection
+// (the residual joins and the embedding never run alone).  x null: none pending - the next projection embeds the tokens.
+struct Join { const float *x, *y, *ln_w, *ln_b; };
+
+// What decoder_step hands to classifier_step: the LAST join (embed = LayerNorm(x + y) with the last layer's norm3) and the route
+struct StepOut { Join join; Route route; };
+
+// One decode position over R rows, as the descriptor builders read it.  `shared`: what the dec_gemm_kernel projections of a
+// step have in common, filled once (decoder_step): M, ntb, live and the embedding's tok / tok_stride / t / emb / pe / emb_scale.
+struct Step {
+  const ac_trm_weights* w; const Ws* ws;
+  const float* memkv; const int* mem_len;        // cross-attention K | V of every layer: R / row_div memory rows of Tm keys
+  float* cache; const unsigned char* mask;       // the active KV cache set; key mask [R][shared.tok_stride]
+  int R, row_div, Tm, max_len, t;
+  DecGemmParams shared;
+};
+
+// What the attentions of a route share: head geometry, where the context rows go, which rows run.  On the wide route they
+// leave as the fragment pack of the out-projection and the launch skips nothing (live stays Live(): the search clears what
+// it wrote for ended segments, search_finalize_kernel); on the others they go to ws.att (the per-row kernels keep them in
+// LDS and ignore it) and the rows of ended segments are skipped.
+void attn_output(const Step& c, bool wide, AttnParams& a) {
+  const int d = c.w->d_model;
+  a.hd = d / c.w->nhead; a.scale = 1.0f / sqrtf((float)a.hd);
+  if (wide) { a.out_pk = (unsigned char*)c.ws->attp; a.pk_kst = d / 16; }
+  else { a.out = c.ws->att; a.ldo = d; a.live = c.shared.live; }
+}
+
+// self attention of layer l: the query and the new key / value row are the thirds of ws.qkv; keys 0 .. t of the cache
+AttnParams self_attn_params(const Step& c, int l, bool wide) {
+  const long d = c.w->d_model;
+  AttnParams a{};
+  a.K = a.Kw = c.cache + (size_t)(2 * l) * c.ws->cache_set_stride;
+  a.V = a.Vw = c.cache + (size_t)(2 * l + 1) * c.ws->cache_set_stride;
+  a.row_stride = (long)c.max_len * d; a.key_stride = d; a.row_div = 1; a.nkeys = c.t + 1;
+  a.q = c.ws->qkv; a.ldq = 3 * d; a.key_mask = c.mask; a.mask_stride = c.shared.tok_stride;
+  a.new_k = c.ws->qkv + d; a.new_v = c.ws->qkv + 2 * d; a.ld_new = 3 * d;
+  attn_output(c, wide, a);
+  return a;
+}
+
+// cross attention of layer l: the query is ws.q2; the first mem_len keys of memory row r / row_div, nothing appended
+AttnParams cross_attn_params(const Step& c, int l, bool wide) {
+  const long d = c.w->d_model;
+  const float* mk = c.memkv + (size_t)l * ((size_t)(c.R / c.row_div) * c.Tm) * 2 * d;
+  AttnParams a{};
+  a.q = c.ws->q2; a.ldq = d; a.K = mk; a.V = mk + d; a.key_len = c.mem_len;
+  a.row_stride = (long)c.Tm * 2 * d; a.key_stride = 2 * d; a.row_div = c.row_div; a.nkeys = c.Tm;
+  attn_output(c, wide, a);
+  return a;
+}
+
+// dec_gemm_kernel<PRO_PLAIN>: Y[M, N] = act(X W^T + bias).  g: the fields the launches of a step share (Step::shared)
+DecGemmParams plain_proj(DecGemmParams g, const float* X, long ldx, const float* Wp, const float* bias, float* Y, long ldy,
+                         int N, int K, int relu) {
+  g.X = X; g.ldx = ldx; g.Wp = Wp; g.bias = bias; g.Y = Y; g.ldy = ldy; g.N = N; g.K = K; g.relu = relu;
+  return g;
+}
+
+// The same over rows a producer makes in the prologue (K = d_model): the pending join j (PRO_ADDLN) or the embedding of the
+// step's tokens (PRO_EMBED: from g, j is not read).  The produced rows are also stored to xout unless it is null.
+DecGemmParams produced_proj(DecGemmParams g, const Join& j, int d, float* xout, long ldxo, const float* Wp, const float* bias,
+                            float* Y, long ldy, int N, int relu) {
+  g = plain_proj(g, j.x, d, Wp, bias, Y, ldy, N, d, relu);
+  g.Y2 = j.y; g.ldy2 = d; g.ln_w = j.ln_w; g.ln_b = j.ln_b; g.xout = xout; g.ldxo = ldxo;
+  return g;
+}
+
+// The wide twin of a produced_proj launch (csrc/decoder_wide.hip) over the same descriptor: producer 2 = the join, 1 = the
+// embedding.  ntb: 64-column groups per workgroup; split_out: Y leaves as a fragment pack
+int wide_produced(const DecGemmParams& p, int producer, int ntb, int split_out, hipStream_t s) {
+  return ac_dec_wide_gemm(producer, p.X, p.ldx, p.Y2, p.ldy2, p.ln_w, p.ln_b, p.tok, p.tok_stride, p.t, p.emb, p.pe, p.emb_scale,
+                          p.xout, p.ldxo, p.Wp, p.bias, p.Y, p.ldy, p.M, p.N, p.K, p.relu, ntb, split_out, (void*)s);
+}
+
+// One per-row sub-layer (dec_row_kernel / dec_row2_kernel): xout = LayerNorm(res + out-projection of attention a), rows of d
+// floats (j.y: the kernel computes it).  The self-attention one also projects its row to the cross query: the caller names those.
+RowParams row_params(const AttnParams& a, const Join& j, const float* WoT, const float* bo, float* xout, long d) {
+  RowParams r{};
+  r.a = a; r.res = j.x; r.ldres = d; r.WoT = WoT; r.bo = bo; r.ln_w = j.ln_w; r.ln_b = j.ln_b; r.xout = xout; r.ldxo = d;
+  return r;
+}
+
+// One decoder position for R rows.  tokens/mask: [R][tok_stride]; the input token is column t.  cache: active KV cache set.
+// Returns through `fin` the operands of the LAST residual join, which the caller fuses into the classifier projection
+// (classifier_step), and the route.  `live` (struct Live): the rows of finished segments of an on-device search are skipped
+// by every kernel of the step (Live() = every row runs; the wide route's attention does not skip, see attn_output).
+//
+// One layer loop for every route (struct Route); a route only chooses the kernel behind a sub-layer:
+//   general  attn_step_kernel and dec_gemm_kernel, 8 launches per layer, any supported shape
+//   wide     the same 8 with every projection on the bf16 matrix cores in 32-row workgroups (csrc/decoder_wide.hip); rows that
+//            feed a projection without a join in front (attention contexts, feed-forward hidden rows) travel as bf16-plane
+//            fragment packs (ws.attp, ws.ffp)
+//   rows     self attention .. norm2 one row per workgroup in ONE launch (rows_split: one per attention); the feed forward
+//            reads the materialised x2: 4 launches per layer (5)
+//   hybrid   general or rows with the joined QKV projection (layer 1 on; the embedding one stays narrow) on its wide twin
+int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
+                 int max_len, int t, const int* tok, const unsigned char* mask, long tok_stride, float* cache,
+                 const Ws& ws, StepOut* fin, hipStream_t s, const Live& live) {
+  if (t >= w->max_pos || !w->step_pk) return AC_ERR_ARG;
+  const int d = w->d_model, ff = w->dim_ff;
+  const float* pk = w->step_pk;
+  const Route rt = resolve_route(w, R, Tm, t);
+  const PackOffsets po = pack_layout(w);
+  Step c{};
+  c.w = w; c.ws = &ws; c.memkv = memkv; c.mem_len = mem_len; c.cache = cache; c.mask = mask;
+  c.R = R; c.row_div = row_div; c.Tm = Tm; c.max_len = max_len; c.t = t;
+  DecGemmParams& g = c.shared;
+  g.tok = tok; g.tok_stride = tok_stride; g.t = t; g.emb = w->emb; g.pe = w->pe; g.emb_scale = sqrtf((float)d);
+  g.M = R; g.ntb = rt.ntb; g.live = live;
+  // a projection of rows a launch wrote: X[R, K] (wide: their fragment pack) -> Y[R, N]
+  auto plain = [&](const float* X, size_t wp, const float* bias, float* Y, int N, int K, int relu) {
+    if (rt.wide)
+      return ac_dec_wide_gemm(0, X, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0.f, nullptr, 0, pk + wp,
+                              bias, Y, N, R, N, K, relu, 1, 0, (void*)s);
+    return launch_dec_gemm<PRO_PLAIN>(plain_proj(g, X, K, pk + wp, bias, Y, N, N, K, relu), s);   // K beyond one chunk: the launcher takes one tile per block
+  };
+  // a projection with a producer: the join j, or with none pending the embedding; the produced rows go to xout as well.
+  // wide_twin: on the wide kernel (out & PACK_OUT: Y leaves as a fragment pack); the hybrid's carries no embedding operands
+  enum { RELU = 1, PACK_OUT = 2 };
+  DecGemmParams rows_only{}; rows_only.M = R;
+  auto produced = [&](const Join& j, bool wide_twin, float* xout, size_t wp, const float* bias, float* Y, int N, int out) {
+    const bool pack_out = out & PACK_OUT;
+    const DecGemmParams p = produced_proj(wide_twin && !rt.wide ? rows_only : g, j, d, xout, d, pk + wp, bias, Y,
+                                          pack_out ? 0 : N, N, out & RELU);
+    if (wide_twin) return wide_produced(p, j.x ? 2 : 1, 1, pack_out, s);
+    return j.x ? launch_dec_gemm<PRO_ADDLN>(p, s) : launch_dec_gemm<PRO_EMBED>(p, s);
+  };
+  auto attention = [&](const AttnParams& a) {
+    hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
+    return ac_check_launch();
+  };
+  float *xa = ws.x, *xb = ws.x2;   // residual stream, ping-pong: a join reads one and writes the other
+  // attention context rows / feed-forward hidden rows, as the route's projections read them
+  float *ctx = rt.wide ? ws.attp : ws.att, *hid = rt.wide ? ws.ffp : ws.ff;
+  Join j{};
+  for (int l = 0; l < w->nlayers; ++l) {
+    const ac_trm_layer& L = w->layer[l];
+    const PackLayout& P = po.layer[l];
+    const ProjOffsets& W = rt.wide ? P.w : P.n;
+    const AttnParams self = self_attn_params(c, l, rt.wide), cross = cross_attn_params(c, l, rt.wide);
+    const bool qkv_twin = rt.wide || (rt.hybrid && l > 0);
+    AC_TRY(produced(j, qkv_twin, xa, qkv_twin ? P.w.sa_in : P.n.sa_in, L.sa_in_b, ws.qkv, 3 * d, 0));
+    if (rt.rows) {
+      RowParams r1 = row_params(self, {xa, nullptr, L.n1_w, L.n1_b}, pk + P.sa_outT, L.sa_out_b, xb, d);    // x1 -> xb
+      r1.WqT = pk + P.ca_qT; r1.bq = L.ca_in_b; r1.qout = ws.q2; r1.ldqo = d;
+      const RowParams r2 = row_params(cross, {xb, nullptr, L.n2_w, L.n2_b}, pk + P.ca_outT, L.ca_out_b, xa, d);   // x2 -> xa
+      if (rt.rows_split) {
+        hipLaunchKernelGGL(dec_row_kernel, dim3(R), dim3(256), 0, s, r1);
+        AC_TRY(ac_check_launch());
+        hipLaunchKernelGGL(dec_row_kernel, dim3(R), dim3(256), 0, s, r2);
+      } else {
+        hipLaunchKernelGGL(dec_row2_kernel, dim3(R), dim3(256), 0, s, r1, r2);
+      }
+      AC_TRY(ac_check_launch());
+      AC_TRY(plain(xa, W.l1, L.l1_b, hid, ff, d, 1));
+    } else {
+      AC_TRY(attention(self));
+      AC_TRY(plain(ctx, W.sa_out, L.sa_out_b, ws.tmp, d, d, 0));
+      AC_TRY(produced({xa, ws.tmp, L.n1_w, L.n1_b}, rt.wide, xb, W.ca_q, L.ca_in_b, ws.q2, d, 0));   // x1 -> xb
+      AC_TRY(attention(cross));
+      AC_TRY(plain(ctx, W.ca_out, L.ca_out_b, ws.tmp, d, d, 0));
+      AC_TRY(produced({xb, ws.tmp, L.n2_w, L.n2_b}, rt.wide, xa, W.l1, L.l1_b, hid, ff, RELU | (rt.wide ? PACK_OUT : 0)));   // x2 -> xa
+    }
+    AC_TRY(plain(hid, W.l2, L.l2_b, ws.tmp, d, ff, 0));
+    // x3 = LN3(x2 + ff) is produced by the next consumer (next layer's QKV or the caller's projection)
+    j = {xa, ws.tmp, L.n3_w, L.n3_b};
+    float* tswap = xa; xa = xb; xb = tswap;  // next layer writes its input into the other buffer
   }
-  static const bool cls_gemm = !(getenv("AUDIOCAPTION_DEC_CLS_GEMM") && !strcmp(getenv("AUDIOCAPTION_DEC_CLS_GEMM"), "0"));
-  if (cls_gemm && R >= 512 && (xout || scratch) && w->cls_w) {
+  fin->join = j; fin->route = rt;
+  return AC_OK;
+}
+
+// logits[R, V] = LayerNorm(fin.join) W_cls^T, the normalised rows also stored to xout (= `embed`).  scratch: R x d_model
+// floats for the normalised rows of the LayerNorm + ac_gemm form when xout is null
+int classifier_step(const ac_trm_weights* w, const StepOut& fin, int R, float* xout, long ldxo, float* logit,
+                    long ldl, hipStream_t s, const Live& live, float* scratch = nullptr) {
+  const Route& rt = fin.route;
+  const Join& j = fin.join;
+  const int d = w->d_model;
+  const PackOffsets po = pack_layout(w);
+  DecGemmParams g{}; g.M = R;
+  if ((rt.wide || rt.hybrid) && (!xout || (ldxo % 4 == 0 && !((uintptr_t)xout & 15))))
+    return wide_produced(produced_proj(g, j, d, xout, ldxo, w->step_pk + po.wcls, nullptr, logit, ldl, w->vocab, 0), 2,
+                         rt.wide_cls_ntb, 0, s);
+  if (rt.cls_ln_gemm && (xout || scratch) && w->cls_w) {
     float* nx = xout ? xout : scratch;
-    const long ldn = xout ? ldxo : (long)w->d_model;
-    AC_TRY(launch_ln(fin.x, fin.y, fin.ln_w, fin.ln_b, nx, R, w->d_model, w->d_model, w->d_model, ldn, s, live));
-    return ac_gemm(nx, ldn, 1, w->cls_w, 1, w->d_model, logit, ldl, R, w->vocab, w->d_model, nullptr, 0, 0.f, 1, 0.f, 0,
-                   nullptr, 0, nullptr, 0, (void*)s);
+    const long ldn = xout ? ldxo : (long)d;
+    AC_TRY(launch_ln(j.x, j.y, j.ln_w, j.ln_b, nx, R, d, d, d, ldn, s, live));
+    return ac_gemm(nx, ldn, 1, w->cls_w, 1, d, logit, ldl, R, w->vocab, d, nullptr, 0, 0.f, 1, 0.f, 0, nullptr, 0, nullptr, 0,
+                   (void*)s);
   }
-  DecGemmParams g;
-  g.tok = nullptr; g.tok_stride = 0; g.t = 0; g.emb = nullptr; g.pe = nullptr; g.emb_scale = 0.f;
-  g.M = R; g.N = w->vocab; g.K = w->d_model; g.relu = 0;
-  g.live = live;
-  static const int dev_cls_ntb = getenv("AUDIOCAPTION_DEC_CLS_NTB") ? atoi(getenv("AUDIOCAPTION_DEC_CLS_NTB")) : 4;   // development
-  g.ntb = dev_cls_ntb;  // 1092 column tiles: four per block keep the grid near one resident wave of blocks
-  g.X = fin.x; g.ldx = w->d_model; g.Y2 = fin.y; g.ldy2 = w->d_model; g.ln_w = fin.ln_w; g.ln_b = fin.ln_b;
-  size_t cls_off;
-  pack_layout(w, nullptr, &cls_off);
-  g.Wp = w->step_pk + cls_off; g.bias = nullptr; g.Y = logit; g.ldy = ldl; g.xout = xout; g.ldxo = ldxo;
-  return launch_dec_gemm<PRO_ADDLN>(g, s);
+  g.ntb = rt.cls_ntb; g.live = live;
+  return launch_dec_gemm<PRO_ADDLN>(produced_proj(g, j, d, xout, ldxo, w->step_pk + po.cls, nullptr, logit, ldl, w->vocab, 0), s);
 }
 
 }  // namespace
@@ -1577,17 +1576,15 @@ extern "C" int ac_trm_memory(const ac_trm_weights* w, const float* attn_emb, int
 
 extern "C" long ac_trm_step_pack_floats(const ac_trm_weights* w) {
   if (check_weights(w) != AC_OK) return -1;
-  return (long)pack_layout(w, nullptr, nullptr);
+  return (long)pack_layout(w).total;
 }
 
 extern "C" int ac_trm_pack_step_weights(const ac_trm_weights* w, float* out, void* stream) {
   AC_TRY(check_weights(w));
-  if (!out || w->d_model % 64 || w->dim_ff % 64) return AC_ERR_ARG;
+  if (!out) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int d = w->d_model, ff = w->dim_ff;
-  PackLayout PL[AC_MAX_LAYERS];
-  size_t cls_off, wcls_off;
-  pack_layout(w, PL, &cls_off, &wcls_off);
+  const PackOffsets po = pack_layout(w);
   const bool wide = wide_shape_ok(w);
   auto wpack = [&](const float* W, int N, int K, float* dst) {
     return wide ? ac_dec_wide_pack(W, (long)K, N, K, dst, stream) : AC_OK;
@@ -1599,29 +1596,28 @@ extern "C" int ac_trm_pack_step_weights(const ac_trm_weights* w, float* out, voi
   };
   for (int l = 0; l < w->nlayers; ++l) {
     const ac_trm_layer& L = w->layer[l];
-    AC_TRY(pack(L.sa_in_w, 3 * d, d, out + PL[l].sa_in));
-    AC_TRY(pack(L.sa_out_w, d, d, out + PL[l].sa_out));
-    AC_TRY(pack(L.ca_in_w, d, d, out + PL[l].ca_q));  // rows 0..d-1 of in_proj = the query projection
-    AC_TRY(pack(L.ca_out_w, d, d, out + PL[l].ca_out));
-    AC_TRY(pack(L.l1_w, ff, d, out + PL[l].l1));
-    AC_TRY(pack(L.l2_w, d, ff, out + PL[l].l2));
-    AC_TRY(wpack(L.sa_in_w, 3 * d, d, out + PL[l].w_sa_in));
-    AC_TRY(wpack(L.sa_out_w, d, d, out + PL[l].w_sa_out));
-    AC_TRY(wpack(L.ca_in_w, d, d, out + PL[l].w_ca_q));
-    AC_TRY(wpack(L.ca_out_w, d, d, out + PL[l].w_ca_out));
-    AC_TRY(wpack(L.l1_w, ff, d, out + PL[l].w_l1));
-    AC_TRY(wpack(L.l2_w, d, ff, out + PL[l].w_l2));
-    if (d % 32 == 0) {
-      const float* src[3] = {L.sa_out_w, L.ca_in_w, L.ca_out_w};
-      const size_t dst[3] = {PL[l].sa_outT, PL[l].ca_qT, PL[l].ca_outT};
-      for (int i = 0; i < 3; ++i) {
-        hipLaunchKernelGGL(transpose_sq_kernel, dim3(d / 32, d / 32), dim3(32, 8), 0, s, src[i], (long)d, d, out + dst[i]);
-        AC_TRY(ac_check_launch());
-      }
+    const PackLayout& P = po.layer[l];
+    AC_TRY(pack(L.sa_in_w, 3 * d, d, out + P.n.sa_in));
+    AC_TRY(pack(L.sa_out_w, d, d, out + P.n.sa_out));
+    AC_TRY(pack(L.ca_in_w, d, d, out + P.n.ca_q));  // rows 0..d-1 of in_proj = the query projection
+    AC_TRY(pack(L.ca_out_w, d, d, out + P.n.ca_out));
+    AC_TRY(pack(L.l1_w, ff, d, out + P.n.l1));
+    AC_TRY(pack(L.l2_w, d, ff, out + P.n.l2));
+    AC_TRY(wpack(L.sa_in_w, 3 * d, d, out + P.w.sa_in));
+    AC_TRY(wpack(L.sa_out_w, d, d, out + P.w.sa_out));
+    AC_TRY(wpack(L.ca_in_w, d, d, out + P.w.ca_q));
+    AC_TRY(wpack(L.ca_out_w, d, d, out + P.w.ca_out));
+    AC_TRY(wpack(L.l1_w, ff, d, out + P.w.l1));
+    AC_TRY(wpack(L.l2_w, d, ff, out + P.w.l2));
+    const float* src[3] = {L.sa_out_w, L.ca_in_w, L.ca_out_w};
+    const size_t dst[3] = {P.sa_outT, P.ca_qT, P.ca_outT};
+    for (int i = 0; i < 3; ++i) {
+      hipLaunchKernelGGL(transpose_sq_kernel, dim3(d / 32, d / 32), dim3(32, 8), 0, s, src[i], (long)d, d, out + dst[i]);
+      AC_TRY(ac_check_launch());
     }
   }
-  AC_TRY(pack(w->cls_w, w->vocab, d, out + cls_off));
-  return wpack(w->cls_w, w->vocab, d, out + wcls_off);
+  AC_TRY(pack(w->cls_w, w->vocab, d, out + po.cls));
+  return wpack(w->cls_w, w->vocab, d, out + po.wcls);
 }
 
 extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int max_len) {
@@ -1752,7 +1748,7 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
   if (B <= 0 || beam <= 0 || beam > 64 || Tm <= 0 || Tm > MAX_KEYS || t < 0 || t >= max_len) return AC_ERR_ARG;
   if (max_len > w->max_pos || !(temp > 0.f)) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int R = B * beam, d = w->d_model, V = w->vocab;
+  const int R = B * beam, V = w->vocab;
   const Ws ws = carve(w, R, max_len, ws_base);
   StepOut fin;
   AC_TRY(decoder_step(w, memkv, mem_len, R, beam, Tm, max_len, t, tokens, key_mask, max_len + 1,
@@ -1770,7 +1766,6 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
     hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(64), 0, s, cand_val, cand_idx, beam, t == 0 ? 1 : beam, top_val, top_idx);
     return ac_check_launch();
   }
-  // lp is written over the qkv/ff scratch?  No: it needs R*V floats, reuse a second logits-sized area.
   float* lp = ws.lg;  // in place: every element is read before it is written by the same thread
   hipLaunchKernelGGL(beam_logprob_kernel, dim3(R), dim3(256), 0, s, ws.lg, cum_logprob, temp, lp, V);
   AC_TRY(ac_check_launch());

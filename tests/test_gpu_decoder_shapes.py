@@ -9,6 +9,9 @@ Bars: 1e-4 absolute on ``embed`` / ``logit`` / ``sampled_logprob``, the project'
 forced inputs are the same plain procedural draws (float64 logits peak at 4-9), on which the oracle's own float32
 evaluation sits 2-6e-6 from float64 (test_float32_oracle_is_well_inside_the_logit_bar).  Ids must be equal."""
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -191,6 +194,43 @@ def test_greedy_rows_that_end_early_beside_long_rows(case, monkeypatch):
         print(f"{case} {call}: tokens before <end> {facts['run_len']}, steps {want['steps']}, "
               f"max|sampled_logprob - f64| over live steps {dlp:.3e}")
         assert dlp < BAR
+
+
+def _s0_greedy_child(tmp_path, dec_row):
+    """The S0 12-step greedy of tools/decoder_route_digest.py in a process of its own (AUDIOCAPTION_DEC_ROW=split is latched
+    by a process's first decode step): (its digest line, the arrays it hashed)."""
+    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "decoder_route_digest.py")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AUDIOCAPTION_DEC_")}
+    env["AUDIOCAPTION_DECODE_GRAPH"] = "0"
+    if dec_row is not None:
+        env["AUDIOCAPTION_DEC_ROW"] = dec_row
+    dump = str(tmp_path / f"{dec_row or 'default'}.npz")
+    r = subprocess.run([sys.executable, tool, "--case", "S0-greedy", "--dump", dump], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    return r.stdout.strip().splitlines()[-1], dict(np.load(dump))
+
+
+def test_greedy_with_the_row_sublayers_as_two_launches_matches_float64(tmp_path):
+    """AUDIOCAPTION_DEC_ROW=split: dec_row_kernel once per attention sub-layer instead of one dec_row2_kernel.  Rows 0-2 and
+    steps 0-11 of the S0 greedy draw (a prefix of ``S.greedy_reference``: no row ends, rows are independent): ids equal to
+    the float64 oracle's and logits within 1e-4, for the two-launch form and, beside it, the default.  Whether the two
+    forms give the same bits is printed, not asserted (profiles/decoder_step_refactor.txt)."""
+    sid, seed, _ = S.GREEDY_CASES["S0"]
+    want = S.greedy_reference(sid, seed)[2]
+    got = {}
+    for dec_row in ("split", None):
+        line, out = _s0_greedy_child(tmp_path, dec_row)
+        got[dec_row] = out
+        rows, steps = out["seq"].shape
+        assert (rows, steps) == (3, 12)
+        dl, at = _worst(torch.from_numpy(out["logit"]).double(), want["logit"][:rows, :steps])
+        print(f"{line}\n  max|logit - f64| {dl:.3e} at (row, step, col) {at}")
+        bad = np.argwhere(out["seq"] != want["seq"][:rows, :steps].numpy())
+        assert bad.size == 0, (dec_row, "first differing (row, step)", bad[0].tolist())
+        assert dl < BAR, (dec_row, dl, at)
+    same = all(np.array_equal(got["split"][k], got[None][k]) for k in got[None])
+    print(f"two launches and one launch give {'the same bits' if same else 'different bits'}")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
