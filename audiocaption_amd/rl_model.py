@@ -10,8 +10,11 @@ current keys.  For ``mode == "train"``:
 2. rollout: ``model.train()``, ``sample_method="sample"``: the train-mode encoder and ``max_length`` decoder passes on the
    words drawn so far (``TrainEngine.rollout``); a clip that has drawn ``<end>`` keeps emitting ``<end>``;
    ``sampled_logprob[n, t] = log_softmax(logit[n, t])[w] / temp``;
-3. reward: ``score(sampled) - score(greedy)`` per clip through ``compute_batch_score`` and the CALLER's scorer
-   (``scorer.compute_score(references, hypothesis) -> (mean, per-key list)``; no scorer is built in);
+3. reward: ``score(sampled) - score(greedy)`` per clip.  With the built-in ``audiocaption_amd.Cider`` as ``scorer`` it is
+   computed on the device from the word ids, both sets read where the decoders left them (cider.py ``score_ids``,
+   csrc/cider.hip; its one upload is the batch's packed references), and feeds the loss kernel directly;
+   any other scorer object goes through ``compute_batch_score`` on the host
+   (``scorer.compute_score(references, hypothesis) -> (mean, per-key list)``) and one upload;
 4. ``mask[n, 0] = 1``, ``mask[n, t] = (seq[n, t-1] != end_idx)``; ``loss = mean_n sum_t -(sampled_logprob * reward[n] *
    mask)`` - one kernel (csrc/scst.hip ac_scst_loss), whose backward hands d(loss)/d(logit) to the training engine's
    bridge node, so ``loss.backward()`` fills ``.grad`` of every trainable parameter;
@@ -28,6 +31,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, ptr, stream
+from .cider import Cider
 from .transformer_model import CaptionMetaMixin, TransformerModel
 
 
@@ -111,21 +115,24 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
         return self.model(input_dict)
 
     def _baseline(self, input_dict, max_length):
-        """The greedy baseline: the inference path in eval mode without gradients."""
+        """The greedy baseline: the inference path in eval mode without gradients.  Returns its words as the inference
+        path hands them out (CPU, int64) and the decoder's device copy of them as int32."""
         model = self.model
         d = {k: v for k, v in input_dict.items() if k not in ("seed", "dropout_seed", "_scst_words", "_cnn_attn")}
-        d.update(mode="inference", sample_method="greedy", max_length=max_length)
+        d.update(mode="inference", sample_method="greedy", max_length=max_length, _seq_on_device=True)
         model.eval()
         with torch.no_grad():
             hook = input_dict.get("_cnn_attn")
             if hook is None:
-                return model(d)["seq"]
-            # parity hook (see TrainEngine._prepare): start downstream of the mel front-end and the Cnn14
-            from .cnn_encoder import cnn14_feat_len
-            enc = model.encoder
-            lens = cnn14_feat_len(input_dict["wav_len"], enc.cnn.hop_length, enc.cnn.downsample_ratio)
-            back = enc.rnn if hasattr(enc, "rnn") else enc.trm
-            return model.forward_decoder(d, back({"attn": hook, "attn_len": lens}))["seq"]
+                res = model(d)
+            else:
+                # parity hook (see TrainEngine._prepare): start downstream of the mel front-end and the Cnn14
+                from .cnn_encoder import cnn14_feat_len
+                enc = model.encoder
+                lens = cnn14_feat_len(input_dict["wav_len"], enc.cnn.hop_length, enc.cnn.downsample_ratio)
+                back = enc.rnn if hasattr(enc, "rnn") else enc.trm
+                res = model.forward_decoder(d, back({"attn": hook, "attn_len": lens}))
+            return res["seq"], res["seq_dev"].to(torch.int32)      # (a copy: the decoder reuses its buffer)
 
     def scst(self, input_dict):
         from .train import TrainEngine, _TrainBridge
@@ -145,9 +152,22 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
             engine = model._train_engine = TrainEngine(model)     # (raises for an encoder the engine is not built for)
         keys = list(input_dict["keys"])
 
-        greedy = self._baseline(input_dict, max_length)
+        greedy, greedy_i32 = self._baseline(input_dict, max_length)
         model.train()
         out = engine.rollout(dict(input_dict, max_length=max_length, temp=temp))
+
+        if isinstance(input_dict["scorer"], Cider):
+            # the built-in scorer reads both sets of words where they are, on the device; the packed references of the
+            # batch are its one upload.  Reward and loss are launched back to back, the downloads follow.
+            res = input_dict["scorer"].score_ids(input_dict["key2refs"], input_dict["vocabulary"], model.vocab_size, keys,
+                                                 (out["seq_i32"], greedy_i32), model.start_idx, model.end_idx)
+            logit = out["logit"]
+            if torch.is_grad_enabled():
+                logit = _TrainBridge.apply(engine, logit, *engine.flat.params)
+            loss = scst_loss(logit, out["seq_i32"], res["reward"], temp, model.end_idx)
+            return {"greedy_seqs": torch.as_tensor(greedy).cpu(), "sampled_seqs": out["seq"].cpu(),
+                    "reward": res["reward"].cpu().double(), "score": res["scores"][0].cpu().double(), "loss": loss}
+
         sampled = out["seq"].cpu()
         greedy = torch.as_tensor(greedy).cpu()
 

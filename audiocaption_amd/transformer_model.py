@@ -132,6 +132,8 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             forward_dict["n_best_size"] = input_dict.get("n_best_size", forward_dict["beam_size"])
         if input_dict.get("seed") is not None:    # sampling: the caller's 64-bit seed (otherwise drawn per call)
             forward_dict["seed"] = input_dict["seed"]
+        if input_dict.get("_seq_on_device"):      # ScstWrapper's baseline: the device copy of the words as well ("seq_dev")
+            forward_dict["_seq_on_device"] = True
         forward_dict.update(encoder_output_dict)
         return forward_dict
 
@@ -546,13 +548,16 @@ class TransformerModel(CaptionModel):
             warnings.warn("one-launch greedy search: a workgroup's partners never started (another process on the GPU?); "
                           "decoding this batch with the launch chain")
             res = self.decoder.greedy(*args, mode="chain")
-        return {
+        out = {
             "seq": res["seq"].cpu(),                          # the reference keeps seq on the CPU (base.py:122)
             "logit": res["logit"],
             "sampled_logprob": res["sampled_logprob"].cpu(),  # CPU as in base.py:126
             "embed": res["embed"],
             "unfinished_cnt": res["unfinished_cnt"],
         }
+        if input_dict.get("_seq_on_device"):
+            out["seq_dev"] = res["seq"]                       # the decoder's own buffer: valid until its next search
+        return out
 
     # ---- sampling (base.py:152-170 + sample_next_word :214-252) -----------------------------------------
     def sample_search(self, input_dict):

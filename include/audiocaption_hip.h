@@ -601,6 +601,35 @@ int ac_scst_pick(const float* logit, long ld, int N, int V, float temp, const ui
  * (softmax(logit[n][t]) - onehot(seq[n][t])), exactly 0 on masked rows.  V <= 16384, temp > 0 (AC_ERR_ARG otherwise). */
 int ac_scst_loss(const float* logit, const int* seq, long seq_ld, const float* reward, float temp, int end_idx, int N, int T,
                  int V, float* row_loss, float* loss, float* dlogit, const float* gscale_dev, void* stream);
+/* ---- CIDEr-D on token ids (csrc/cider.hip): the SCST reward without a trip through the host -----------------------
+ * The metric as pycocoevalcap's cider_scorer.py computes it (n-grams of 1 .. order words, order = 4 and sigma = 6 there;
+ * document frequencies counted over the keys of THIS call's references, hypotheses not counted):
+ *   df[g] = keys with g in at least one reference;  idf[g] = log(keys) - log(max(1, df[g]));
+ *   vec[n][g] = tf(g) * idf[g] per sentence, norm[n] = |vec[n]|, length = max(words - 1, 0);
+ *   val[n] = sum over g in h of min(vec_h[n][g], vec_r[n][g]) * vec_r[n][g], divided by norm_h[n] * norm_r[n] when both
+ *   are non-zero (and held to <= 1, its bound in exact arithmetic), times exp(-(length_h - length_r)^2 / (2 sigma^2));
+ *   score of a key = 10 * mean_n(sum over its references of val[n]) / references.
+ * hyp: HOST array of `sets` (<= AC_CIDER_MAX_SETS) device pointers, each int32 [N][hyp_ld], T <= AC_CIDER_MAX_HYP_WORDS
+ * words per row.  The sentence of a row (model_util.py:117-164): start_idx skipped, cut at the first end_idx, each word w
+ * (0 <= w < vocab_size, else the scores are NaN - never a read) replaced by canon[w], the first id that spells the same
+ * word.  Rows of one key are scored once, on row first_row[key] (keys distinct keys, row_key [N] the key of each row).
+ * References: ref_words [total_words] canonical ids below n_words (vocab_size + the words outside the vocabulary),
+ * sentence s = ref_words[sent_off[s] .. sent_off[s + 1]) with at most max_ref_words <= AC_CIDER_MAX_REF_WORDS words
+ * (the caller's maximum over sent_off, checked here before anything is launched; a longer sentence found on the device
+ * turns every score into NaN instead), key k owns sentences key_off[k] .. key_off[k + 1], at least one.  All of them in
+ * device memory.  workspace: 256-byte aligned, the number of bytes the workspace query returns for the same sizes.
+ * scores f32 [sets][N]; reward (optional, sets >= 2) f32 [N] = scores[0] - scores[1].  Integer document frequencies
+ * through a table that stores whole n-grams (by the position of one occurrence) and compares them; every float sum has a
+ * fixed order: a call is bitwise repeatable.  AC_ERR_ARG beyond any limit, nothing launched. */
+#define AC_CIDER_MAX_SETS 4
+#define AC_CIDER_MAX_HYP_WORDS 1024
+#define AC_CIDER_MAX_REF_WORDS 1024
+long ac_cider_workspace_bytes(long ref_words, int sentences, int keys, int sets);
+int ac_cider_scores(const int* const* hyp, int sets, long hyp_ld, int N, int T, int start_idx, int end_idx,
+                    const int* canon, int vocab_size, int n_words, const int* ref_words, long total_words,
+                    const int* sent_off, int sentences, int max_ref_words, const int* key_off, int keys,
+                    const int* row_key, const int* first_row, int order, float sigma, void* workspace,
+                    long workspace_bytes, float* scores, float* reward, void* stream);
 /* ac_gru_layer that also keeps (r, z, n, W_hn h + b_hn) per (clip, step, direction): save [B][T][2][4H]. */
 int ac_gru_layer_train(const float* gx, const float* whhT, const float* bhh, const int* lens, float* out, float* save,
                        int B, int T, int hidden, void* stream);

@@ -88,7 +88,7 @@ parts = {"baseline": 0.0, "rollout": 0.0, "reward": 0.0, "backward+update": 0.0}
 for _ in range(args.steps):
     opt.zero_grad()
     t0 = sync()
-    greedy = wrapper._baseline(batch, T).cpu()
+    greedy = wrapper._baseline(batch, T)[0].cpu()
     t1 = sync()
     model.train()
     ro = eng.rollout(batch)
