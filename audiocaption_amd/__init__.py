@@ -10,6 +10,7 @@ from .transformer_model import CaptionModel, TransformerModel
 from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
 from .cider import Cider
+from .kd_loss import SupKdLoss, TokenLevelKdLoss
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
-           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "Cider", "init_model_from_config", "cnn14rnn_trm_config"]
+           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "Cider", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]

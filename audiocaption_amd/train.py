@@ -551,9 +551,13 @@ class TrainEngine:
     def _prepare(self, input_dict, rollout=False):
         model = self.model
         enc, dec = model.encoder, model.decoder
-        if not model.training:
-            raise RuntimeError("TrainEngine needs model.train() (run.py:79)")
-        specaug = bool(input_dict.get("specaug", False)) and enc.cnn.training
+        # A model in eval() (a distillation teacher, run_kd.py:42,133; a teacher-forced validation loss) runs the same
+        # kernels with every dropout probability 0 and SpecAugment off; scheduled sampling is honoured as in train mode
+        # (transformer_model.py:44 looks at input_dict["mode"], not at the module's flag).  Nothing is kept for a backward.
+        evalm = not model.training
+        if evalm and rollout:
+            raise RuntimeError("TrainEngine.rollout needs model.train() (rl_model.py:35)")
+        specaug = bool(input_dict.get("specaug", False)) and enc.cnn.training and not evalm
         wav = input_dict["wav"]
         dev = wav.device
         if not wav.is_cuda:
@@ -569,7 +573,7 @@ class TrainEngine:
             Tq = enc.cnn.geometry(wav.shape[1])[1][5]
         else:
             Tq = hook.shape[1]
-        p_dec = float(dec.in_dropout.p)
+        p_dec = 0.0 if evalm else float(dec.in_dropout.p)
         trm = self.enc_kind == "trm"
         if trm:
             if Tq + 1 > ENC_LMAX:
@@ -579,14 +583,18 @@ class TrainEngine:
             p_rnn = (float(enc.trm.attn_proj[2].p),) + tuple(
                 (float(ly.self_attn.dropout), float(ly.dropout1.p), float(ly.dropout.p), float(ly.dropout2.p))
                 for ly in enc.trm.model.layers)
+            if evalm:
+                p_rnn = (0.0,) + ((0.0, 0.0, 0.0, 0.0),) * len(enc.trm.model.layers)
         else:
-            p_rnn = float(enc.rnn.network.dropout)
-        p_cnn = 0.2 if enc.cnn.training else 0.0
+            p_rnn = 0.0 if evalm else float(enc.rnn.network.dropout)
+        p_cnn = 0.2 if enc.cnn.training and not evalm else 0.0
         Tm = Tq + 1 if trm else Tq      # decoder memory rows per clip (the Transformer encoder prepends cls_token)
         key = (dev, N, Tc, tuple(wav.shape) if hook is None else ("hook", Tq), teacher_forcing, p_dec, p_rnn, p_cnn,
                model.start_idx, model.pad_idx, specaug and hook is None)
         if rollout:
             key += ("rollout",)     # the SCST rollout's states never collide with the cross-entropy step's of the same shape
+        if evalm:
+            key += ("eval",)        # nor an eval-mode forward's with a train-mode one's whose dropout happens to be 0
         st = self._states.get(key)
         if st is None:
             lay = self._layout(N, T, Tm, teacher_forcing, dev)
@@ -594,7 +602,7 @@ class TrainEngine:
             if self._wsg is None or self._wsg.device != dev:
                 self._wsg = _Ws(dev)
             st = {"key": key, "ws": self._wsg, "lay": lay, "N": N, "T": T, "Tc": Tc, "Tq": Tq, "Tm": Tm,
-                  "teacher_forcing": teacher_forcing,
+                  "teacher_forcing": teacher_forcing, "eval": evalm,
                   "p_dec": p_dec, "p_rnn": p_rnn, "p_cnn": p_cnn, "graphs": {}, "steps": 0,
                   "wav": torch.empty_like(wav, dtype=torch.float32) if hook is None else None,
                   "cnn_attn_in": torch.empty(N, Tq, 2048, device=dev) if hook is not None else None,
@@ -932,10 +940,11 @@ class TrainEngine:
 
     def forward(self, input_dict):
         """The reference's ``model(input_dict)`` for mode "train": returns ``logit`` (N, T, V) [+ ``seq``] as fresh
-        device tensors and keeps what the backward needs."""
+        device tensors and keeps what the backward needs.  On a model in ``eval()`` - a frozen teacher, a validation loss -
+        the same kernels run with every dropout probability 0 and SpecAugment off, and nothing is kept."""
         st = self._prepare(input_dict)
         self._launch_forward(st)
-        self._saved = st
+        self._saved = None if st["eval"] else st      # a model in eval(): no backward state (``backward`` raises)
         out = self._outputs(st)
         out["logit"] = out["logit"].clone()
         if "seq" in out:
@@ -1172,11 +1181,13 @@ class TrainEngine:
         side.join()
 
     # ---- fast path: forward + loss + backward (+ gradient all-reduce) + clip + Adam -----------------------
-    def _launch_part(self, st, smoothing, part):
+    def _launch_part(self, st, smoothing, part, kd=None):
         """One capturable piece of an iteration:
         "fwd0"       frozen Cnn14, GRU, audio memory and EVERY decoder pass teacher forced as one batch;
         ("pass", t)  free-running pass t re-run on the model's own predictions (only the passes the draws made so);
         "tail"       label-smoothing loss (mean over the valid target tokens, counted on the device) + the whole backward;
+                     with ``kd`` = (temp, sup_weight) the distillation loss ac_kd_loss against the teacher logits that
+                     ``step`` copied into the workspace buffer "tchr_logit", in its place;
         "tail_head" / "gru"   the same in two halves (see ``_launch_backward``) when gradients are all-reduced."""
         self._seed_ptr = st["small"].data_ptr()
         if part == "fwd0":
@@ -1191,9 +1202,14 @@ class TrainEngine:
         dlogit = ws.f("dlogit", N * T, V)
         row_loss, loss = ws.f("row_loss", N * T), ws.f("loss", 1)
         tgt_len = st["small"].data_ptr() + 4 * (2 + N)
-        check(self.lib.ac_label_smoothing_loss(logit, st["cap"].data_ptr() + 8, Tc, tgt_len, N, T, V, float(smoothing), 0.0,
-                                               row_loss, loss, dlogit, 0.0, None, _lib.stream()),
-              "ac_label_smoothing_loss")
+        if kd is None:
+            check(self.lib.ac_label_smoothing_loss(logit, st["cap"].data_ptr() + 8, Tc, tgt_len, N, T, V, float(smoothing),
+                                                   0.0, row_loss, loss, dlogit, 0.0, None, _lib.stream()),
+                  "ac_label_smoothing_loss")
+        else:
+            check(self.lib.ac_kd_loss(logit, ws.f("tchr_logit", N * T, V), st["cap"].data_ptr() + 8, Tc, tgt_len, N, T, V,
+                                      float(smoothing), kd[0], kd[1], 0.0, row_loss, ws.f("row_kd", N * T), ws.f("kd_loss", 3),
+                                      dlogit, 0.0, None, _lib.stream()), "ac_kd_loss")
         self._launch_backward(st, dlogit, "all" if part == "tail" else "head")
 
     # ---- frozen Cnn14 one iteration ahead ---------------------------------------------------------------------------
@@ -1249,7 +1265,7 @@ class TrainEngine:
                 bool(cnn.training), int(seed))
 
     def step(self, input_dict, optimizer, smoothing=0.1, max_grad_norm=1.0, process_group=None, use_graph=True,
-             next_batch=None):
+             next_batch=None, kd=None):
         """One training iteration (run.py:106-126) without leaving the HIP path; returns the loss as a device scalar.
 
         The launches of an iteration are latency-bound at the reference's batch sizes, so for each batch shape they are
@@ -1260,10 +1276,25 @@ class TrainEngine:
         loss + backward.  Gradients land in the flat buffer (= the parameters' ``.grad``); with ``torch.distributed``
         initialised they are summed over the ranks by two all-reduces (the decoder's slice under the GRU backward, then
         the GRU's) and the division by the world size is folded into the clip coefficient; clip + Adam are three launches
-        on the flat buffers."""
+        on the flat buffers.
+
+        ``kd`` = {"tchr_logit": (N, T, V) f32 device tensor, "temp": float, "sup_weight": float}: token-level distillation
+        (run_kd.py with kd_type "token", kd_loss.py:36-49) - the loss of the step becomes ``sup_weight`` x label smoothing +
+        (1 - ``sup_weight``) x the cross entropy against ``softmax(tchr_logit / temp)`` (``ac_kd_loss`` in the place of
+        ``ac_label_smoothing_loss``; everything else is unchanged).  The teacher logits are per-iteration data like the
+        captions: copied into a static buffer; ``temp`` and ``sup_weight`` are part of the graph key.  The result then
+        carries ``sup_loss`` and ``kd_loss`` beside ``loss`` (the total)."""
+        import math
         from .optim import FusedAdam, clip_grad_norm_
         if "cap_len" not in input_dict:
             raise KeyError("cap_len")
+        if not self.model.training:
+            raise RuntimeError("TrainEngine.step needs model.train() (run.py:79); a model in eval() only runs forward()")
+        kdkey = None
+        if kd is not None:
+            kdkey = (float(kd.get("temp", 1.0)), float(kd.get("sup_weight", 0.5)))
+            if not (math.isfinite(kdkey[0]) and kdkey[0] > 0 and 0.0 <= kdkey[1] <= 1.0):
+                raise ValueError(f"step(kd=...): temp must be finite and > 0, sup_weight in [0, 1]; got {kdkey}")
         # ``next_batch``: the batch of the FOLLOWING iteration - its frozen Cnn14 forward is launched on a side stream under
         # this iteration's GRU / decoder work (``prefetch_cnn``).  The convolutions share one set of activation buffers, so
         # with a look-ahead in play this iteration's own Cnn14 forward goes through the side stream as well.
@@ -1279,6 +1310,18 @@ class TrainEngine:
             torch.cuda.current_stream(input_dict["wav"].device).wait_event(pf["event"])
             input_dict = dict(input_dict, _cnn_attn=pf["attn"], dropout_seed=want)
         st = self._prepare(input_dict)
+        if kd is not None:
+            # the teacher's logits of THIS batch into their static buffer (allocated here, never inside a capture)
+            tl = kd["tchr_logit"]
+            N_, T_, V_ = st["N"], st["T"], self.model.decoder.vocab_size
+            if not tl.is_cuda:
+                raise _lib.HipLibraryError("step(kd=...): tchr_logit must be on the ROCm device; there is no CPU fallback")
+            if tuple(tl.shape) != (N_, T_, V_):
+                raise ValueError(f"step(kd=...): tchr_logit {tuple(tl.shape)}, expected {(N_, T_, V_)}")
+            st["ws"].f("tchr_logit", N_ * T_, V_)
+            st["ws"].f("row_kd", N_ * T_)
+            st["ws"].f("kd_loss", 3)
+            st["ws"].tensor("tchr_logit")[:N_ * T_ * V_].view(N_, T_, V_).copy_(tl.detach(), non_blocking=True)
         if next_batch is not None:
             # the next iteration's own seed if it carries one, else the one it will draw by default
             self.prefetch_cnn(next_batch, int(next_batch.get("dropout_seed", self.seed)))
@@ -1294,7 +1337,7 @@ class TrainEngine:
         works = []
         for part in parts:
             if eager:
-                self._launch_part(st, smoothing, part)
+                self._launch_part(st, smoothing, part, kdkey)
             else:
                 # A captured graph holds RAW ADDRESSES: the flat parameter storage, the shared workspace, and - through
                 # the frozen Cnn14 - its packed weights and its activation buffers, which are shared by all batch shapes
@@ -1309,18 +1352,21 @@ class TrainEngine:
                     # unless the Cnn14's own tensors changed)
                     cnn._pack(st["cap"].device, cnn_algo)
                 ident, refs = cnn.capture_token(cnn_algo) if cnn_algo is not None else (None, None)
-                gkey = (smoothing, _lib.param_generation_flat(self), st["ws"].gen, ident, world > 1)
+                # (distillation - on or off, temp, sup_weight - is baked into the part that holds the loss launch only)
+                pkd = kdkey if part in ("tail", "tail_head") else None
+                base = (smoothing, _lib.param_generation_flat(self), st["ws"].gen, ident, world > 1)
+                gkey = base + (pkd,)
                 hit = graphs.get(part)
                 if hit is None or hit[1] != gkey:
-                    if part != "fwd0" and (graphs.get("fwd0") is None or graphs["fwd0"][1] != gkey):
+                    if part != "fwd0" and (graphs.get("fwd0") is None or graphs["fwd0"][1][:5] != base):
                         raise RuntimeError("TrainEngine: graph parts out of order")   # fwd0 refreshes the shared context
                     torch.cuda.synchronize(st["cap"].device)
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
-                        self._launch_part(st, smoothing, part)
+                        self._launch_part(st, smoothing, part, pkd)
                     ident, refs = cnn.capture_token(cnn_algo) if cnn_algo is not None else (None, None)
                     hit = graphs[part] = (graph, (smoothing, _lib.param_generation_flat(self), st["ws"].gen, ident,
-                                                  world > 1), refs)
+                                                  world > 1, pkd), refs)
                 hit[0].replay()
             if world > 1 and part in ("tail_head", "gru"):
                 o = self.flat.decoder_offset
@@ -1365,8 +1411,12 @@ class TrainEngine:
                 optimizer.step()
                 _lib.bump_param_generation(self.flat.params)
         out = self._outputs(st)
-        return {"loss": st["ws"].tensor("loss")[0], "total_norm": clip.total_norm, "logit": out["logit"],
-                "seq": out.get("seq"), "skipped_updates": self._skipped[0]}
+        res = {"loss": st["ws"].tensor("loss")[0], "total_norm": clip.total_norm, "logit": out["logit"],
+               "seq": out.get("seq"), "skipped_updates": self._skipped[0]}
+        if kd is not None:
+            kl = st["ws"].tensor("kd_loss")
+            res.update(loss=kl[0], sup_loss=kl[1], kd_loss=kl[2])
+        return res
 
     def _gru_error_word(self, st):
         """The split-GRU kernel's sticky error word of this engine's workspace as a 1-element int32 device view, or None."""
@@ -1420,6 +1470,7 @@ def train_forward(model, input_dict):
     if engine is None:
         engine = model._train_engine = TrainEngine(model)
     out = engine.forward(input_dict)
-    if torch.is_grad_enabled():
+    # a model in eval() (a distillation teacher, a validation loss): plain logits, no bridge node, nothing to back-propagate
+    if model.training and torch.is_grad_enabled():
         out["logit"] = _TrainBridge.apply(engine, out["logit"], *engine.flat.params)
     return out

@@ -601,6 +601,21 @@ int ac_scst_pick(const float* logit, long ld, int N, int V, float temp, const ui
  * (softmax(logit[n][t]) - onehot(seq[n][t])), exactly 0 on masked rows.  V <= 16384, temp > 0 (AC_ERR_ARG otherwise). */
 int ac_scst_loss(const float* logit, const int* seq, long seq_ld, const float* reward, float temp, int end_idx, int N, int T,
                  int V, float* row_loss, float* loss, float* dlogit, const float* gscale_dev, void* stream);
+/* ---- token-level knowledge distillation (kd_loss.py:8-49; csrc/kd.hip) ------------------------------
+ * ac_kd_loss: SupKdLoss(LabelSmoothingLoss(smoothing), TokenLevelKdLoss(temp, "kl"), sup_weight) in one pass per row.
+ * logit / tchr_logit [N][T][V] (student / frozen teacher), tgt int64 [N][tgt_ld], tgt_len int32 [N].  On a valid row
+ * (t < tgt_len[n]) row_sup[n*T + t] is ac_label_smoothing_loss' row term and row_kd[n*T + t] =
+ * -sum_v softmax(tchr / temp)_v * log_softmax(logit / temp)_v (not scaled by temp^2, as the reference); a masked row gets
+ * 0 in both and neither logit row is read there (NaN at a teacher's padded positions stays out).
+ * loss[1] = inv_count * sum(row_sup), loss[2] = inv_count * sum(row_kd), loss[0] = sup_weight * loss[1] +
+ * (1 - sup_weight) * loss[2].  dlogit (optional) = gscale [* gscale_dev[0]] * [sup_weight * (softmax(logit) - q) +
+ * (1 - sup_weight) * (softmax(logit / temp) - softmax(tchr / temp)) / temp] on valid rows, exactly 0 elsewhere; with
+ * sup_weight == 1 the teacher's values do not enter it.  inv_count <= 0 / gscale <= 0: "1 / sum_n min(tgt_len[n], T)" on
+ * the device, as in ac_label_smoothing_loss.  2 <= V <= 16384, temp finite and > 0, 0 <= sup_weight <= 1 (AC_ERR_ARG
+ * otherwise). */
+int ac_kd_loss(const float* logit, const float* tchr_logit, const long long* tgt, long tgt_ld, const int* tgt_len, int N,
+               int T, int V, float smoothing, float temp, float sup_weight, float inv_count, float* row_sup, float* row_kd,
+               float* loss, float* dlogit, float gscale, const float* gscale_dev, void* stream);
 /* ---- CIDEr-D on token ids (csrc/cider.hip): the SCST reward without a trip through the host -----------------------
  * The metric as pycocoevalcap's cider_scorer.py computes it (n-grams of 1 .. order words, order = 4 and sigma = 6 there;
  * document frequencies counted over the keys of THIS call's references, hypotheses not counted):
