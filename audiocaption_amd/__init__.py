@@ -10,7 +10,8 @@ from .transformer_model import CaptionModel, TransformerModel
 from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
 from .cider import Cider
+from .caption_metrics import Bleu, Rouge
 from .kd_loss import SupKdLoss, TokenLevelKdLoss
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
-           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "Cider", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]
+           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]

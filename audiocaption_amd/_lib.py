@@ -127,6 +127,12 @@ SIGNATURES = {
     "ac_cider_workspace_bytes": (_L, [_L, _I, _I, _I]),
     "ac_cider_scores": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _I, _I, _P, _L, _P, _I, _I, _P, _I, _P, _P, _I, _F, _P, _L, _P,
                              _P, _P]),
+    # BLEU and ROUGE-L on token ids (csrc/capmetrics.hip)
+    "ac_capmetrics_workspace_bytes": (_L, [_I, _I]),
+    "ac_bleu_scores": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _I, _P, _I, _P, _P, _I, _P, _L, _P, _P, _P,
+                            _P]),
+    "ac_rouge_l_scores": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _I, _P, _I, _P, _P, _P, _L, _P, _P, _P,
+                               _P]),
     "ac_gru_layer_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_gru_layer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_swa_update": (_I, [_P, _P, _L, _I, _P]),

@@ -62,7 +62,7 @@ class PackedBatch:
     ``sent_off`` (M + 1), ``key_off`` (K + 1, first sentence of each distinct key, keys in order of first appearance),
     ``row_key`` (N, the distinct-key index of each row), ``first_row`` (K), and ``n_words``: ids are below it."""
 
-    def __init__(self, keys, refs_of_key, n_words):
+    def __init__(self, keys, refs_of_key, n_words, who="Cider"):
         index, order, first_row = {}, [], []
         row_key = np.empty(len(keys), dtype=np.int32)
         for row, key in enumerate(keys):
@@ -76,7 +76,7 @@ class PackedBatch:
         for key in order:
             refs = refs_of_key(key)
             if len(refs) == 0:
-                raise ValueError(f"Cider: key {key!r} has no reference sentence")
+                raise ValueError(f"{who}: key {key!r} has no reference sentence")
             sentences.extend(refs)
             key_off.append(len(sentences))
         lens = np.fromiter((len(s) for s in sentences), dtype=np.int64, count=len(sentences))
@@ -93,19 +93,11 @@ class PackedBatch:
         return int(np.diff(self.sent_off).max(initial=0))
 
 
-class Cider:
-
-    def __init__(self, n=4, sigma=6.0):
-        if not 1 <= int(n) <= 4:
-            raise ValueError("Cider: n-grams of 1 to 4 words are built in")
-        if not sigma > 0:
-            raise ValueError("Cider: sigma must be > 0")
-        self._n, self._sigma = int(n), float(sigma)
-        self._workspace = None
-        self.clear_cache()
-
-    def method(self):
-        return "CIDEr"
+class PackedScorer:
+    """What the built-in scorers share (``Cider`` here, ``Bleu`` and ``Rouge`` of caption_metrics.py): the canonical-id
+    table and the per-key cache of packed references behind ``pack_ids``, the checks and the one upload in front of a
+    kernel call, and the numbering of the string route.  ``_who`` names the scorer in its refusals."""
+    _who = "Cider"
 
     def clear_cache(self):
         self._vocab = None        # (vocabulary, vocab_size, word2id, canon, {device: canon on it})
@@ -113,88 +105,6 @@ class Cider:
         self._refs = (None, {})   # (key2refs, {key: [ids of each reference]})
         self.packed_keys = 0      # keys packed since the last clear (a key is packed once per key2refs)
 
-    # ---- the kernels ---------------------------------------------------------------------------------------------
-    def score_packed(self, batch, words, start_idx, end_idx, canon, vocab_size):
-        """Scores (S, N) f32 and reward (N,) f32 (None for S == 1) on the device of ``canon`` for the hypothesis sets
-        ``words`` (S tensors N x T of word ids) against the references of ``batch``.  Everything is checked before the
-        first launch: what the host can see raises ValueError here, and the entry point checks its limits again."""
-        lib = _lib.load()
-        dev = canon.device
-        N = batch.row_key.shape[0]
-        if not 1 <= len(words) <= MAX_SETS:
-            raise ValueError(f"Cider: 1 to {MAX_SETS} hypothesis sets, got {len(words)}")
-        if batch.max_ref_words > MAX_REF_WORDS:
-            raise ValueError(f"Cider: a reference sentence of {batch.max_ref_words} words; the kernels take {MAX_REF_WORDS}")
-        if batch.words.size and (int(batch.words.min()) < 0 or int(batch.words.max()) >= batch.n_words):
-            raise ValueError(f"Cider: a reference word id outside [0, {batch.n_words}) (vocabulary {vocab_size} + "
-                             f"{batch.n_words - vocab_size} words outside it)")
-        sets = []
-        for w in words:
-            w = torch.as_tensor(w)
-            if w.dim() != 2 or w.shape[0] != N:
-                raise ValueError(f"Cider: hypothesis words must be ({N} rows, length), got {tuple(w.shape)}")
-            if w.shape[1] > MAX_HYP_WORDS:
-                raise ValueError(f"Cider: hypotheses of {w.shape[1]} words; the kernels take {MAX_HYP_WORDS}")
-            if not w.is_cuda:      # a host copy can be checked; on the device the kernel answers a bad id with NaN
-                ok = ((w >= 0) & (w < vocab_size)) | (w == start_idx) | (w == end_idx)
-                if not bool(ok.all()):
-                    raise ValueError(f"Cider: a hypothesis word id outside [0, {vocab_size})")
-            sets.append(w.to(device=dev, dtype=torch.int32))
-        T = sets[0].shape[1]
-        if any(w.shape[1] != T for w in sets):
-            raise ValueError("Cider: the hypothesis sets must have one length")
-        if any(w.stride(1) != 1 or w.stride(0) != sets[0].stride(0) for w in sets) or T == 0:
-            sets = [w.contiguous() for w in sets]
-        S, K, M, W = len(sets), batch.first_row.shape[0], batch.sent_off.shape[0] - 1, batch.words.shape[0]
-        host = np.concatenate((batch.words, batch.sent_off, batch.key_off, batch.row_key, batch.first_row))
-        ints = torch.from_numpy(host).to(dev)          # the one upload
-        base = ints.data_ptr()
-        at = np.cumsum([0, W, M + 1, K + 1, N])
-        p_words, p_sent, p_key, p_row, p_first = (ctypes.c_void_p(base + 4 * int(o)) for o in at)
-        need = lib.ac_cider_workspace_bytes(W, M, K, S)
-        if need < 0:
-            raise _lib.HipLibraryError(f"ac_cider_workspace_bytes refused ({W} words, {M} sentences, {K} keys, {S} sets)")
-        if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-        workspace = self._workspace
-        scores = torch.empty(S, N, device=dev, dtype=torch.float32)
-        reward = torch.empty(N, device=dev, dtype=torch.float32) if S >= 2 else None
-        hyp = (ctypes.c_void_p * S)(*[w.data_ptr() for w in sets])
-        check(lib.ac_cider_scores(ctypes.cast(hyp, ctypes.c_void_p), S, sets[0].stride(0), N, T, int(start_idx), int(end_idx),
-                                  ptr(canon), int(vocab_size), batch.n_words, p_words, W, p_sent, M, batch.max_ref_words,
-                                  p_key, K, p_row, p_first, self._n, self._sigma, ptr(workspace), workspace.numel(),
-                                  ptr(scores), ptr(reward), stream()), "ac_cider_scores")
-        return scores, reward
-
-    # ---- strings (pycocoevalcap's contract) ------------------------------------------------------------------------
-    def compute_score(self, references, hypothesis):
-        keys = list(references.keys())
-        if not keys:
-            raise ValueError("Cider.compute_score: no references")
-        if set(keys) != set(hypothesis.keys()):
-            raise ValueError("Cider.compute_score: references and hypothesis must have the same keys")
-        end_idx, start_idx, first_word = 0, 1, 2
-        table = {}
-
-        def ids(sentence):
-            return np.asarray([table.setdefault(w, first_word + len(table)) for w in sentence.split()], dtype=np.int32)
-
-        hyps = []
-        for key in keys:
-            if len(hypothesis[key]) != 1:
-                raise ValueError(f"Cider.compute_score: one hypothesis per key, {key!r} has {len(hypothesis[key])}")
-            hyps.append(ids(hypothesis[key][0]))
-        batch = PackedBatch(keys, lambda key: [ids(s) for s in references[key]], 0)
-        batch.n_words = vocab_size = first_word + len(table)
-        rows = np.full((len(keys), max(1, max(len(h) for h in hyps))), end_idx, dtype=np.int32)
-        for row, h in zip(rows, hyps):
-            row[:len(h)] = h
-        canon = torch.arange(vocab_size, device="cuda", dtype=torch.int32)
-        scores, _ = self.score_packed(batch, [torch.from_numpy(rows)], start_idx, end_idx, canon, vocab_size)
-        scores = scores[0].cpu().numpy().astype(np.float64)
-        return float(scores.mean()), scores
-
-    # ---- word ids (self-critical sequence training) ------------------------------------------------------------------
     def pack_ids(self, key2refs, vocabulary, vocab_size, keys):
         """The PackedBatch of ``keys`` (one per row) under ``vocabulary`` and the canonical-id table (host)."""
         vocab_size = int(vocab_size)
@@ -212,22 +122,147 @@ class Cider:
                 self.packed_keys += 1
             return hit
 
-        batch = PackedBatch(list(keys), refs_of_key, 0)
+        batch = PackedBatch(list(keys), refs_of_key, 0, self._who)
         batch.n_words = vocab_size + len(self._oov)
         return batch, self._vocab[3]
 
-    def score_ids(self, key2refs, vocabulary, vocab_size, keys, words, start_idx, end_idx):
-        """``{"scores": (S, N) f32, "reward": (N,) f32 = scores[0] - scores[1] (None for S == 1)}`` on the device, for the
-        S hypothesis sets ``words`` (N x T word ids each; N = len(keys))."""
+    def _pack_for_ids(self, key2refs, vocabulary, vocab_size, keys, words):
+        """``(batch, hypothesis tensors, canon on the device)`` for ``score_ids``: the device is that of the first
+        hypothesis set that lives on one, else the current one."""
         words = [torch.as_tensor(w) for w in words]
         on_dev = [w.device for w in words if w.is_cuda]
         dev = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
         keys = list(keys)
         if words[0].dim() != 2 or words[0].shape[0] != len(keys):
-            raise ValueError(f"Cider: {len(keys)} keys for hypothesis words of shape {tuple(words[0].shape)}")
+            raise ValueError(f"{self._who}: {len(keys)} keys for hypothesis words of shape {tuple(words[0].shape)}")
         batch, canon = self.pack_ids(key2refs, vocabulary, vocab_size, keys)
         canon_dev = self._vocab[4].get(dev)
         if canon_dev is None:
             canon_dev = self._vocab[4][dev] = torch.from_numpy(canon).to(dev)
+        return batch, words, canon_dev
+
+    def _pack_strings(self, references, hypothesis):
+        """pycocoevalcap's arguments as ``(batch, rows, start_idx, end_idx, vocab_size)``: one row per key in the order of
+        ``references.keys()``, the words numbered through a table private to the call."""
+        who = f"{self._who}.compute_score"
+        keys = list(references.keys())
+        if not keys:
+            raise ValueError(f"{who}: no references")
+        if set(keys) != set(hypothesis.keys()):
+            raise ValueError(f"{who}: references and hypothesis must have the same keys")
+        end_idx, start_idx, first_word = 0, 1, 2
+        table = {}
+
+        def ids(sentence):
+            return np.asarray([table.setdefault(w, first_word + len(table)) for w in sentence.split()], dtype=np.int32)
+
+        hyps = []
+        for key in keys:
+            if len(hypothesis[key]) != 1:
+                raise ValueError(f"{who}: one hypothesis per key, {key!r} has {len(hypothesis[key])}")
+            hyps.append(ids(hypothesis[key][0]))
+        batch = PackedBatch(keys, lambda key: [ids(s) for s in references[key]], 0, self._who)
+        batch.n_words = vocab_size = first_word + len(table)
+        rows = np.full((len(keys), max(1, max(len(h) for h in hyps))), end_idx, dtype=np.int32)
+        for row, h in zip(rows, hyps):
+            row[:len(h)] = h
+        return batch, rows, start_idx, end_idx, vocab_size
+
+    def _device_inputs(self, batch, words, start_idx, end_idx, canon, vocab_size):
+        """Everything the host can check, raised as ValueError before the first launch, then the hypothesis sets as int32
+        planes of one length and stride on the device of ``canon`` and the references in one upload:
+        ``(sets, ints, (ref_words, sent_off, key_off, row_key, first_row) pointers)``; ``ints`` owns that memory."""
+        who = self._who
+        dev = canon.device
+        N = batch.row_key.shape[0]
+        if not 1 <= len(words) <= MAX_SETS:
+            raise ValueError(f"{who}: 1 to {MAX_SETS} hypothesis sets, got {len(words)}")
+        if batch.max_ref_words > MAX_REF_WORDS:
+            raise ValueError(f"{who}: a reference sentence of {batch.max_ref_words} words; the kernels take {MAX_REF_WORDS}")
+        if batch.words.size and (int(batch.words.min()) < 0 or int(batch.words.max()) >= batch.n_words):
+            raise ValueError(f"{who}: a reference word id outside [0, {batch.n_words}) (vocabulary {vocab_size} + "
+                             f"{batch.n_words - vocab_size} words outside it)")
+        sets = []
+        for w in words:
+            w = torch.as_tensor(w)
+            if w.dim() != 2 or w.shape[0] != N:
+                raise ValueError(f"{who}: hypothesis words must be ({N} rows, length), got {tuple(w.shape)}")
+            if w.shape[1] > MAX_HYP_WORDS:
+                raise ValueError(f"{who}: hypotheses of {w.shape[1]} words; the kernels take {MAX_HYP_WORDS}")
+            if not w.is_cuda:      # a host copy can be checked; on the device the kernel answers a bad id with NaN
+                ok = ((w >= 0) & (w < vocab_size)) | (w == start_idx) | (w == end_idx)
+                if not bool(ok.all()):
+                    raise ValueError(f"{who}: a hypothesis word id outside [0, {vocab_size})")
+            sets.append(w.to(device=dev, dtype=torch.int32))
+        T = sets[0].shape[1]
+        if any(w.shape[1] != T for w in sets):
+            raise ValueError(f"{who}: the hypothesis sets must have one length")
+        if any(w.stride(1) != 1 or w.stride(0) != sets[0].stride(0) for w in sets) or T == 0:
+            sets = [w.contiguous() for w in sets]
+        K, M, W = batch.first_row.shape[0], batch.sent_off.shape[0] - 1, batch.words.shape[0]
+        host = np.concatenate((batch.words, batch.sent_off, batch.key_off, batch.row_key, batch.first_row))
+        ints = torch.from_numpy(host).to(dev)          # the one upload
+        base = ints.data_ptr()
+        at = np.cumsum([0, W, M + 1, K + 1, N])
+        return sets, ints, tuple(ctypes.c_void_p(base + 4 * int(o)) for o in at)
+
+    def _workspace_of(self, need, dev):
+        if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        return self._workspace
+
+
+class Cider(PackedScorer):
+
+    def __init__(self, n=4, sigma=6.0):
+        if not 1 <= int(n) <= 4:
+            raise ValueError("Cider: n-grams of 1 to 4 words are built in")
+        if not sigma > 0:
+            raise ValueError("Cider: sigma must be > 0")
+        self._n, self._sigma = int(n), float(sigma)
+        self._workspace = None
+        self.clear_cache()
+
+    def method(self):
+        return "CIDEr"
+
+    # ---- the kernels ---------------------------------------------------------------------------------------------
+    def score_packed(self, batch, words, start_idx, end_idx, canon, vocab_size):
+        """Scores (S, N) f32 and reward (N,) f32 (None for S == 1) on the device of ``canon`` for the hypothesis sets
+        ``words`` (S tensors N x T of word ids) against the references of ``batch``.  Everything is checked before the
+        first launch: what the host can see raises ValueError here, and the entry point checks its limits again."""
+        lib = _lib.load()
+        dev = canon.device
+        sets, ints, (p_words, p_sent, p_key, p_row, p_first) = self._device_inputs(batch, words, start_idx, end_idx, canon,
+                                                                                   vocab_size)
+        T = sets[0].shape[1]
+        S, N, K = len(sets), batch.row_key.shape[0], batch.first_row.shape[0]
+        M, W = batch.sent_off.shape[0] - 1, batch.words.shape[0]
+        need = lib.ac_cider_workspace_bytes(W, M, K, S)
+        if need < 0:
+            raise _lib.HipLibraryError(f"ac_cider_workspace_bytes refused ({W} words, {M} sentences, {K} keys, {S} sets)")
+        workspace = self._workspace_of(need, dev)
+        scores = torch.empty(S, N, device=dev, dtype=torch.float32)
+        reward = torch.empty(N, device=dev, dtype=torch.float32) if S >= 2 else None
+        hyp = (ctypes.c_void_p * S)(*[w.data_ptr() for w in sets])
+        check(lib.ac_cider_scores(ctypes.cast(hyp, ctypes.c_void_p), S, sets[0].stride(0), N, T, int(start_idx), int(end_idx),
+                                  ptr(canon), int(vocab_size), batch.n_words, p_words, W, p_sent, M, batch.max_ref_words,
+                                  p_key, K, p_row, p_first, self._n, self._sigma, ptr(workspace), workspace.numel(),
+                                  ptr(scores), ptr(reward), stream()), "ac_cider_scores")
+        return scores, reward
+
+    # ---- strings (pycocoevalcap's contract) ------------------------------------------------------------------------
+    def compute_score(self, references, hypothesis):
+        batch, rows, start_idx, end_idx, vocab_size = self._pack_strings(references, hypothesis)
+        canon = torch.arange(vocab_size, device="cuda", dtype=torch.int32)
+        scores, _ = self.score_packed(batch, [torch.from_numpy(rows)], start_idx, end_idx, canon, vocab_size)
+        scores = scores[0].cpu().numpy().astype(np.float64)
+        return float(scores.mean()), scores
+
+    # ---- word ids (self-critical sequence training) ------------------------------------------------------------------
+    def score_ids(self, key2refs, vocabulary, vocab_size, keys, words, start_idx, end_idx):
+        """``{"scores": (S, N) f32, "reward": (N,) f32 = scores[0] - scores[1] (None for S == 1)}`` on the device, for the
+        S hypothesis sets ``words`` (N x T word ids each; N = len(keys))."""
+        batch, words, canon_dev = self._pack_for_ids(key2refs, vocabulary, vocab_size, keys, words)
         scores, reward = self.score_packed(batch, words, start_idx, end_idx, canon_dev, int(vocab_size))
         return {"scores": scores, "reward": reward}

@@ -645,6 +645,41 @@ int ac_cider_scores(const int* const* hyp, int sets, long hyp_ld, int N, int T, 
                     const int* sent_off, int sentences, int max_ref_words, const int* key_off, int keys,
                     const int* row_key, const int* first_row, int order, float sigma, void* workspace,
                     long workspace_bytes, float* scores, float* reward, void* stream);
+/* ---- BLEU and ROUGE-L on token ids (csrc/capmetrics.hip): the other two string metrics of the reference's evaluation --
+ * Both read what ac_cider_scores reads, under the same limits (AC_CIDER_MAX_*) and the same sentence rule: hyp, canon,
+ * ref_words / sent_off / key_off / row_key / first_row as described there; a hypothesis word outside [0, vocab_size)
+ * turns the scores of its key (and the totals over the keys) into NaN and is never used as an index; reference words
+ * are only compared.  workspace: 256-byte aligned, ac_capmetrics_workspace_bytes(keys, sets) bytes, for either entry.
+ * Every count is an integer, float64 enters in the closed formulas below and in one sum of fixed order: a call is
+ * bitwise repeatable.  AC_ERR_ARG beyond any limit, nothing launched.
+ *
+ * ac_bleu_scores - pycocoevalcap's bleu_scorer.py with option "closest", n-grams of 1 .. order (<= 4) words, per key:
+ *   testlen = hypothesis words;  guess[k] = max(0, testlen - k);
+ *   correct[k] = sum over the distinct hypothesis (k+1)-grams of min(count in the hypothesis, max over the key's
+ *   references of the count in that reference), whole n-grams compared word by word;
+ *   reflen = the reference length closest to testlen, of two equally close the smaller;
+ *   b_k = prod_{j <= k} (correct[j] + 1e-15) / (guess[j] + 1e-9);  bleu_k = b_k^(1 / (k + 1)), times exp(1 - 1 / ratio)
+ *   when ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1.
+ * stats int32 [sets][keys][2 + 2 * order] = testlen, reflen, guess[order], correct[order] (all -1 for a NaN key);
+ * scores f64 [sets][order][N], the rows of a key sharing the score of first_row[key]; corpus f64 [sets][order]: the same
+ * formulas on the integer totals of the four quantities over the distinct keys.
+ *
+ * ac_rouge_l_scores - pycocoevalcap's rouge.py, beta = 1.2, per key: lcs(h, r) the longest common subsequence in words of
+ * the hypothesis and each reference (the full dynamic program, bit-parallel over 64 hypothesis positions per word: no
+ * length heuristic, no band, no cut-off), p = max_r lcs / len(h), r = max_r lcs / len(r) (the two maxima may come from
+ * different references), score = (1 + beta^2) p r / (r + beta^2 p) when both are non-zero, else 0.
+ * lcs int32 [sets][sentences] (-1 in a NaN key); scores f64 [sets][N]; mean f64 [sets] over the distinct keys. */
+long ac_capmetrics_workspace_bytes(int keys, int sets);
+int ac_bleu_scores(const int* const* hyp, int sets, long hyp_ld, int N, int T, int start_idx, int end_idx,
+                   const int* canon, int vocab_size, const int* ref_words, long total_words, const int* sent_off,
+                   int sentences, int max_ref_words, const int* key_off, int keys, const int* row_key,
+                   const int* first_row, int order, void* workspace, long workspace_bytes, int* stats, double* scores,
+                   double* corpus, void* stream);
+int ac_rouge_l_scores(const int* const* hyp, int sets, long hyp_ld, int N, int T, int start_idx, int end_idx,
+                      const int* canon, int vocab_size, const int* ref_words, long total_words, const int* sent_off,
+                      int sentences, int max_ref_words, const int* key_off, int keys, const int* row_key,
+                      const int* first_row, void* workspace, long workspace_bytes, int* lcs, double* scores, double* mean,
+                      void* stream);
 /* ac_gru_layer that also keeps (r, z, n, W_hn h + b_hn) per (clip, step, direction): save [B][T][2][4H]. */
 int ac_gru_layer_train(const float* gx, const float* whhT, const float* bhh, const int* lens, float* out, float* save,
                        int B, int T, int hidden, void* stream);
