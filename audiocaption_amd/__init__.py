@@ -7,6 +7,8 @@ from .crnn_trm_encoder import Cnn14RnnEncoder, CrnnEncoder
 from .rnn_encoder import RnnEncoder
 from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionModel, TransformerModel
+from .rnn_decoder import BahAttnCatFcDecoder, RnnDecoder, Seq2SeqAttention, TemporalBahAttnDecoder
+from .attn_model import Seq2SeqAttnModel, TemporalSeq2SeqAttnModel
 from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
 from .cider import Cider
@@ -14,4 +16,5 @@ from .caption_metrics import Bleu, Rouge
 from .kd_loss import SupKdLoss, TokenLevelKdLoss
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
-           "CaptionModel", "TransformerModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]
+           "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
+           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]

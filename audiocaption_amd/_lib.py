@@ -32,9 +32,17 @@ class AcTrmWeights(ctypes.Structure):
         ("layer", AcTrmLayer * AC_MAX_LAYERS)]
 
 
+class AcBahWeights(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "emb_dim", "d_model", "attn_size", "attn_emb_dim", "fc_emb_dim", "vocab", "n_tags", "reserved")] + [
+        (n, ctypes.c_void_p) for n in ("emb", "temb", "w_ih", "w_hh", "b_ih", "b_hh", "attn_w", "attn_b", "attn_v",
+                                       "fc_w", "fc_b", "ctx_w", "ctx_b", "cls_w", "cls_b")]
+
+
 _I, _L, _F, _P = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 _U64 = ctypes.c_ulonglong
 _WP = ctypes.POINTER(AcTrmWeights)
+_BP = ctypes.c_void_p   # const ac_bah_weights*: callers pass ctypes.byref(AcBahWeights)
 
 # name -> (restype, argtypes); must list every symbol of include/audiocaption_hip.h
 SIGNATURES = {
@@ -93,6 +101,13 @@ SIGNATURES = {
     "ac_ens_greedy_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_sample_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_beam_step_select": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    # Bahdanau-attention GRU decoder (csrc/attn_gru.hip)
+    "ac_bah_workspace_floats": (_L, [_BP, _I, _I, _I, _I]),
+    "ac_bah_memory": (_I, [_BP, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ac_bah_step_logits": (_I, [_BP, _P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _P, _P]),
+    "ac_bah_greedy": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_bah_sample": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
+    "ac_bah_beam_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     # training step (csrc/train.hip)
     "ac_gemm": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),
     "ac_gemm_bf16x3": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),

@@ -166,6 +166,34 @@ def decoder_state_diverse(kind, prefix="decoder.", vocab_size=4981):
     return d
 
 
+def bah_decoder_state(prefix="", vocab_size=4981, emb_dim=512, d_model=512, attn_size=512, attn_emb_dim=512,
+                      fc_emb_dim=512, temporal=True, seed=BASE_SEED, end_scale=3.0):
+    """BahAttnCatFcDecoder / TemporalBahAttnDecoder tensors (reference rnn_decoder.py:159-181, hf_wrapper.py:1502-1511).
+    The GRU state is bounded by 1, so a wide classifier (std 4 / sqrt(d)) makes the next word depend on the state and the
+    attention scores (v of std 4 / sqrt(attn_size)) tell frames apart without going one-hot.  The classifier's <end> row is
+    ``end_scale`` times as long as the others: its logit swings that much wider with the state, so it now and then beats the
+    maximum of the other rows and clips stop at different steps."""
+    E, d, S, A, F = emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim
+    spec = [("word_embedding.weight", (vocab_size, E), 1.0),
+            ("model.weight_ih_l0", (3 * d, 3 * E), 1.0 / math.sqrt(3 * E)),
+            ("model.weight_hh_l0", (3 * d, d), 1.0 / math.sqrt(d)),
+            ("attn.h2attn.weight", (S, d + A), 1.0 / math.sqrt(d + A)),
+            ("attn.v", (S,), 4.0 / math.sqrt(S)),
+            ("fc_proj.weight", (E, F), 1.0 / math.sqrt(F)),
+            ("ctx_proj.weight", (E, A), 1.0 / math.sqrt(A)),
+            ("classifier.weight", (vocab_size, d), 4.0 / math.sqrt(d))]
+    if temporal:
+        spec.append(("temporal_embedding.weight", (4, E), 1.0))
+    out = {}
+    for name, shape, std in spec:
+        out[prefix + name] = _normal(prefix + name, shape, std, seed)
+    for name, n in (("model.bias_ih_l0", 3 * d), ("model.bias_hh_l0", 3 * d), ("attn.h2attn.bias", S), ("fc_proj.bias", E),
+                    ("ctx_proj.bias", E), ("classifier.bias", vocab_size)):
+        out[prefix + name] = _uniform(prefix + name, (n,), -0.1, 0.1, seed)
+    out[prefix + "classifier.weight"][2] *= np.float32(end_scale)
+    return out
+
+
 def cnn14rnn_trm_state(vocab_size=4368, seed=BASE_SEED):
     """Full state dict of the Cnn14Rnn-Trm captioner."""
     out = {}

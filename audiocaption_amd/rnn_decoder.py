@@ -1,0 +1,227 @@
+"""Bahdanau-attention GRU caption decoders, MI355X path.  Plugin-compatible with the reference classes ``RnnDecoder``,
+``BahAttnCatFcDecoder`` (captioning/models/rnn_decoder.py:10-36,159-216), ``Seq2SeqAttention`` (utils/model_util.py, as
+restated at hf_wrapper.py:1377-1414) and ``TemporalBahAttnDecoder`` (hf_wrapper.py:1502-1554): same constructor keywords,
+attributes and ``state_dict()`` keys, so a reference checkpoint loads with ``strict=True``.
+
+The nn modules own the parameters only; the arithmetic runs in csrc/attn_gru.hip.  ``forward`` is one decoder step
+(``ac_bah_step_logits``) with the reference's dict contract; the searches of ``attn_model.py`` call ``memory`` once per batch
+and then ``greedy`` / ``sample`` (one C call each) or ``step`` (beam search).
+
+Built: ``rnn_type="GRU"``, ``num_layers=1``, unidirectional; emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim each a
+multiple of 32 up to 1024; vocab_size <= 16384.  Anything else raises NotImplementedError in the constructor.  Inference
+only: dropout is the identity.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import kernels as K
+from ._lib import check, f32c, ptr, stream
+from .transformer_decoder import BaseDecoder
+
+MAX_DIM, MAX_VOCAB, MAX_FRAMES = 1024, 16384, 2048
+
+
+class Seq2SeqAttention(nn.Module):
+    """Parameters of the additive attention: ``h2attn`` takes cat(decoder state, encoder frame) - the first ``hs_dec`` input
+    columns belong to the decoder state (hf_wrapper.py:1401) - and ``v`` scores tanh(h2attn(.))."""
+
+    def __init__(self, hs_enc, hs_dec, attn_size):
+        super().__init__()
+        self.h2attn = nn.Linear(hs_enc + hs_dec, attn_size)
+        self.v = nn.Parameter(torch.randn(attn_size))
+
+    def forward(self, h_dec, h_enc, src_lens):
+        raise NotImplementedError("Seq2SeqAttention runs inside the decoder step (csrc/attn_gru.hip), not on its own")
+
+
+class RnnDecoder(BaseDecoder):
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout)
+        self.d_model = d_model
+        self.num_layers = kwargs.get("num_layers", 1)
+        self.bidirectional = kwargs.get("bidirectional", False)
+        self.rnn_type = kwargs.get("rnn_type", "GRU")
+        if self.rnn_type != "GRU":
+            raise NotImplementedError(f"rnn_type={self.rnn_type!r}: the HIP decoder runs a GRU only")
+        if self.num_layers != 1:
+            raise NotImplementedError(f"num_layers={self.num_layers}: the HIP decoder runs one GRU layer")
+        if self.bidirectional:
+            raise NotImplementedError("bidirectional=True: the HIP decoder is unidirectional")
+        self.classifier = nn.Linear(self.d_model, vocab_size)
+
+    def forward(self, x):
+        raise NotImplementedError
+
+    def init_hidden(self, bs, device):
+        return torch.zeros(1, bs, self.d_model, device=device)
+
+
+class BahAttnCatFcDecoder(RnnDecoder):
+    """GRU over cat(word embedding, ctx_proj(attention context), fc_proj(fc_emb)) (rnn_decoder.py:159-216)."""
+
+    n_tags = 0
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs)
+        attn_size = kwargs.get("attn_size", self.d_model)
+        for name, v in (("emb_dim", emb_dim), ("d_model", d_model), ("attn_size", attn_size),
+                        ("attn_emb_dim", attn_emb_dim), ("fc_emb_dim", fc_emb_dim)):
+            if v < 32 or v % 32 or v > MAX_DIM:
+                raise NotImplementedError(f"{name}={v}: the HIP decoder needs a multiple of 32 up to {MAX_DIM}")
+        if not 1 <= vocab_size <= MAX_VOCAB:
+            raise NotImplementedError(f"vocab_size={vocab_size}: the pick and sampling kernels hold at most {MAX_VOCAB} words")
+        self.attn_size = attn_size
+        self.model = nn.GRU(input_size=self.emb_dim * 3, hidden_size=self.d_model, batch_first=True, num_layers=1,
+                            bidirectional=False)
+        self.attn = Seq2SeqAttention(self.attn_emb_dim, self.d_model, attn_size)
+        self.fc_proj = nn.Linear(self.fc_emb_dim, self.emb_dim)
+        self.ctx_proj = nn.Linear(self.attn_emb_dim, self.emb_dim)
+        self._w = self._w_key = self._w_keep = None
+
+    # ------------------------------------------------------------------------------------------
+    def weights(self):
+        """ac_bah_weights struct of device pointers (rebuilt when a parameter changes)."""
+        key = tuple((t.data_ptr(), t._version, t.dtype) for t in self.parameters()) + (_lib.param_generation(),)
+        if self._w is not None and key == self._w_key:
+            return self._w
+        keep = []
+
+        def P(t):
+            t = f32c(t.detach())
+            keep.append(t)
+            return ctypes.c_void_p(ptr(t).value)
+
+        w = _lib.AcBahWeights()
+        w.emb_dim, w.d_model, w.attn_size = self.emb_dim, self.d_model, self.attn_size
+        w.attn_emb_dim, w.fc_emb_dim, w.vocab, w.n_tags = self.attn_emb_dim, self.fc_emb_dim, self.vocab_size, self.n_tags
+        w.emb = P(self.word_embedding.weight)
+        if self.n_tags:
+            w.temb = P(self.temporal_embedding.weight)
+        w.w_ih, w.w_hh = P(self.model.weight_ih_l0), P(self.model.weight_hh_l0)
+        w.b_ih, w.b_hh = P(self.model.bias_ih_l0), P(self.model.bias_hh_l0)
+        w.attn_w, w.attn_b, w.attn_v = P(self.attn.h2attn.weight), P(self.attn.h2attn.bias), P(self.attn.v)
+        w.fc_w, w.fc_b = P(self.fc_proj.weight), P(self.fc_proj.bias)
+        w.ctx_w, w.ctx_b = P(self.ctx_proj.weight), P(self.ctx_proj.bias)
+        w.cls_w, w.cls_b = P(self.classifier.weight), P(self.classifier.bias)
+        self._w, self._w_key, self._w_keep = w, key, keep
+        return w
+
+    def memory(self, attn_emb, fc_emb, attn_emb_len, rows_per_clip=1, max_length=20):
+        """Once per batch: the workspace with the key projection and the fc part of the input gates (``ac_bah_memory``).
+        Returns the handle ``step`` / ``greedy`` / ``sample`` take."""
+        lib = _lib.load()
+        w = self.weights()
+        attn_emb, fc_emb = f32c(attn_emb), f32c(fc_emb)
+        ptr(attn_emb), ptr(fc_emb)   # a CPU tensor is refused here, before anything is uploaded
+        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
+            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
+                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        B, Tm, _ = attn_emb.shape
+        if Tm > MAX_FRAMES:
+            raise NotImplementedError(f"{Tm} frames of audio memory: the attention kernel holds at most {MAX_FRAMES}")
+        dev = attn_emb.device
+        R = B * int(rows_per_clip)
+        n = lib.ac_bah_workspace_floats(ctypes.byref(w), B, R, Tm, int(max_length))
+        if n <= 0:
+            raise _lib.HipLibraryError("ac_bah_workspace_floats rejected the decoder configuration")
+        mem = {"attn_emb": attn_emb, "len": K.upload(attn_emb_len, dev, torch.int32), "B": B, "R": R, "Tm": Tm,
+               "max_length": int(max_length), "row_div": int(rows_per_clip),
+               "ws": torch.empty(n, device=dev, dtype=torch.float32)}
+        check(lib.ac_bah_memory(ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), B, R, Tm, int(max_length), ptr(mem["ws"]),
+                                stream()), "ac_bah_memory")
+        return mem
+
+    def step(self, mem, state_in, state_out, words=None, word_stride=1, tags=None, logit=None, ldl=None, embed=None,
+             attn_weight=None, attn_strides=(0, 0)):
+        """One decoder step over the rows of ``mem`` into caller-owned buffers (``ac_bah_step_logits``)."""
+        ldl = self.vocab_size if ldl is None else ldl
+        check(_lib.load().ac_bah_step_logits(
+            ctypes.byref(self.weights()), ptr(mem["attn_emb"]), ptr(mem["len"]), mem["B"], mem["R"], mem["row_div"], mem["Tm"],
+            mem["max_length"], ptr(state_in), ptr(words), word_stride, ptr(tags), ptr(state_out), ptr(embed), self.d_model,
+            ptr(logit), ldl, ptr(attn_weight), attn_strides[0], attn_strides[1], ptr(mem["ws"]), stream()),
+            "ac_bah_step_logits")
+
+    def _search(self, mem, tags, start_idx, end_idx, pad_idx, sampler=None):
+        lib = _lib.load()
+        B, Tm, L, dev = mem["B"], mem["Tm"], mem["max_length"], mem["attn_emb"].device
+        f32 = dict(device=dev, dtype=torch.float32)
+        out = {"seq": torch.empty(B, L, device=dev, dtype=torch.int64), "logit": torch.empty(B, L, self.vocab_size, **f32),
+               "sampled_logprob": torch.empty(B, L, **f32), "embed": torch.empty(B, L, self.d_model, **f32),
+               "attn_weight": torch.empty(B, Tm, L, **f32), "state": torch.empty(1, B, self.d_model, **f32),
+               "unfinished_cnt": torch.empty(L, device=dev, dtype=torch.int32)}
+        args = [ctypes.byref(self.weights()), ptr(mem["attn_emb"]), ptr(mem["len"]), ptr(tags), B, Tm, L, start_idx, end_idx,
+                pad_idx, ptr(out["seq"]), ptr(out["logit"]), ptr(out["sampled_logprob"]), ptr(out["embed"]),
+                ptr(out["attn_weight"]), ptr(out["state"]), ptr(out["unfinished_cnt"]), ptr(mem["ws"])]
+        if sampler is None:
+            check(lib.ac_bah_greedy(*args, stream()), "ac_bah_greedy")
+        else:
+            method, k, top_p, temp, seed = sampler
+            from .sampling import seed_word
+            mem["seed"] = torch.full((1,), seed_word(seed), device=dev, dtype=torch.int64)
+            check(lib.ac_bah_sample(*args, method, k, float(top_p), float(temp), ptr(mem["seed"]), stream()), "ac_bah_sample")
+        return out
+
+    def greedy(self, mem, tags, start_idx, end_idx, pad_idx):
+        """The whole greedy search in one C call (``ac_bah_greedy``); ``mem`` from ``memory(..., rows_per_clip=1)``."""
+        return self._search(mem, tags, start_idx, end_idx, pad_idx)
+
+    def sample(self, mem, tags, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed):
+        """The whole sampled search in one C call (``ac_bah_sample``): the sampler and Philox counters of ``ac_trm_sample``."""
+        return self._search(mem, tags, start_idx, end_idx, pad_idx, (method, k, top_p, temp, seed))
+
+    def _tags(self, input_dict, n):
+        return None
+
+    def forward(self, input_dict):
+        """One step with the reference's contract (rnn_decoder.py:183-216): ``word`` (N, 1), optional ``state``
+        (1, N, d_model), ``fc_emb``, ``attn_emb``, ``attn_emb_len`` -> ``state``, ``embed`` (N, 1, d_model), ``logit``
+        (N, 1, V), ``attn_weight`` (N, Tm).  The memory side is recomputed on every call, as in the reference."""
+        attn_emb = input_dict["attn_emb"]
+        dev = attn_emb.device
+        N, Tm = attn_emb.shape[0], attn_emb.shape[1]
+        mem = self.memory(attn_emb, input_dict["fc_emb"], input_dict["attn_emb_len"], 1, 1)
+        state = input_dict.get("state")
+        state_in = f32c(state).reshape(N, self.d_model) if state is not None else torch.zeros(N, self.d_model, device=dev)
+        word = input_dict["word"]
+        if word.dim() != 2 or word.shape != (N, 1):
+            raise NotImplementedError(f"word of shape {tuple(word.shape)}: the HIP decoder step takes word ids (N, 1)")
+        tags = self._tags(input_dict, N)
+        if tags is not None:
+            tags = K.upload(tags, dev, torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        out = {"state": torch.empty(1, N, self.d_model, **f32), "embed": torch.empty(N, 1, self.d_model, **f32),
+               "logit": torch.empty(N, 1, self.vocab_size, **f32), "attn_weight": torch.empty(N, Tm, **f32)}
+        self.step(mem, state_in, out["state"], words=K.upload(word.reshape(N), dev, torch.int32), tags=tags,
+                  logit=out["logit"], embed=out["embed"], attn_weight=out["attn_weight"], attn_strides=(Tm, 1))
+        return out
+
+
+def check_temporal_tag(tag, n):
+    """``temporal_tag`` as int64 (n,) on the host; raises ValueError unless it holds n integers in 0..3."""
+    if tag is None:
+        raise ValueError("temporal_tag is required: one integer in 0..3 per clip")
+    tag = torch.as_tensor(tag).detach().cpu()
+    if tag.dtype.is_floating_point or tag.dtype == torch.bool or tag.numel() != n:
+        raise ValueError(f"temporal_tag must hold {n} integers in 0..3 (got dtype {tag.dtype}, {tag.numel()} values)")
+    tag = tag.reshape(n).to(torch.int64)
+    if n and (int(tag.min()) < 0 or int(tag.max()) > 3):
+        raise ValueError(f"temporal_tag must be in 0..3 (got {tag.tolist()})")
+    return tag
+
+
+class TemporalBahAttnDecoder(BahAttnCatFcDecoder):
+    """``BahAttnCatFcDecoder`` whose first input is the embedding of the clip's temporal tag instead of <start>
+    (hf_wrapper.py:1502-1554)."""
+
+    n_tags = 4
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs)
+        self.temporal_embedding = nn.Embedding(4, emb_dim)
+
+    def _tags(self, input_dict, n):
+        return check_temporal_tag(input_dict.get("temporal_tag"), n) if input_dict["t"] == 0 else None

@@ -470,6 +470,74 @@ int ac_ens_sample_pick(const float* const* logits, int n_models, long ld, int ro
 int ac_ens_beam_step_select(const float* const* logits, int n_models, long ld, int B, int beam, int V, int t, float temp,
                             const float* cum_logprob, float* top_val, int* top_idx, float* scratch, void* stream);
 
+/* ---- Bahdanau-attention GRU decoder (rnn_decoder.py:10-36,74-113,159-216, hf_wrapper.py:1377-1554) -------------
+ * BahAttnCatFcDecoder / TemporalBahAttnDecoder for inference, csrc/attn_gru.hip.  One GRU layer, unidirectional.  With
+ * E = emb_dim, d = d_model, S = attn_size, A = attn_emb_dim, F = fc_emb_dim (each a multiple of 32 up to 1024), V = vocab
+ * (<= 16384, the pick and sampling kernels' limit), Tm <= 2048 frames; n_tags = 4 (temporal decoder) or 0.  Every entry
+ * point refuses anything else before it launches (AC_ERR_ARG; the size query: -1).
+ * One step over R rows (row r uses the audio memory of clip r / row_div), in the reference's order:
+ *   score_t = v . tanh(W_h h + ek[t]), -1e10 at t >= len, softmax, c = sum_t w_t attn_emb[t], p_ctx = ctx_proj c,
+ *   GRU cell (gates r, z, n) on W_ih[:, :2E] [embed, p_ctx] + gf and W_hh h + b_hh, logit = classifier h' + bias.
+ * The projections run on 64-row tiles of the exact-f32 MFMA GEMM (each weight is read once per tile of rows); accurate
+ * tanhf / expf.  ek = W_enc attn_emb + b_attn [B][Tm][S] and gf = W_ih[:, 2E:3E] fc_proj(fc_emb) + b_ih [B][3d] do not
+ * depend on the step: ac_bah_memory computes them once per batch into the workspace. */
+typedef struct {
+  int32_t emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim, vocab, n_tags, reserved;
+  const float* emb;    /* word_embedding.weight     [V][E]                                      */
+  const float* temb;   /* temporal_embedding.weight [4][E] (NULL when n_tags == 0)              */
+  const float* w_ih;   /* model.weight_ih_l0        [3d][3E]: columns embed | p_ctx | p_fc      */
+  const float* w_hh;   /* model.weight_hh_l0        [3d][d]                                     */
+  const float* b_ih;   /* model.bias_ih_l0 [3d]                                                 */
+  const float* b_hh;   /* model.bias_hh_l0 [3d]                                                 */
+  const float* attn_w; /* attn.h2attn.weight [S][d + A]: decoder-state columns, then the frame's */
+  const float* attn_b; /* attn.h2attn.bias   [S]                                                */
+  const float* attn_v; /* attn.v             [S]                                                */
+  const float* fc_w;   /* fc_proj.weight  [E][F] */
+  const float* fc_b;
+  const float* ctx_w;  /* ctx_proj.weight [E][A] */
+  const float* ctx_b;
+  const float* cls_w;  /* classifier.weight [V][d] */
+  const float* cls_b;  /* classifier.bias   [V]    */
+} ac_bah_weights;
+
+/* Workspace floats of a batch of B clips decoded over R >= B rows (R = B for greedy / sampled search, B * beam for beam
+ * search); the same (B, R, Tm, max_len) go to every call that shares the workspace.  16-byte aligned. */
+long ac_bah_workspace_floats(const ac_bah_weights* w, int B, int R, int Tm, int max_len);
+/* Once per batch: attn_emb [B][Tm][A], fc_emb [B][F] -> ek, gf in ws (the reference recomputes both for every row at every
+ * step, hf_wrapper.py:1402,1542). */
+int ac_bah_memory(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, int B, int R, int Tm, int max_len,
+                  float* ws, void* stream);
+/* ONE decoder step over R = B * row_div rows.  state_in / state_out [R][d] (distinct buffers; zeros before the first step);
+ * the input of row r is word id words[r * word_stride] or, with tags != NULL (step 0 of a temporal decoder,
+ * hf_wrapper.py:1521-1523), the embedding of tag tags[r / row_div] (0..3).  Writes logit row r at logit + r * ldl (ldl >= V),
+ * the GRU output at embed + r * ld_embed (embed may be NULL) and the weight of frame t at
+ * attn_weight + r * attn_row_stride + t * attn_frame_stride (may be NULL). */
+int ac_bah_step_logits(const ac_bah_weights* w, const float* attn_emb, const int* mem_len, int B, int R, int row_div,
+                       int Tm, int max_len, const float* state_in, const int* words, long word_stride, const int* tags,
+                       float* state_out, float* embed, long ld_embed, float* logit, long ldl, float* attn_weight,
+                       long attn_row_stride, long attn_frame_stride, float* ws, void* stream);
+/* Greedy / sampled search (base.py:152-218 with attn_model.py:60-92) in one call, no host synchronisation: max_len times the
+ * step plus ac_ens_greedy_pick's / the sampler's pick and bookkeeping.  tags [B] for a temporal decoder, NULL otherwise.
+ * seq [B][max_len] int64, logit [B][max_len][V], logprob [B][max_len], embed [B][max_len][d], attn_weight [B][Tm][max_len],
+ * state [B][d] (the state after the last executed step), unfinished_cnt [max_len] as ac_trm_greedy's.  Every output is
+ * written in full: the columns of a row after its first <end>, and of the steps after every row has ended, read seq = end_idx
+ * and 0 everywhere else (the launch sequence does not depend on the data; once the search is over the per-row kernels return
+ * at once and the state passes through).  Sampling: ac_trm_sample's rules and Philox counters (step, row). */
+int ac_bah_greedy(const ac_bah_weights* w, const float* attn_emb, const int* mem_len, const int* tags, int B, int Tm,
+                  int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                  float* embed, float* attn_weight, float* state, int* unfinished_cnt, float* ws, void* stream);
+int ac_bah_sample(const ac_bah_weights* w, const float* attn_emb, const int* mem_len, const int* tags, int B, int Tm,
+                  int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                  float* embed, float* attn_weight, float* state, int* unfinished_cnt, float* ws, int method, int k,
+                  float top_p, float temp, const uint64_t* seed_dev, void* stream);
+/* Beam search is ac_bah_step_logits + ac_ens_beam_step_select (one member) + ac_trm_beam_update + this re-gather
+ * (hf_wrapper.py:1661,1665-1669): row r of state_next / hist_out takes the new state and the attention history
+ * [max_len][Tm] (columns 0..t-1 of hist_in plus step_weight [R][Tm] as column t) of row src_row[r]; the rows of a clip with
+ * active_before[clip] == 0 (retired before step t) keep their own.  Distinct in / out buffers. */
+int ac_bah_beam_gather(const int* src_row, const int* active_before, const float* state_new, float* state_next,
+                       const float* step_weight, const float* hist_in, float* hist_out, int B, int beam, int d, int Tm,
+                       int max_len, int t, void* stream);
+
 /* ================================== training step ==================================
  * The reference trains GRU + decoder on the frozen Cnn14 with scheduled sampling: step t runs the decoder on a
  * (N, t+1) prefix and keeps the last position's logit (base.py:131-137,152-199, transformer_model.py:34-57).  The
