@@ -9,6 +9,7 @@ from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionModel, TransformerModel
 from .rnn_decoder import BahAttnCatFcDecoder, RnnDecoder, Seq2SeqAttention, TemporalBahAttnDecoder
 from .attn_model import Seq2SeqAttnModel, TemporalSeq2SeqAttnModel
+from .sed_model import Cnn8rnnSedModel
 from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
 from .cider import Cider
@@ -17,4 +18,4 @@ from .kd_loss import SupKdLoss, TokenLevelKdLoss
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
            "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
-           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]
+           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]

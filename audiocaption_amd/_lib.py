@@ -108,6 +108,11 @@ SIGNATURES = {
     "ac_bah_greedy": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_bah_sample": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
     "ac_bah_beam_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    # sound-event tagger (csrc/sed.hip)
+    "ac_pool_avgmax": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ac_sed_head": (_I, [_P, _P, _P, _P, _L, _I, _P]),
+    "ac_sed_tag_workspace_bytes": (_L, [_I, _I, _I]),
+    "ac_sed_temporal_tag": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _L, _P, _P]),
     # training step (csrc/train.hip)
     "ac_gemm": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),
     "ac_gemm_bf16x3": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _I, _F, _I, _F, _U64, _P, _L, _P, _I, _P]),

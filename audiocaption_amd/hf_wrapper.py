@@ -15,6 +15,10 @@ LongTensor (B, max_length); ``model.config.sample_rate`` is what callers resampl
 With ``transformers`` importable the two classes ARE a ``PretrainedConfig`` / ``PreTrainedModel`` (``from_pretrained`` /
 ``save_pretrained`` work on a local directory); without it they fall back to plain classes with ``load_checkpoint``.
 
+``Cnn14RnnTempAttnGruConfig`` / ``Cnn14RnnTempAttnGruModel`` mirror hf_wrapper.py:1862-1974 the same way: ``cap_model`` =
+``TemporalSeq2SeqAttnModel(Cnn14RnnEncoder, TemporalBahAttnDecoder)`` and ``sed_model`` = ``Cnn8rnnSedModel(447)``, whose
+temporal tag (0..3 per clip) the decoder embeds at step 0; the tagger runs first, on the device, then the captioner.
+
 ``CaptioningModel`` is the same call surface around ANY model of this package (the reference ships it only for its EffB2
 model), so ``demo.py``-style callers can use the Cnn14Rnn-Trm captioner without the input_dict plumbing.
 """
@@ -23,8 +27,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import kernels as K
+from .attn_model import TemporalSeq2SeqAttnModel
+from .cnn_encoder import Cnn14Encoder
 from .config import merge_load_state_dict
+from .crnn_trm_encoder import Cnn14RnnEncoder
 from .effnet_encoder import EfficientNetB2
+from .mel import MelSpectrogramBuffers, MelTables
+from .rnn_decoder import TemporalBahAttnDecoder, check_temporal_tag
+from .rnn_encoder import RnnEncoder
+from .sed_model import Cnn8rnnSedModel
 from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionMetaMixin, TransformerModel
 
@@ -182,6 +194,100 @@ class Effb2TrmCaptioningModel(PreTrainedModel):
     def forward(self, audio, audio_length, sample_method="beam", beam_size=3, max_length=20, temp=1.0):
         return self.model(_input_dict(self.device, audio, audio_length, sample_method, beam_size, max_length,
                                       temp))["seq"].cpu()
+
+
+class Cnn14RnnTempAttnGruConfig(PretrainedConfig):
+    """hf_wrapper.py:1862-1894: same keys, same defaults."""
+    model_type = "cnn14rnn_tempattn_gru_captioning"
+
+    def __init__(self, sample_rate=32000, encoder_rnn_bidirectional=True, encoder_rnn_hidden_size=256,
+                 encoder_rnn_dropout=0.5, encoder_rnn_num_layers=3, decoder_emb_dim=512, vocab_size=4981, fc_emb_dim=512,
+                 attn_emb_dim=512, decoder_rnn_type="GRU", decoder_num_layers=1, decoder_d_model=512, decoder_dropout=0.5,
+                 **kwargs):
+        self.sample_rate = sample_rate
+        self.encoder_rnn_bidirectional = encoder_rnn_bidirectional
+        self.encoder_rnn_hidden_size = encoder_rnn_hidden_size
+        self.encoder_rnn_dropout = encoder_rnn_dropout
+        self.encoder_rnn_num_layers = encoder_rnn_num_layers
+        self.decoder_emb_dim = decoder_emb_dim
+        self.vocab_size = vocab_size
+        self.fc_emb_dim = fc_emb_dim
+        self.attn_emb_dim = attn_emb_dim
+        self.decoder_rnn_type = decoder_rnn_type
+        self.decoder_num_layers = decoder_num_layers
+        self.decoder_d_model = decoder_d_model
+        self.decoder_dropout = decoder_dropout
+        super().__init__(**kwargs)
+
+
+class Cnn14RnnTempAttnGruModel(PreTrainedModel):
+    """hf_wrapper.py:1897-1974.  The state dict has the reference's keys (``cap_model.encoder.cnn...``,
+    ``cap_model.encoder.rnn.network...``, ``cap_model.decoder...``, ``sed_model...``) and the two buffers of the top-level
+    ``melspec_extractor``, which a checkpoint may or may not carry; the tagger's log-mel is computed from them."""
+    config_class = Cnn14RnnTempAttnGruConfig
+    main_input_name = "audio"
+    _keys_to_ignore_on_load_missing = [r"melspec_extractor\."]
+
+    def __init__(self, config):
+        super().__init__(config)
+        sr = config.sample_rate
+        self.melspec_extractor = MelSpectrogramBuffers(sr, 32 * sr // 1000, 50.0, float({32000: 14000, 16000: 8000}[sr]), 64,
+                                                       "slaney", "slaney")
+        encoder = Cnn14RnnEncoder(
+            Cnn14Encoder(sample_rate=sr),
+            RnnEncoder(-1, 2048, 2048, bidirectional=config.encoder_rnn_bidirectional,
+                       hidden_size=config.encoder_rnn_hidden_size, dropout=config.encoder_rnn_dropout,
+                       num_layers=config.encoder_rnn_num_layers))
+        decoder = TemporalBahAttnDecoder(emb_dim=config.decoder_emb_dim, vocab_size=config.vocab_size,
+                                         fc_emb_dim=config.fc_emb_dim, attn_emb_dim=config.attn_emb_dim,
+                                         rnn_type=config.decoder_rnn_type, num_layers=config.decoder_num_layers,
+                                         d_model=config.decoder_d_model, dropout=config.decoder_dropout)
+        self.cap_model = TemporalSeq2SeqAttnModel(encoder, decoder)
+        self.sed_model = Cnn8rnnSedModel(classes_num=447, sample_rate=sr)
+        self._sed_tables = None
+        self._sed_tables_key = None
+        self.post_init()
+
+    def _init_weights(self, module):
+        """The sub-modules initialise themselves at construction (as the reference's do); nothing is re-drawn here."""
+
+    def load_checkpoint(self, state_dict, strict=True, output_fn=lambda s: None):
+        """Load a state dict in the published layout (a path, or a dict, possibly under ``"model"``).  ``strict``: every key
+        of the module must be present with the right shape (the mel buffers may be absent); otherwise the tolerant
+        shape-filtered merge of train_util.py:188-202."""
+        if isinstance(state_dict, str):
+            state_dict = torch.load(state_dict, map_location="cpu")
+        if "model" in state_dict and isinstance(state_dict["model"], dict):
+            state_dict = state_dict["model"]
+        if strict:
+            return self.load_state_dict(state_dict, strict=True)
+        return merge_load_state_dict(state_dict, self, output_fn)
+
+    def _tables(self, dev):
+        mkey = self.melspec_extractor.key()
+        if self._sed_tables is None or self._sed_tables.window.device != dev or self._sed_tables_key != mkey:
+            sr = self.config.sample_rate
+            cnn = self.cap_model.encoder.cnn
+            self._sed_tables = MelTables(sr, cnn.n_fft, cnn.hop_length, cnn.f_min, cnn.f_max, 64, "slaney", "slaney", dev,
+                                         window=self.melspec_extractor.spectrogram.window, fb=self.melspec_extractor.mel_scale.fb)
+            self._sed_tables_key = mkey
+        return self._sed_tables
+
+    def temporal_tags(self, audio, temporal_tag=None):
+        """The clips' temporal tags as the reference forms them (hf_wrapper.py:1954-1961): the tagger's, combined with a
+        caller's ``temporal_tag`` by element-wise minimum.  int64 on the host - one copy of B integers, which
+        ``check_temporal_tag`` wants there anyway."""
+        sed_tag = self.sed_model.forward_wav(audio, tables=self._tables(audio.device))
+        if temporal_tag is not None:
+            mine = K.upload(check_temporal_tag(temporal_tag, audio.shape[0]), audio.device, torch.int32)
+            sed_tag = torch.minimum(sed_tag, mine)
+        return sed_tag.cpu().long()
+
+    @torch.no_grad()
+    def forward(self, audio, audio_length, temporal_tag=None, sample_method="beam", beam_size=3, max_length=20, temp=1.0):
+        d = _input_dict(self.device, audio, audio_length, sample_method, beam_size, max_length, temp)
+        d["temporal_tag"] = self.temporal_tags(d["wav"], temporal_tag)
+        return self.cap_model(d)["seq"].cpu()
 
 
 class CaptioningConfig:

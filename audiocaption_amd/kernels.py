@@ -5,6 +5,7 @@ current stream to libaudiocaption_hip.so and raises on any failure.  No function
 anything on the host and none has a fallback.
 """
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -517,3 +518,49 @@ def specaug_stripes(seed, B, T, F=64, time_width=64, time_num=2, freq_width=8, f
             d = int(rng.integers(0, freq_width))
             out[b, time_num + k] = (int(rng.integers(0, F - d)), d)
     return out
+
+
+# ---- sound-event tagger (csrc/sed.hip) ----------------------------------------------------------------------------------
+def pool_avgmax(x, out, B, Hp, H, W, C, ph, Hp_out=0, mean_w=False):
+    """avg_pool + max_pool over a (ph, 2) window (time, mel) on the conv stack's layout: x [B*Hp][W][C] f32 -> out
+    [B*Hp_out][W/2][C] with rows at or beyond H // ph written as zeros, or, with ``mean_w`` (ph = 1), the pool followed by the
+    mean over the pooled mel columns, out dense (B, H, C)."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("pool_avgmax reads and writes f32")
+    need_in = B * Hp * W * C
+    need_out = B * H * C if mean_w else B * Hp_out * (W // 2) * C
+    if x.numel() < need_in or out.numel() < need_out:
+        raise ValueError("pool_avgmax: a buffer is smaller than its geometry")
+    check(lib.ac_pool_avgmax(ptr(x), ptr(out), B, Hp, H, W, C, ph, Hp_out, 1 if mean_w else 0, stream()), "ac_pool_avgmax")
+    return out
+
+
+def sed_head(x, bias=None, pre=None):
+    """x (rows, C) -> clamp(sigmoid(x + bias), 1e-7, 1); ``pre`` (same shape, optional) receives x + bias."""
+    lib = _lib.load()
+    x = f32c(_dev(x))
+    rows, C = x.shape
+    prob = torch.empty_like(x)
+    if pre is not None and (pre.shape != x.shape or pre.dtype != torch.float32 or not pre.is_contiguous()):
+        raise ValueError("sed_head: pre must be a contiguous f32 tensor of x's shape")
+    check(lib.ac_sed_head(ptr(x), ptr(bias), ptr(pre), ptr(prob), rows, C, stream()), "ac_sed_head")
+    return prob
+
+
+def sed_temporal_tag(prob, frames_num, ratio=4, high=0.75, low=0.25, n_connect=1, time_resolution=0.01, thre=0.5,
+                     workspace=None):
+    """Segment-wise probabilities (B, S, C) -> (int32 device tensor (B,) of temporal tags 0..3, workspace): the reference's
+    double_threshold + decode_with_timestamps on the frame-wise array (segments repeated ``ratio`` times, the last one
+    stretched to ``frames_num``) without forming it.  ``workspace``: a previous call's, re-used when large enough."""
+    lib = _lib.load()
+    prob = f32c(_dev(prob))
+    B, S, C = prob.shape
+    need = lib.ac_sed_tag_workspace_bytes(B, S, C)
+    if workspace is None or workspace.numel() * 4 < need or workspace.device != prob.device:
+        workspace = torch.empty((need + 15) // 16, 4, device=prob.device, dtype=torch.int32)
+    tags = torch.empty(B, device=prob.device, dtype=torch.int32)
+    rule = (ctypes.c_double * 2)(float(time_resolution), float(thre))   # host doubles: the pair rule runs in float64
+    check(lib.ac_sed_temporal_tag(ptr(prob), B, S, C, int(frames_num), int(ratio), float(high), float(low), int(n_connect),
+                                  rule, ptr(workspace), workspace.numel() * 4, ptr(tags), stream()), "ac_sed_temporal_tag")
+    return tags, workspace

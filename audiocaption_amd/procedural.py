@@ -194,6 +194,66 @@ def bah_decoder_state(prefix="", vocab_size=4981, emb_dim=512, d_model=512, attn
     return out
 
 
+SED_CHANNELS = [1, 64, 128, 256, 512]
+
+
+def sed_state(prefix="", classes_num=447, seed=BASE_SEED, head_seed=None, head_scale=5.0, active=3):
+    """Cnn8rnnSedModel tensors (reference hf_wrapper.py:1791-1808).  The conv blocks, fc1 and the GRU are drawn like the
+    Cnn14 stack's.  ``fc_audioset`` makes a tagger whose events can be counted: every class sits at a bias in [-4, -3] with
+    a narrow weight row (probabilities of a few percent, far below the low threshold) except ``active`` classes, chosen by
+    ``head_seed``, whose rows are ``head_scale`` wide around a bias near 0 - their probabilities swing across both
+    thresholds as the GRU state moves."""
+    out = {}
+    p = prefix + "bn0"
+    _bn(p, 64, out, seed)
+    out[p + ".running_mean"] = _uniform(p + ".running_mean", (64,), -30.0, -20.0, seed)
+    out[p + ".running_var"] = _uniform(p + ".running_var", (64,), 25.0, 40.0, seed)
+    for b in range(4):
+        cin, cout = SED_CHANNELS[b], SED_CHANNELS[b + 1]
+        for j, ci in ((1, cin), (2, cout)):
+            k = f"{prefix}conv_block{b + 1}.conv{j}.weight"
+            # avg + max pooling about doubles the scale of what it pools: the layer behind every pool is drawn half as
+            # wide, so that activations stay O(1) from block to block as a trained network's do
+            gain = 0.5 if (j == 1 and b > 0) else 1.0
+            out[k] = _normal(k, (cout, ci, 3, 3), gain * math.sqrt(2.0 / (9 * ci)), seed)
+            _bn(f"{prefix}conv_block{b + 1}.bn{j}", cout, out, seed)
+    out[prefix + "fc1.weight"] = _normal(prefix + "fc1.weight", (512, 512), 0.5 * math.sqrt(2.0 / 512), seed)
+    out[prefix + "fc1.bias"] = _uniform(prefix + "fc1.bias", (512,), -0.05, 0.05, seed)
+    for suf in ("", "_reverse"):
+        k = f"{prefix}rnn.weight_ih_l0{suf}"
+        out[k] = _normal(k, (768, 512), 1.0 / math.sqrt(512), seed)
+        k = f"{prefix}rnn.weight_hh_l0{suf}"
+        out[k] = _normal(k, (768, 256), 1.0 / math.sqrt(256), seed)
+        for b in ("bias_ih", "bias_hh"):
+            k = f"{prefix}rnn.{b}_l0{suf}"
+            out[k] = _uniform(k, (768,), -0.1, 0.1, seed)
+    out.update(sed_head_state(prefix, classes_num, seed if head_seed is None else head_seed, head_scale, active))
+    return out
+
+
+def sed_head_state(prefix, classes_num, head_seed, head_scale=5.0, active=3):
+    """``fc_audioset`` of ``sed_state`` alone (tests/golden/make_golden_sed.py searches its draws)."""
+    k = prefix + "fc_audioset.weight"
+    w = _normal(k, (classes_num, 512), 0.5 / math.sqrt(512), head_seed)
+    bias = _uniform(prefix + "fc_audioset.bias", (classes_num,), -4.0, -3.0, head_seed)
+    rows = _rng(prefix + "fc_audioset.active", head_seed).choice(classes_num, size=min(active, classes_num), replace=False)
+    w[rows] *= np.float32(head_scale / 0.5)
+    bias[rows] = _uniform(prefix + "fc_audioset.active_bias", (len(rows),), -0.5, 0.5, head_seed)
+    return {k: w, prefix + "fc_audioset.bias": bias}
+
+
+def cnn14rnn_tempattn_state(vocab_size=4981, seed=BASE_SEED, sed=None, **decoder):
+    """State dict of ``Cnn14RnnTempAttnGruModel`` (hf_wrapper.py:1897-1940): ``cap_model.encoder.cnn`` / ``.rnn`` (Cnn14 +
+    3 bi-GRU layers), ``cap_model.decoder`` (TemporalBahAttnDecoder; ``decoder``: its shape keywords) and ``sed_model``
+    (``sed``: keywords of ``sed_state``)."""
+    out = {}
+    out.update(cnn14_state("cap_model.encoder.cnn.", seed))
+    out.update(gru_state("cap_model.encoder.rnn.", 2048, 256, 3, seed))
+    out.update(bah_decoder_state("cap_model.decoder.", vocab_size=vocab_size, temporal=True, seed=seed, **decoder))
+    out.update(sed_state("sed_model.", seed=seed, **(sed or {})))
+    return out
+
+
 def cnn14rnn_trm_state(vocab_size=4368, seed=BASE_SEED):
     """Full state dict of the Cnn14Rnn-Trm captioner."""
     out = {}

@@ -538,6 +538,36 @@ int ac_bah_beam_gather(const int* src_row, const int* active_before, const float
                        const float* step_weight, const float* hist_in, float* hist_out, int B, int beam, int d, int Tm,
                        int max_len, int t, void* stream);
 
+/* ---- sound-event tagger (Cnn8rnnSedModel, hf_wrapper.py:1791-1859; csrc/sed.hip) ------------------------------------
+ * The tagger's convolutions run on the Cnn14 conv kernels above in mode 0; these entries are what they lack.
+ *
+ * avg_pool + max_pool of ConvBlock.forward(pool_type="avg+max"), hf_wrapper.py:1212-1215, over a (ph, 2) window (time, mel),
+ * ph = 2 or 1, on the row-padded channels-last layout: in [B*Hp][W][C] f32 -> out [B*Hp_out][W/2][C] f32.  Output rows
+ * h < H / ph (floor) hold avg + max of their window; rows H / ph <= h < Hp_out are written as zeros (the next conv's zero
+ * padding: an odd last input row does not reach them).  mean_w != 0 (ph = 1 only; Hp_out unused): the pool is followed by
+ * the mean over the W/2 pooled columns (hf_wrapper.py:1840-1842), out dense [B][H][C].  C % 4 == 0 (16-byte accesses), W
+ * even, Hp >= H, Hp_out >= H / ph, in / out 16-byte aligned. */
+int ac_pool_avgmax(const float* in, float* out, int B, int Hp, int H, int W, int C, int ph, int Hp_out, int mean_w,
+                   void* stream);
+/* prob = clamp(sigmoid(x + bias), 1e-7, 1) (hf_wrapper.py:1848) over x [rows][C]; bias [C] or NULL; pre (may be NULL)
+ * receives the pre-activation x + bias. */
+int ac_sed_head(const float* x, const float* bias, float* pre, float* prob, long rows, int C, void* stream);
+/* Cnn8rnnSedModel.forward's host post-processing on the device: double_threshold(framewise, high, low, n_connect) followed
+ * by decode_with_timestamps(., time_resolution) (hf_wrapper.py:89-216), where framewise is prob [B][S][C] with every segment
+ * repeated `ratio` times and the last one stretched to frames_num >= S * ratio (interpolate + pad_framewise_output,
+ * hf_wrapper.py:54-87) - an array this call never forms.  Pass 1, per (clip, class): runs of p > low (f32, strict) that
+ * contain a p > high, merged when the gap between two is <= n_connect frames, as (class, onset frame, offset frame).  Pass 2,
+ * per clip: segments_to_temporal_tag over all ordered pairs of segments of different classes in the reference's float64
+ * arithmetic (t = frame * time_resolution, overlap = e_j - s_k against thre * min(e_j - s_j, e_k - s_k), no contraction),
+ * leaving early once both flags are set.  tags [B] int32 = 2 * after + while (-1: the segment list overflowed, which the
+ * workspace's worst-case size C * ceil(S / 2) per clip rules out).  Pass 2 is quadratic in a clip's segments: a few
+ * hundred segments are microseconds, the (unphysical) worst case of every class alternating in step is seconds.
+ * rule: HOST pointer to two doubles {time_resolution, thre} (0.01 and 0.5 in the reference), read before the call returns.
+ * workspace: ac_sed_tag_workspace_bytes(B, S, C) bytes, 16-byte aligned; the call clears what it needs. */
+long ac_sed_tag_workspace_bytes(int B, int S, int C);
+int ac_sed_temporal_tag(const float* prob, int B, int S, int C, int frames_num, int ratio, float high, float low,
+                        int n_connect, const double* rule, void* workspace, long workspace_bytes, int* tags, void* stream);
+
 /* ================================== training step ==================================
  * The reference trains GRU + decoder on the frozen Cnn14 with scheduled sampling: step t runs the decoder on a
  * (N, t+1) prefix and keeps the last position's logit (base.py:131-137,152-199, transformer_model.py:34-57).  The
