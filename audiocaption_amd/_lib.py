@@ -39,6 +39,12 @@ class AcBahWeights(ctypes.Structure):
                                        "fc_w", "fc_b", "ctx_w", "ctx_b", "cls_w", "cls_b")]
 
 
+class AcBahGrads(ctypes.Structure):
+    """ac_bah_grads: where ac_bah_train_backward adds the gradient of each tensor of AcBahWeights."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("emb", "temb", "w_ih", "w_hh", "b_ih", "b_hh", "attn_w", "attn_b", "attn_v",
+                                               "fc_w", "fc_b", "ctx_w", "ctx_b", "cls_w", "cls_b")]
+
+
 _I, _L, _F, _P = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 _U64 = ctypes.c_ulonglong
 _WP = ctypes.POINTER(AcTrmWeights)
@@ -108,6 +114,12 @@ SIGNATURES = {
     "ac_bah_greedy": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_bah_sample": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
     "ac_bah_beam_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    # its training forward and backward (csrc/attn_gru_train.hip)
+    "ac_bah_train_workspace_floats": (_L, [_BP, _I, _I, _I]),
+    "ac_bah_train_forward": (_I, [_BP, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  _P]),
+    "ac_bah_train_backward": (_I, [_BP, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),
+    "ac_bah_mean_lens_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     # sound-event tagger (csrc/sed.hip)
     "ac_pool_avgmax": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ac_sed_head": (_I, [_P, _P, _P, _P, _L, _I, _P]),

@@ -17,8 +17,15 @@ Two quirks of the reference's beam search are kept:
 * a clip exits early when its finished count EQUALS ``beam_size`` (base.py:318-323) - a clip that finishes two beams in the
   step that takes it past ``beam_size`` searches on to ``max_length``.
 
-Not on this path (NotImplementedError): ``sample_method="dbs"``, ``mode="train"``, ``forward_async``; ``ScstWrapper`` and
-``EnsembleModel`` take ``TransformerModel`` members only.
+``mode="train"`` over a ``CrnnEncoder`` (``freeze_cnn=True``, ``freeze_cnn_bn=True``, GRU hidden 256) runs the reference's
+scheduled-sampling forward (base.py:131-208 with attn_model.py:34-65; one ``random.random()`` per step, every step run,
+``seq`` the arg-max of every step) through ``train_attn_gru.AttnGruTrainEngine`` and returns ``seq`` and
+``sampled_logprob`` (CPU), ``logit`` (N, T, V) attached to autograd by one bridge node, ``embed``, ``attn_weight``
+(N, Tm, T), ``state`` and the encoder's ``attn_emb_len``; in ``eval()`` or under ``no_grad`` the logits are plain tensors.
+
+Not on this path (NotImplementedError): ``sample_method="dbs"``, ``mode="train"`` over any other encoder, ``forward_async``,
+the fused ``TrainEngine.step`` and knowledge distillation for these models; ``ScstWrapper`` and ``EnsembleModel`` take
+``TransformerModel`` members only.
 """
 import ctypes
 
@@ -43,8 +50,10 @@ class Seq2SeqAttnModel(CaptionModel):
 
     def forward(self, input_dict):
         if input_dict["mode"] == "train":
-            raise NotImplementedError(f"{type(self).__name__}: mode='train' is not on the HIP path (inference only; the "
-                                      "training step covers TransformerModel)")
+            # the whole training forward (frozen Cnn14, bi-GRU, scheduled-sampling decoder) is one engine call; ``logit``
+            # comes back attached to autograd by a single bridge node (audiocaption_amd/train_attn_gru.py)
+            from .train_attn_gru import train_forward
+            return train_forward(self, input_dict)
         return super().forward(input_dict)
 
     def forward_async(self, input_dict, pair=None):

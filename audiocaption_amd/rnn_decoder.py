@@ -7,9 +7,14 @@ The nn modules own the parameters only; the arithmetic runs in csrc/attn_gru.hip
 (``ac_bah_step_logits``) with the reference's dict contract; the searches of ``attn_model.py`` call ``memory`` once per batch
 and then ``greedy`` / ``sample`` (one C call each) or ``step`` (beam search).
 
+Training (csrc/attn_gru_train.hip): ``train_forward`` runs the scheduled-sampling forward of the reference's
+``stepwise_forward`` for ``mode="train"`` (base.py:152-208, attn_model.py:34-65) in one C call and keeps what
+``train_backward`` - the backward through time, one C call - needs.  The constructor's ``dropout`` (``in_dropout`` on the
+step's input embedding) takes effect when ``self.training`` is set: counter-hash masks at site ``train.OP_BAH_IN``,
+regenerated in the backward.  The models of ``attn_model.py`` reach both through ``train_attn_gru.AttnGruTrainEngine``.
+
 Built: ``rnn_type="GRU"``, ``num_layers=1``, unidirectional; emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim each a
-multiple of 32 up to 1024; vocab_size <= 16384.  Anything else raises NotImplementedError in the constructor.  Inference
-only: dropout is the identity.
+multiple of 32 up to 1024; vocab_size <= 16384.  Anything else raises NotImplementedError in the constructor.
 """
 import ctypes
 
@@ -172,6 +177,108 @@ class BahAttnCatFcDecoder(RnnDecoder):
     def sample(self, mem, tags, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed):
         """The whole sampled search in one C call (``ac_bah_sample``): the sampler and Philox counters of ``ac_trm_sample``."""
         return self._search(mem, tags, start_idx, end_idx, pad_idx, (method, k, top_p, temp, seed))
+
+    # ---- training ------------------------------------------------------------------------------------------
+    GRAD_FIELDS = (("emb", "word_embedding.weight"), ("temb", "temporal_embedding.weight"), ("w_ih", "model.weight_ih_l0"),
+                   ("w_hh", "model.weight_hh_l0"), ("b_ih", "model.bias_ih_l0"), ("b_hh", "model.bias_hh_l0"),
+                   ("attn_w", "attn.h2attn.weight"), ("attn_b", "attn.h2attn.bias"), ("attn_v", "attn.v"),
+                   ("fc_w", "fc_proj.weight"), ("fc_b", "fc_proj.bias"), ("ctx_w", "ctx_proj.weight"),
+                   ("ctx_b", "ctx_proj.bias"), ("cls_w", "classifier.weight"), ("cls_b", "classifier.bias"))
+
+    def grad_struct(self, address_of):
+        """ac_bah_grads whose fields are ``address_of(parameter name)`` (an int): where ``train_backward`` adds."""
+        g = _lib.AcBahGrads()
+        for field, name in self.GRAD_FIELDS:
+            if field != "temb" or self.n_tags:
+                setattr(g, field, ctypes.c_void_p(address_of(name)))
+        return g
+
+    def train_forward(self, attn_emb, fc_emb, attn_emb_len, cap, use_cap, tags=None, start_idx=1, dropout_seed=0,
+                      seed_dev=None):
+        """The training forward over T = cap.size(1) - 1 steps (``ac_bah_train_forward``; no host synchronisation).
+        ``attn_emb`` (N, Tm, A), ``fc_emb`` (N, F) and ``cap`` (N, T + 1, int64) on the device; ``attn_emb_len``: host values
+        or an int32 device tensor; ``use_cap``: the T scheduled-sampling coins, drawn by the caller (1: the step takes
+        ``cap[:, t]``; 0: <start> at t == 0, else the arg-max of step t - 1); ``tags``: int32 (N,) on the device for a temporal
+        decoder.  ``in_dropout`` is active when ``self.training``: the mask of site ``train.OP_BAH_IN`` for the base seed
+        ``dropout_seed`` - or, with ``seed_dev`` (the address of a device word holding the base seed), for that word.
+        Returns seq (int64), logit (N, T, V), sampled_logprob, embed (N, T, d), attn_weight (N, Tm, T), state (1, N, d) on
+        the device, and under "saved" what ``train_backward`` takes."""
+        from .train import OP_BAH_IN
+        lib = _lib.load()
+        w = self.weights()
+        attn_emb, fc_emb = f32c(attn_emb), f32c(fc_emb)
+        ptr(attn_emb), ptr(fc_emb), ptr(cap)
+        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
+            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
+                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        B, Tm, _ = attn_emb.shape
+        if Tm > MAX_FRAMES:
+            raise NotImplementedError(f"{Tm} frames of audio memory: the attention kernels hold at most {MAX_FRAMES}")
+        if cap.dtype != torch.int64 or cap.dim() != 2 or cap.shape[0] != B or cap.shape[1] < 2 or not cap.is_contiguous():
+            raise ValueError(f"cap must be a contiguous int64 ({B}, T + 1) tensor with T >= 1")
+        T = cap.shape[1] - 1
+        use_cap = [int(bool(u)) for u in use_cap]
+        if len(use_cap) != T:
+            raise ValueError(f"use_cap holds {len(use_cap)} coins for {T} steps")
+        if (tags is None) != (self.n_tags == 0):
+            raise ValueError("tags: required by a temporal decoder, refused by a plain one")
+        dev = attn_emb.device
+        lens = attn_emb_len if (torch.is_tensor(attn_emb_len) and attn_emb_len.is_cuda and attn_emb_len.dtype == torch.int32) \
+            else K.upload(attn_emb_len, dev, torch.int32)
+        n = lib.ac_bah_train_workspace_floats(ctypes.byref(w), B, Tm, T)
+        if n <= 0:
+            raise _lib.HipLibraryError("ac_bah_train_workspace_floats rejected the decoder configuration")
+        f32 = dict(device=dev, dtype=torch.float32)
+        p = float(self.in_dropout.p) if self.training else 0.0
+        if seed_dev is None:       # the kernels' effective seed is drop_seed + (*seed_dev << 16)
+            seed = ((int(dropout_seed) << 16) + OP_BAH_IN) & 0xFFFFFFFFFFFFFFFF
+        else:
+            seed = OP_BAH_IN
+        out = {"seq": torch.empty(B, T, device=dev, dtype=torch.int64), "logit": torch.empty(B, T, self.vocab_size, **f32),
+               "sampled_logprob": torch.empty(B, T, **f32), "embed": torch.empty(B, T, self.d_model, **f32),
+               "attn_weight": torch.empty(B, Tm, T, **f32), "state": torch.empty(1, B, self.d_model, **f32)}
+        saved = {"w": w, "attn_emb": attn_emb, "fc_emb": fc_emb, "len": lens, "B": B, "Tm": Tm, "T": T, "p": p, "seed": seed,
+                 "seed_dev": seed_dev, "ws": torch.empty(n, **f32)}
+        check(lib.ac_bah_train_forward(
+            ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), ptr(lens), ptr(cap), cap.shape[1], (ctypes.c_int * T)(*use_cap),
+            ptr(tags), B, Tm, T, int(start_idx), p, seed, seed_dev, ptr(out["seq"]), ptr(out["logit"]),
+            ptr(out["sampled_logprob"]), ptr(out["embed"]), ptr(out["attn_weight"]), ptr(out["state"]), ptr(saved["ws"]),
+            stream()), "ac_bah_train_forward")
+        out["saved"] = saved
+        return out
+
+    def train_backward(self, saved, dlogit, grads=None, d_attn_emb=None, d_fc_emb=None):
+        """Backward through time of the ``train_forward`` that returned ``saved`` (``ac_bah_train_backward``), given
+        ``dlogit`` (N, T, V; a tensor or a device address).  ``grads``: an ``ac_bah_grads`` (``grad_struct``) the gradients
+        are ADDED to; None: fresh zeroed tensors, returned by parameter name.  ``d_attn_emb`` (N, Tm, A) / ``d_fc_emb``
+        (N, F): tensors or device addresses that are WRITTEN; None: fresh tensors.
+        Returns (grads by name or None, d_attn_emb, d_fc_emb)."""
+        lib = _lib.load()
+        B, Tm, T = saved["B"], saved["Tm"], saved["T"]
+        dev = saved["attn_emb"].device
+        named = None
+        if grads is None:
+            params = dict(self.named_parameters())
+            named = {name: torch.zeros_like(params[name], dtype=torch.float32).contiguous()
+                     for field, name in self.GRAD_FIELDS if field != "temb" or self.n_tags}
+            grads = self.grad_struct(lambda name: named[name].data_ptr())
+        if torch.is_tensor(dlogit):
+            dlogit = f32c(dlogit)
+            if tuple(dlogit.shape) != (B, T, self.vocab_size):
+                raise ValueError(f"dlogit {tuple(dlogit.shape)}: expected {(B, T, self.vocab_size)}")
+        if d_attn_emb is None:
+            d_attn_emb = torch.empty(B, Tm, self.attn_emb_dim, device=dev, dtype=torch.float32)
+        if d_fc_emb is None:
+            d_fc_emb = torch.empty(B, self.fc_emb_dim, device=dev, dtype=torch.float32)
+
+        def P(x):
+            return ptr(x) if torch.is_tensor(x) else ctypes.c_void_p(x)
+
+        check(lib.ac_bah_train_backward(
+            ctypes.byref(saved["w"]), ctypes.byref(grads), ptr(saved["attn_emb"]), ptr(saved["fc_emb"]), ptr(saved["len"]),
+            P(dlogit), B, Tm, T, saved["p"], saved["seed"], saved["seed_dev"], P(d_attn_emb), P(d_fc_emb), ptr(saved["ws"]),
+            stream()), "ac_bah_train_backward")
+        return named, d_attn_emb, d_fc_emb
 
     def _tags(self, input_dict, n):
         return None

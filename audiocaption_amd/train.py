@@ -22,7 +22,8 @@ row space with every pass run on the words drawn so far, feeding the same backwa
 
 ``TrainEngine`` is the fast path (``engine.step(batch)``); ``TransformerModel.forward`` with ``mode="train"`` goes
 through the same engine and returns ``logit`` attached to torch.autograd by ONE bridge node, so the reference's
-runner (``loss.backward()``, any torch optimizer) works unchanged.
+runner (``loss.backward()``, any torch optimizer) works unchanged.  The attention-GRU captioners train through
+``train_attn_gru.AttnGruTrainEngine``, this engine with the decoder half replaced (autograd route only).
 """
 import os
 import random
@@ -40,6 +41,7 @@ OP_GRU_LAYER = 10
 OP_MEM = 20
 OP_EMB_A, OP_EMB_B = 21, 22
 OP_LAYER = 30
+OP_BAH_IN = 40       # in_dropout of the attention-GRU decoder's training forward (train_attn_gru.py)
 # Transformer encoder (Cnn14TransformerEncoder): attn_proj dropout, then per layer l
 # OP_ENC_LAYER + 10 * l + {0: self-attention P, 1: dropout1, 2: feed-forward dropout, 3: dropout2}
 OP_ENC_PROJ = 100
@@ -307,19 +309,7 @@ class TrainEngine:
             raise NotImplementedError(
                 "TrainEngine: built for the reference's training recipe, CrnnEncoder or Cnn14TransformerEncoder with "
                 "freeze_cnn=True, freeze_cnn_bn=True (cnn14rnn_trm.yaml:9-13); the backward through the Cnn14 is not built")
-        dec = model.decoder
-        if self.enc_kind == "trm":
-            trm = enc.trm
-            if dec.d_model != D or dec.nhead * 64 != D or trm.d_model != D or trm.nhead * 64 != D:
-                raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 (decoder and TransformerEncoder) only")
-            self.enc_width = trm.d_model
-            if dec.attn_emb_dim != self.enc_width:
-                raise NotImplementedError(f"TrainEngine: decoder attn_emb_dim {dec.attn_emb_dim} != TransformerEncoder "
-                                          f"d_model {self.enc_width}")
-        else:
-            if dec.d_model != D or dec.nhead * 64 != D or model.encoder.rnn.hidden_size != H:
-                raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 / GRU hidden 256 only")
-            self.enc_width = 2 * H
+        self.enc_width = self._check_widths(model)
         self.model = model
         self.lib = _lib.load()
         self.flat = None
@@ -340,6 +330,21 @@ class TrainEngine:
         self._pw_table = None  # device copy of the pack records (ac_pw_gemm_pack_table)
         self._pw_hold = []     # tables captured graphs may still reference
         self.gru_algo = os.environ.get("AUDIOCAPTION_GRU_ALGO", "split")   # forward recurrence kernel (see RnnEncoder)
+
+    def _check_widths(self, model):
+        """Refuses the widths the kernels are not built for; returns the encoder's output width."""
+        enc, dec = model.encoder, model.decoder
+        if self.enc_kind == "trm":
+            trm = enc.trm
+            if dec.d_model != D or dec.nhead * 64 != D or trm.d_model != D or trm.nhead * 64 != D:
+                raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 (decoder and TransformerEncoder) only")
+            if dec.attn_emb_dim != trm.d_model:
+                raise NotImplementedError(f"TrainEngine: decoder attn_emb_dim {dec.attn_emb_dim} != TransformerEncoder "
+                                          f"d_model {trm.d_model}")
+            return trm.d_model
+        if dec.d_model != D or dec.nhead * 64 != D or model.encoder.rnn.hidden_size != H:
+            raise NotImplementedError("TrainEngine: d_model 256 / head_dim 64 / GRU hidden 256 only")
+        return 2 * H
 
     # ---- small launch helpers (raw addresses; s = stream handle) ------------------------------------------
     def _hooked(self, M, N, K, launch):
@@ -630,6 +635,7 @@ class TrainEngine:
         # one draw per step, exactly the reference's call pattern (transformer_model.py:44)
         use_cap = [1] * T if teacher_forcing else [int(random.random() < ss_ratio) for _ in range(T)]
         use_cap = input_dict.get("_use_cap", use_cap)
+        st["use_cap"] = [int(u) for u in use_cap]
         # passes whose prefix is the model's own prediction (pass 0 always starts from <start> alone)
         st["free_ts"] = [] if teacher_forcing else [t for t in range(1, T) if not int(use_cap[t])]
         S = st["lay"]["S"]

@@ -1,0 +1,146 @@
+"""Training of the attention-GRU captioners (``Seq2SeqAttnModel`` / ``TemporalSeq2SeqAttnModel`` over ``CrnnEncoder``) on
+the MI355X path: ``TrainEngine`` with the decoder half replaced.
+
+The encoder half is the engine's own - the frozen Cnn14 forward, the 3-layer bi-GRU forward with saved gates
+(``_launch_forward_gru``) and its backward through time from ``gru_dout`` (``_launch_backward_gru``), ``FlatParams``, the
+``_cnn_attn`` test hook - under the engine's own limits: ``freeze_cnn=True``, ``freeze_cnn_bn=True``, GRU hidden 256.
+Between the two sits the decoder of csrc/attn_gru_train.hip (``rnn_decoder.BahAttnCatFcDecoder.train_forward`` /
+``train_backward``): ``fc_emb`` is the mean of the GRU output over each clip's valid frames (``ac_mean_with_lens``), and in
+the backward the decoder's ``d fc_emb`` goes back into every valid frame (``ac_bah_mean_lens_bwd``) on top of its
+``d attn_emb``; the total lands in ``gru_dout``.
+
+``model(input_dict)`` with ``mode="train"`` (``train_forward`` below) returns ``logit`` attached to autograd by one
+bridge node, so the reference runner's ``loss.backward()``, ``clip_grad_norm_`` and any torch optimiser - or
+``optim.FusedAdam`` - work unchanged.  The scheduled-sampling coins follow the reference (attn_model.py:44): one
+``random.random()`` per step in step order, at ``ss_ratio == 1`` as well, all drawn on the host before anything is launched.
+
+Not built for these models: the fused ``step`` (device-side loss, clip, Adam, graph capture, the split all-reduce), the
+SCST ``rollout`` and the Cnn14 look-ahead.
+"""
+import random
+
+import torch
+
+from . import _lib
+from . import kernels as K
+from ._lib import check
+from .rnn_decoder import check_temporal_tag
+from .train import H, OP_CNN_BLOCK, TrainEngine, _TrainBridge
+
+
+class AttnGruTrainEngine(TrainEngine):
+
+    def _check_widths(self, model):
+        from .attn_model import Seq2SeqAttnModel
+        if not isinstance(model, Seq2SeqAttnModel):
+            raise NotImplementedError("AttnGruTrainEngine trains Seq2SeqAttnModel / TemporalSeq2SeqAttnModel")
+        dec = model.decoder
+        if self.enc_kind != "rnn" or model.encoder.rnn.hidden_size != H:
+            raise NotImplementedError("AttnGruTrainEngine: mode='train' needs a CrnnEncoder with freeze_cnn=True, "
+                                      "freeze_cnn_bn=True and GRU hidden 256")
+        if dec.attn_emb_dim != 2 * H or dec.fc_emb_dim != 2 * H:
+            raise NotImplementedError(f"AttnGruTrainEngine: attn_emb_dim {dec.attn_emb_dim} / fc_emb_dim {dec.fc_emb_dim} do "
+                                      f"not fit the bi-GRU's {2 * H} features")
+        return 2 * H
+
+    def _prepare(self, input_dict, rollout=False):
+        if rollout:
+            raise NotImplementedError("AttnGruTrainEngine: the SCST rollout covers TransformerModel only")
+        T = input_dict["cap"].shape[1] - 1
+        tags = None
+        if self.model.decoder.n_tags:
+            tags = check_temporal_tag(input_dict.get("temporal_tag"), input_dict["cap"].shape[0])
+        # one coin per step, in step order, whatever ss_ratio is: the engine draws them unless ss_ratio == 1, where the
+        # reference's attention model still consumes the stream (attn_model.py:44) and every coin comes out 1
+        if input_dict["ss_ratio"] == 1:
+            for _ in range(T):
+                random.random()
+        st = super()._prepare(input_dict)     # st["use_cap"]: the T coins
+        st["tags"] = None if tags is None else K.upload(tags, st["cap"].device, torch.int32)
+        return st
+
+    def _launch_forward(self, st, free=True):
+        model, lib = self.model, self.lib
+        enc, dec = model.encoder, model.decoder
+        s = _lib.stream()
+        self._phase = "forward"
+        ws = st["ws"]
+        N, Tq, p_cnn = st["N"], st["Tq"], st["p_cnn"]
+        small = st["small"]
+        self._seed_ptr = small.data_ptr()
+        self._pw_pack_all(s)
+        if st["cnn_attn_in"] is not None:
+            cnn_attn = st["cnn_attn_in"]
+        else:
+            cnn_attn = enc.cnn.encode(st["wav"], dropout=(p_cnn, OP_CNN_BLOCK, self._seed_ptr) if p_cnn > 0 else None,
+                                      specaug=st["specaug"], train=True)
+        st["cnn_attn"] = cnn_attn
+        st["gru"], _ = self._launch_forward_gru(st, cnn_attn)
+        A = self.enc_width
+        # the last GRU layer's output is the audio memory (no dropout behind the last layer); all T' frames are kept, the
+        # frames beyond a clip's length are zero and masked
+        attn_emb = ws.tensor(f"gru_out{enc.rnn.num_layers - 1}")[:N * Tq * A].view(N, Tq, A)
+        lens = small[2:2 + N]
+        ws.f("bah_fc", N, A)
+        fc_emb = ws.tensor("bah_fc")[:N * A].view(N, A)
+        check(lib.ac_mean_with_lens(attn_emb.data_ptr(), lens.data_ptr(), fc_emb.data_ptr(), N, Tq, A, 0, s),
+              "ac_mean_with_lens")
+        was = dec.training
+        dec.training = not st["eval"]     # a model in eval(): every dropout probability 0, as TrainEngine does
+        try:
+            st["bah"] = dec.train_forward(attn_emb, fc_emb, lens, st["cap"], st["use_cap"], st.get("tags"), model.start_idx,
+                                          seed_dev=self._seed_ptr)
+        finally:
+            dec.training = was
+
+    def _outputs(self, st):
+        out = {k: v for k, v in st["bah"].items() if k != "saved"}
+        out["attn_emb_len"] = st["lens_host"]
+        # the reference's memory is as long as the longest clip (pad_packed_sequence)
+        out["attn_weight"] = out["attn_weight"][:, :int(st["lens_host"].max())]
+        return out
+
+    def _launch_backward(self, sv, dl, part="all"):
+        if part != "all":
+            raise NotImplementedError("AttnGruTrainEngine: the backward runs in one piece")
+        lib, fp, dec = self.lib, self.flat, self.model.decoder
+        s = _lib.stream()
+        self._phase = "backward"
+        ws = sv["ws"]
+        N, Tq, A = sv["N"], sv["Tq"], self.enc_width
+        fp.grad.zero_()
+        self._seed_ptr = sv["small"].data_ptr()
+        dout = ws.f("gru_dout", N * Tq, A)        # where _launch_backward_gru reads d(loss)/d(GRU output)
+        d_fc = ws.f("bah_dfc", N, A)
+        saved = sv.pop("bah")["saved"]
+        dec.train_backward(saved, dl, dec.grad_struct(lambda name: fp.g("decoder." + name)), dout, d_fc)
+        check(lib.ac_bah_mean_lens_bwd(d_fc, saved["len"].data_ptr(), dout, N, Tq, A, A, s), "ac_bah_mean_lens_bwd")
+        self._launch_backward_gru(sv)
+
+    def rollout(self, input_dict):
+        raise NotImplementedError("AttnGruTrainEngine: the SCST rollout covers TransformerModel only")
+
+    def step(self, *args, **kwargs):
+        raise NotImplementedError("AttnGruTrainEngine: the fused step (device-side loss, clip, Adam, graph capture) covers "
+                                  "TransformerModel only; use model(input_dict) with loss.backward() and an optimiser")
+
+    def prefetch_cnn(self, input_dict, seed):
+        raise NotImplementedError("AttnGruTrainEngine: the Cnn14 look-ahead belongs to the fused step")
+
+
+def train_forward(model, input_dict):
+    """``Seq2SeqAttnModel.forward`` for ``mode == "train"``."""
+    from .crnn_trm_encoder import CrnnEncoder
+    if not isinstance(model.encoder, CrnnEncoder):
+        raise NotImplementedError(f"{type(model).__name__}: mode='train' is on the HIP path over a CrnnEncoder only (frozen "
+                                  f"Cnn14 + bi-GRU), not over {type(model.encoder).__name__}")
+    engine = getattr(model, "_train_engine", None)
+    if engine is None:
+        engine = model._train_engine = AttnGruTrainEngine(model)
+    out = engine.forward(input_dict)
+    out["seq"] = out["seq"].cpu()                            # the reference keeps seq and sampled_logprob on the CPU
+    out["sampled_logprob"] = out["sampled_logprob"].cpu()
+    # a model in eval() or under no_grad: plain logits, no bridge node
+    if model.training and torch.is_grad_enabled():
+        out["logit"] = _TrainBridge.apply(engine, out["logit"], *engine.flat.params)
+    return out

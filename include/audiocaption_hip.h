@@ -538,6 +538,44 @@ int ac_bah_beam_gather(const int* src_row, const int* active_before, const float
                        const float* step_weight, const float* hist_in, float* hist_out, int B, int beam, int d, int Tm,
                        int max_len, int t, void* stream);
 
+/* ---- training of the attention-GRU decoder (base.py:131-208 with attn_model.py:34-65; csrc/attn_gru_train.hip) --------
+ * The same shapes as above, one row per clip, T = cap.size(1) - 1 steps; every step runs (no early stop).  Step t is the
+ * arithmetic of ac_bah_step_logits on the input word  use_cap[t] ? cap[b][t] : (t == 0 ? start_idx : seq[b][t - 1])  (the
+ * tag's embedding at t == 0 when tags != NULL), its embedding multiplied by in_dropout's mask: the counter hash of
+ * ac_dropout at element index (t * B + b) * E + e with (drop_p, drop_seed, seed_dev).  use_cap is a HOST array of T flags
+ * (the scheduled-sampling coins are drawn before anything is launched); cap is int64 [B][cap_ld] on the device, cap_ld >= T.
+ * Outputs, written in full: seq [B][T] int64 = the arg-max of every step (first index on ties), logit [B][T][V],
+ * logprob [B][T] = max(log_softmax(logit)), embed [B][T][d], attn_weight [B][Tm][T], state [B][d] after the last step.
+ * The workspace (ac_bah_train_workspace_floats(w, B, Tm, T) floats, 16-byte aligned; -1: configuration refused) keeps,
+ * per (step, clip), the state going in and coming out, W_h h and W_hh h + b_hh, the attention weights, the context, the
+ * GRU input, the gates and the input word; tanh(W_h h + ek) is recomputed by the backward, not kept. */
+long ac_bah_train_workspace_floats(const ac_bah_weights* w, int B, int Tm, int T);
+int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
+                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
+                         int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
+                         float* ws, void* stream);
+/* Where the backward ADDS the gradient of each tensor of the ac_bah_weights struct - same names and shapes (temb may be NULL when
+ * n_tags == 0).  The buffers may be slices of one flat gradient buffer; the caller clears them. */
+typedef struct {
+  float *emb, *temb, *w_ih, *w_hh, *b_ih, *b_hh, *attn_w, *attn_b, *attn_v, *fc_w, *fc_b, *ctx_w, *ctx_b, *cls_w, *cls_b;
+} ac_bah_grads;
+/* Backward through time of the forward whose workspace is ws (same w, attn_emb, fc_emb, mem_len, B, Tm, T and dropout
+ * arguments; the masks are regenerated), given dlogit [B][T][V].  Per step t = T-1 .. 0: the gate backward, dxin and dctx
+ * (exact-f32 products over the B rows), the attention backward - one workgroup per clip, which accumulates the clip's
+ * d attn_emb and d(key projection) over the steps by plain read-modify-write (a clip's rows belong to its workgroup and the
+ * steps run in stream order) - and the two products into dh_{t-1}.  Off the recurrence, once over all B T rows: dlogit W_cls,
+ * every weight gradient and bias column sum, the embedding scatter (word_embedding; temporal_embedding for the tag step).
+ * d_attn_emb [B][Tm][A] and d_fc_emb [B][F] are WRITTEN (not added to); frames at or beyond a clip's length get exactly 0. */
+int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* fc_emb,
+                          const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
+                          unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
+                          float* d_fc_emb, float* ws, void* stream);
+/* Backward of fc_emb = mean_with_lens(attn_emb)[:, :F] (rnn_encoder.py:44): d_attn_emb[b][t][c] += d_fc_emb[b][c] / lens[b]
+ * for t < lens[b], c < F <= A. */
+int ac_bah_mean_lens_bwd(const float* d_fc_emb, const int* lens, float* d_attn_emb, int B, int Tm, int A, int F,
+                         void* stream);
+
 /* ---- sound-event tagger (Cnn8rnnSedModel, hf_wrapper.py:1791-1859; csrc/sed.hip) ------------------------------------
  * The tagger's convolutions run on the Cnn14 conv kernels above in mode 0; these entries are what they lack.
  *
