@@ -118,6 +118,8 @@ SIGNATURES = {
     "ac_bah_train_workspace_floats": (_L, [_BP, _I, _I, _I]),
     "ac_bah_train_forward": (_I, [_BP, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P]),
+    "ac_bah_train_rollout": (_I, [_BP, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _L, _F, _U64, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _P]),
     "ac_bah_train_backward": (_I, [_BP, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),
     "ac_bah_mean_lens_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     # sound-event tagger (csrc/sed.hip)

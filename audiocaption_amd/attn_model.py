@@ -23,9 +23,13 @@ scheduled-sampling forward (base.py:131-208 with attn_model.py:34-65; one ``rand
 ``sampled_logprob`` (CPU), ``logit`` (N, T, V) attached to autograd by one bridge node, ``embed``, ``attn_weight``
 (N, Tm, T), ``state`` and the encoder's ``attn_emb_len``; in ``eval()`` or under ``no_grad`` the logits are plain tensors.
 
-Not on this path (NotImplementedError): ``sample_method="dbs"``, ``mode="train"`` over any other encoder, ``forward_async``,
-the fused ``TrainEngine.step`` and knowledge distillation for these models; ``ScstWrapper`` and ``EnsembleModel`` take
-``TransformerModel`` members only.
+Self-critical sequence training: ``rl_model.ScstWrapper`` wraps these models over a ``CrnnEncoder``.  Its greedy baseline is
+this file's greedy search (with ``_seq_on_device`` the result also carries ``seq_dev``, the decoder's device copy of the
+words); its sampled rollout is ``AttnGruTrainEngine.rollout``.
+
+Not on this path (NotImplementedError): ``sample_method="dbs"`` (the reference's own diverse beam search raises for both
+attention models), ``mode="train"`` and SCST over any other encoder, ``forward_async``, the fused ``TrainEngine.step`` and
+knowledge distillation for these models; ``EnsembleModel`` takes ``TransformerModel`` members only.
 """
 import ctypes
 
@@ -68,6 +72,8 @@ class Seq2SeqAttnModel(CaptionModel):
             forward_dict["n_best_size"] = input_dict.get("n_best_size", forward_dict["beam_size"])
         if input_dict.get("seed") is not None:
             forward_dict["seed"] = input_dict["seed"]
+        if input_dict.get("_seq_on_device"):      # ScstWrapper's baseline: the device copy of the words as well ("seq_dev")
+            forward_dict["_seq_on_device"] = True
         forward_dict.update(encoder_output_dict)
         return forward_dict
 
@@ -93,6 +99,8 @@ class Seq2SeqAttnModel(CaptionModel):
             res = dec.greedy(mem, tags, self.start_idx, self.end_idx, self.pad_idx)
         else:
             res = dec.sample(mem, tags, self.start_idx, self.end_idx, self.pad_idx, *sampler)
+        if input_dict.get("_seq_on_device"):
+            res["seq_dev"] = res["seq"]                          # the words where the decoder left them (int64)
         res["seq"] = res["seq"].cpu()                            # the reference keeps seq on the CPU (base.py:122)
         res["sampled_logprob"] = res["sampled_logprob"].cpu()    # CPU as in base.py:126
         return res

@@ -10,6 +10,8 @@
 //   bah_train_gate_kernel    GRU cell; keeps r, z, n and h_{t+1}
 //   logit[:, t] = h_{t+1} classifier^T + b                        GEMM
 //   bah_train_pick_kernel    seq[:, t] = arg-max (first index on ties), its log-probability
+// The SCST rollout (ac_bah_train_rollout) is the same chain with no caption: the pick is ac_scst_pick (the sampled or forced
+// word under the finished-row rule, into an int32 buffer) and step t > 0 feeds the word that step t - 1 stored there.
 // Kept per (step, clip): h_t, h_{t+1}, hg (the query projection W_h h and W_hh h + b_hh), the attention weights, the
 // context, xin, the gates, the input word.  tanh(q + ek) is NOT kept (B T Tm S floats): the backward recomputes it.
 //
@@ -86,6 +88,7 @@ struct TAttnP {
   const int* tags;                       // [B] at the tag step, null otherwise
   const long long* cap; long cap_ld;     // [B][cap_ld]
   const int64_t* seq;                    // [B][T]: the arg-max of the steps so far
+  const int* words; long words_ld;       // rollout: [B][words_ld], the words ac_scst_pick stored; null otherwise
   int* tok;                              // this step's [B]
   float *ctx, *xin, *w;                  // this step's [B][A], [B][2E], [B][Tm]
   float* attn_out;                       // weight of (clip b, frame tm) at attn_out + (b * Tm + tm) * T
@@ -114,8 +117,10 @@ __global__ __launch_bounds__(256) void bah_train_attn_kernel(TAttnP p) {
       src = p.temb + (size_t)g * p.E;
       code = -1 - g;
     } else {
-      long long wd = p.use_cap ? p.cap[(size_t)b * p.cap_ld + p.t]
-                               : (p.t == 0 ? (long long)p.start_idx : (long long)p.seq[(size_t)b * p.T + p.t - 1]);
+      long long wd;
+      if (p.words) wd = p.t == 0 ? (long long)p.start_idx : (long long)p.words[(size_t)b * p.words_ld + p.t - 1];
+      else wd = p.use_cap ? p.cap[(size_t)b * p.cap_ld + p.t]
+                          : (p.t == 0 ? (long long)p.start_idx : (long long)p.seq[(size_t)b * p.T + p.t - 1]);
       wd = wd < 0 ? 0 : (wd >= p.V ? p.V - 1 : wd);
       src = p.emb + (size_t)wd * p.E;
       code = (int)wd;
@@ -406,23 +411,22 @@ bool grads_ok(const ac_bah_weights* w, const ac_bah_grads* g) {
 
 #define BAH_TRY(call) do { if ((call) != AC_OK) return AC_ERR_LAUNCH; } while (0)
 
-}  // namespace
+// What the SCST rollout has in place of the caption and the arg-max pick
+struct Rollout {
+  int* seq;                          // [B][T] int32: the stored words (ac_scst_pick writes, the next step's word feed reads)
+  int* scratch;                      // [2 B]: ac_scst_pick's done and drawn
+  const int* forced; long forced_ld; // the caller's words instead of the draws, or null
+  const uint64_t* sample_seed_dev;
+  float temp;
+  int end_idx;
+};
 
-extern "C" {
-
-long ac_bah_train_workspace_floats(const ac_bah_weights* w, int B, int Tm, int T) {
-  if (!train_dims_ok(w, B, Tm, T, 0.f)) return -1;
-  return (long)train_carve(w, nullptr, B, Tm, T).total;
-}
-
-int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
-                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
-                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
-                         int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
-                         float* ws, void* stream) {
-  if (!train_dims_ok(w, B, Tm, T, drop_p) || !attn_emb || !fc_emb || !mem_len || !cap || cap_ld < T || !use_cap || !seq ||
-      !logit || !logprob || !embed || !attn_weight || !state || !ws || (w->n_tags == 0) != (tags == nullptr))
-    return AC_ERR_ARG;
+// The forward chain of T steps; the arguments have been checked.  ro == null: scheduled sampling on cap / the arg-max.
+int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                        const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
+                        int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
+                        const int64_t* seq_in, int64_t* seq, const Rollout* ro, float* logit, float* logprob, float* embed,
+                        float* attn_weight, float* state, float* ws, void* stream) {
   const int E = w->emb_dim, d = w->d_model, S = w->attn_size, A = w->attn_emb_dim, F = w->fc_emb_dim, V = w->vocab;
   hipStream_t s = (hipStream_t)stream;
   const TrainWs c = train_carve(w, ws, B, Tm, T);
@@ -445,9 +449,10 @@ int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const f
     TAttnP a;
     a.hg = hg; a.ld_hg = ld_hg; a.ek = c.ek; a.attn_emb = attn_emb; a.v = w->attn_v; a.mem_len = mem_len;
     a.emb = w->emb; a.temb = w->temb; a.tags = (t == 0 && w->n_tags) ? tags : nullptr;
-    a.cap = cap; a.cap_ld = cap_ld; a.seq = seq; a.tok = c.tok + r0;
+    a.cap = cap; a.cap_ld = cap_ld; a.seq = seq_in; a.tok = c.tok + r0;
+    a.words = ro ? ro->seq : nullptr; a.words_ld = T;
     a.ctx = ctx; a.xin = xin; a.w = c.w + r0 * Tm; a.attn_out = attn_weight + t; a.drop = drop;
-    a.use_cap = use_cap[t] != 0; a.t = t; a.T = T; a.B = B; a.start_idx = start_idx;
+    a.use_cap = ro ? 0 : use_cap[t] != 0; a.t = t; a.T = T; a.B = B; a.start_idx = start_idx;
     a.Tm = Tm; a.S = S; a.A = A; a.E = E; a.V = V; a.n_tags = w->n_tags;
     hipLaunchKernelGGL(bah_train_attn_kernel, dim3(B), dim3(256), 0, s, a);
     BAH_TRY(ac_check_launch());
@@ -460,14 +465,58 @@ int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const f
     hipLaunchKernelGGL(bah_train_gate_kernel, dim3((unsigned)(((long)B * d + 255) / 256)), dim3(256), 0, s, g);
     BAH_TRY(ac_check_launch());
     BAH_TRY(gemm(h_out, d, w->cls_w, d, w->cls_b, logit + (size_t)t * V, (long)T * V, B, V, d, stream));
-    hipLaunchKernelGGL(bah_train_pick_kernel, dim3(B), dim3(256), 0, s, logit + (size_t)t * V, (long)T * V, V, seq + t,
-                       logprob + t, (long)T);
-    BAH_TRY(ac_check_launch());
+    if (ro) {
+      BAH_TRY(ac_scst_pick(logit + (size_t)t * V, (long)T * V, B, V, ro->temp, ro->sample_seed_dev, t, ro->end_idx, ro->forced,
+                           ro->forced_ld, ro->scratch, ro->scratch + B, ro->seq, T, logprob, T, stream));
+    } else {
+      hipLaunchKernelGGL(bah_train_pick_kernel, dim3(B), dim3(256), 0, s, logit + (size_t)t * V, (long)T * V, V, seq + t,
+                         logprob + t, (long)T);
+      BAH_TRY(ac_check_launch());
+    }
   }
   if (hipMemcpyAsync(state, c.h_all + (size_t)T * B * d, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, s) !=
       hipSuccess)
     return AC_ERR_LAUNCH;
   return AC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long ac_bah_train_workspace_floats(const ac_bah_weights* w, int B, int Tm, int T) {
+  if (!train_dims_ok(w, B, Tm, T, 0.f)) return -1;
+  return (long)train_carve(w, nullptr, B, Tm, T).total;
+}
+
+int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
+                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
+                         int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
+                         float* ws, void* stream) {
+  if (!train_dims_ok(w, B, Tm, T, drop_p) || !attn_emb || !fc_emb || !mem_len || !cap || cap_ld < T || !use_cap || !seq ||
+      !logit || !logprob || !embed || !attn_weight || !state || !ws || (w->n_tags == 0) != (tags == nullptr))
+    return AC_ERR_ARG;
+  return train_forward_steps(w, attn_emb, fc_emb, mem_len, cap, cap_ld, use_cap, tags, B, Tm, T, start_idx, drop_p, drop_seed,
+                             seed_dev, seq, seq, nullptr, logit, logprob, embed, attn_weight, state, ws, stream);
+}
+
+int ac_bah_train_rollout(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const int* tags, int B, int Tm, int T, int start_idx, int end_idx, float temp,
+                         const uint64_t* sample_seed_dev, const int* forced, long forced_ld, float drop_p,
+                         unsigned long long drop_seed, const unsigned long long* seed_dev, int* seq, int* scratch,
+                         float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
+                         void* stream) {
+  if (T < 1 || !train_dims_ok(w, B, Tm, T, drop_p) || !attn_emb || !fc_emb || !mem_len || !sample_seed_dev || !seq ||
+      !scratch || !logit || !logprob || !embed || !attn_weight || !state || !ws || !isfinite(temp) || !(temp > 0.f) ||
+      (forced && forced_ld < T) || (w->n_tags == 0) != (tags == nullptr) ||
+      ac_sample_check(w->vocab, AC_SAMPLE_PLAIN, 0, 1.0f, temp) != AC_OK)
+    return AC_ERR_ARG;
+  Rollout ro;
+  ro.seq = seq; ro.scratch = scratch; ro.forced = forced; ro.forced_ld = forced_ld; ro.sample_seed_dev = sample_seed_dev;
+  ro.temp = temp; ro.end_idx = end_idx;
+  return train_forward_steps(w, attn_emb, fc_emb, mem_len, nullptr, 0, nullptr, tags, B, Tm, T, start_idx, drop_p, drop_seed,
+                             seed_dev, nullptr, nullptr, &ro, logit, logprob, embed, attn_weight, state, ws, stream);
 }
 
 int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* fc_emb,

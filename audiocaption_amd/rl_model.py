@@ -8,7 +8,8 @@ current keys.  For ``mode == "train"``:
 
 1. baseline: ``model.eval()``, no gradients, ``sample_method="greedy"`` - the inference path as it is - -> ``greedy_seqs``;
 2. rollout: ``model.train()``, ``sample_method="sample"``: the train-mode encoder and ``max_length`` decoder passes on the
-   words drawn so far (``TrainEngine.rollout``); a clip that has drawn ``<end>`` keeps emitting ``<end>``;
+   words drawn so far (``TrainEngine.rollout``; for the attention-GRU models ``max_length`` steps of the GRU decoder, each
+   on the word the step before drew, ``AttnGruTrainEngine.rollout``); a clip that has drawn ``<end>`` keeps emitting ``<end>``;
    ``sampled_logprob[n, t] = log_softmax(logit[n, t])[w] / temp``;
 3. reward: ``score(sampled) - score(greedy)`` per clip.  With the built-in ``audiocaption_amd.Cider`` as ``scorer`` it is
    computed on the device from the word ids, both sets read where the decoders left them (cider.py ``score_ids``,
@@ -20,8 +21,9 @@ current keys.  For ``mode == "train"``:
    bridge node, so ``loss.backward()`` fills ``.grad`` of every trainable parameter;
 5. output ``{"greedy_seqs", "sampled_seqs", "reward", "score", "loss"}``; the model is left in ``train()`` mode.
 
-Any other mode is forwarded to the wrapped model.  The caller's ``input_dict`` is not modified (the reference overwrites
-its ``mode`` and ``sample_method``).
+The wrapped model is a ``TransformerModel``, or a ``Seq2SeqAttnModel`` / ``TemporalSeq2SeqAttnModel`` over a ``CrnnEncoder``
+(``temporal_tag`` then goes to both the baseline and the rollout).  Any other mode is forwarded to the wrapped model.
+The caller's ``input_dict`` is not modified (the reference overwrites its ``mode`` and ``sample_method``).
 """
 import math
 
@@ -104,9 +106,14 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
 
     def __init__(self, model):
         super().__init__()
-        if not isinstance(model, TransformerModel):
-            raise NotImplementedError(f"ScstWrapper: the wrapped model must be a TransformerModel (the HIP training "
-                                      f"engine's rollout), got {model.__class__.__name__}")
+        from .attn_model import Seq2SeqAttnModel
+        from .crnn_trm_encoder import CrnnEncoder
+        self._attn_gru = isinstance(model, Seq2SeqAttnModel) and isinstance(model.encoder, CrnnEncoder)
+        if not (isinstance(model, TransformerModel) or self._attn_gru):
+            over = f" over {model.encoder.__class__.__name__}" if isinstance(model, Seq2SeqAttnModel) else ""
+            raise NotImplementedError(f"ScstWrapper: the wrapped model must be a TransformerModel, or a Seq2SeqAttnModel / "
+                                      f"TemporalSeq2SeqAttnModel over a CrnnEncoder (the HIP training engines' rollouts), "
+                                      f"got {model.__class__.__name__}{over}")
         self.model = model
 
     def forward(self, input_dict):
@@ -135,7 +142,7 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
             return res["seq"], res["seq_dev"].to(torch.int32)      # (a copy: the decoder reuses its buffer)
 
     def scst(self, input_dict):
-        from .train import TrainEngine, _TrainBridge
+        from .train import _TrainBridge
         model = self.model
         for k in ("keys", "key2refs", "vocabulary", "scorer"):
             if input_dict.get(k) is None:
@@ -148,8 +155,13 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
             raise NotImplementedError(f"ScstWrapper: the rollout draws with plain sampling ('sample'), not {method!r}")
         max_length = int(input_dict.get("max_length", model.max_length))
         engine = getattr(model, "_train_engine", None)
-        if engine is None:
-            engine = model._train_engine = TrainEngine(model)     # (raises for an encoder the engine is not built for)
+        if engine is None:     # (raises for an encoder the engine is not built for)
+            if self._attn_gru:
+                from .train_attn_gru import AttnGruTrainEngine
+                engine = model._train_engine = AttnGruTrainEngine(model)
+            else:
+                from .train import TrainEngine
+                engine = model._train_engine = TrainEngine(model)
         keys = list(input_dict["keys"])
 
         greedy, greedy_i32 = self._baseline(input_dict, max_length)

@@ -11,12 +11,15 @@ Training (csrc/attn_gru_train.hip): ``train_forward`` runs the scheduled-samplin
 ``stepwise_forward`` for ``mode="train"`` (base.py:152-208, attn_model.py:34-65) in one C call and keeps what
 ``train_backward`` - the backward through time, one C call - needs.  The constructor's ``dropout`` (``in_dropout`` on the
 step's input embedding) takes effect when ``self.training`` is set: counter-hash masks at site ``train.OP_BAH_IN``,
-regenerated in the backward.  The models of ``attn_model.py`` reach both through ``train_attn_gru.AttnGruTrainEngine``.
+regenerated in the backward.  ``train_rollout`` is the sampled rollout of self-critical sequence training
+(``ac_bah_train_rollout``): the same chain with no caption, each step on the word the step before drew, and the same kept
+state.  The models of ``attn_model.py`` reach all three through ``train_attn_gru.AttnGruTrainEngine``.
 
 Built: ``rnn_type="GRU"``, ``num_layers=1``, unidirectional; emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim each a
 multiple of 32 up to 1024; vocab_size <= 16384.  Anything else raises NotImplementedError in the constructor.
 """
 import ctypes
+import math
 
 import torch
 import torch.nn as nn
@@ -244,6 +247,63 @@ class BahAttnCatFcDecoder(RnnDecoder):
             ptr(tags), B, Tm, T, int(start_idx), p, seed, seed_dev, ptr(out["seq"]), ptr(out["logit"]),
             ptr(out["sampled_logprob"]), ptr(out["embed"]), ptr(out["attn_weight"]), ptr(out["state"]), ptr(saved["ws"]),
             stream()), "ac_bah_train_forward")
+        out["saved"] = saved
+        return out
+
+    def train_rollout(self, attn_emb, fc_emb, attn_emb_len, max_length, temp, sample_seed, tags=None, forced=None,
+                      start_idx=1, end_idx=2, dropout_seed=0, seed_dev=None):
+        """The sampled rollout of self-critical sequence training over ``max_length`` steps (``ac_bah_train_rollout``; no
+        host synchronisation): ``train_forward`` with no caption, step t > 0 on the word step t - 1 stored.  The word of
+        step t is drawn from softmax(log_softmax(logit_t) / temp) by the plain sampler at Philox counter (t, clip) under
+        ``sample_seed`` (one int64 device word, see ``sampling.seed_word``) - or is ``forced[:, t]`` (int32 (N, T) on the
+        device, the parity hook); a clip that has stored ``end_idx`` keeps storing it, and every step runs.  The other
+        arguments are ``train_forward``'s.  Returns what ``train_forward`` returns with ``seq_i32`` (the stored words where
+        the decoder left them) next to ``seq`` (int64) and ``sampled_logprob`` = log_softmax(logit)[word] / temp; "saved"
+        feeds ``train_backward`` unchanged."""
+        from .train import OP_BAH_IN
+        lib = _lib.load()
+        w = self.weights()
+        attn_emb, fc_emb = f32c(attn_emb), f32c(fc_emb)
+        ptr(attn_emb), ptr(fc_emb)
+        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
+            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
+                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        B, Tm, _ = attn_emb.shape
+        if Tm > MAX_FRAMES:
+            raise NotImplementedError(f"{Tm} frames of audio memory: the attention kernels hold at most {MAX_FRAMES}")
+        T, temp = int(max_length), float(temp)
+        if T < 1:
+            raise ValueError("train_rollout: max_length must be at least 1")
+        if not (math.isfinite(temp) and temp > 0):
+            raise ValueError(f"train_rollout: temp must be finite and > 0, got {temp}")
+        if (tags is None) != (self.n_tags == 0):
+            raise ValueError("tags: required by a temporal decoder, refused by a plain one")
+        dev = attn_emb.device
+        if forced is not None and (forced.dtype != torch.int32 or tuple(forced.shape) != (B, T) or not forced.is_contiguous()
+                                   or forced.device != dev):
+            raise ValueError(f"forced must be a contiguous int32 ({B}, {T}) tensor on the device")
+        if sample_seed.dtype != torch.int64 or sample_seed.device != dev:
+            raise ValueError("sample_seed must be one int64 word on the device")
+        lens = attn_emb_len if (torch.is_tensor(attn_emb_len) and attn_emb_len.is_cuda and attn_emb_len.dtype == torch.int32) \
+            else K.upload(attn_emb_len, dev, torch.int32)
+        n = lib.ac_bah_train_workspace_floats(ctypes.byref(w), B, Tm, T)
+        if n <= 0:
+            raise _lib.HipLibraryError("ac_bah_train_workspace_floats rejected the decoder configuration")
+        f32 = dict(device=dev, dtype=torch.float32)
+        p = float(self.in_dropout.p) if self.training else 0.0
+        seed = ((int(dropout_seed) << 16) + OP_BAH_IN) & 0xFFFFFFFFFFFFFFFF if seed_dev is None else OP_BAH_IN
+        out = {"seq_i32": torch.empty(B, T, device=dev, dtype=torch.int32), "logit": torch.empty(B, T, self.vocab_size, **f32),
+               "sampled_logprob": torch.empty(B, T, **f32), "embed": torch.empty(B, T, self.d_model, **f32),
+               "attn_weight": torch.empty(B, Tm, T, **f32), "state": torch.empty(1, B, self.d_model, **f32)}
+        saved = {"w": w, "attn_emb": attn_emb, "fc_emb": fc_emb, "len": lens, "B": B, "Tm": Tm, "T": T, "p": p, "seed": seed,
+                 "seed_dev": seed_dev, "ws": torch.empty(n, **f32), "sample_seed": sample_seed, "forced": forced}
+        scratch = torch.empty(2 * B, device=dev, dtype=torch.int32)
+        check(lib.ac_bah_train_rollout(
+            ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), ptr(lens), ptr(tags), B, Tm, T, int(start_idx), int(end_idx), temp,
+            ptr(sample_seed), ptr(forced), T, p, seed, seed_dev, ptr(out["seq_i32"]), ptr(scratch), ptr(out["logit"]),
+            ptr(out["sampled_logprob"]), ptr(out["embed"]), ptr(out["attn_weight"]), ptr(out["state"]), ptr(saved["ws"]),
+            stream()), "ac_bah_train_rollout")
+        out["seq"] = out["seq_i32"].to(torch.int64)
         out["saved"] = saved
         return out
 

@@ -14,9 +14,15 @@ bridge node, so the reference runner's ``loss.backward()``, ``clip_grad_norm_`` 
 ``optim.FusedAdam`` - work unchanged.  The scheduled-sampling coins follow the reference (attn_model.py:44): one
 ``random.random()`` per step in step order, at ``ss_ratio == 1`` as well, all drawn on the host before anything is launched.
 
-Not built for these models: the fused ``step`` (device-side loss, clip, Adam, graph capture, the split all-reduce), the
-SCST ``rollout`` and the Cnn14 look-ahead.
+``AttnGruTrainEngine.rollout`` is the sampled rollout of self-critical sequence training with ``TrainEngine.rollout``'s
+contract (``rl_model.ScstWrapper`` drives it): the same train-mode encoder, then ``max_length`` decoder steps with no
+caption, each on the word the step before drew (``BahAttnCatFcDecoder.train_rollout``, ``ac_bah_train_rollout``).  It keeps
+the state of a ``forward``, so ``backward`` and the bridge node work after it; it draws no scheduled-sampling coins.
+
+Not built for these models: the fused ``step`` (device-side loss, clip, Adam, graph capture, the split all-reduce), graph
+capture or an early exit of the rollout, and the Cnn14 look-ahead.
 """
+import math
 import random
 
 import torch
@@ -44,18 +50,17 @@ class AttnGruTrainEngine(TrainEngine):
         return 2 * H
 
     def _prepare(self, input_dict, rollout=False):
-        if rollout:
-            raise NotImplementedError("AttnGruTrainEngine: the SCST rollout covers TransformerModel only")
         T = input_dict["cap"].shape[1] - 1
         tags = None
         if self.model.decoder.n_tags:
             tags = check_temporal_tag(input_dict.get("temporal_tag"), input_dict["cap"].shape[0])
         # one coin per step, in step order, whatever ss_ratio is: the engine draws them unless ss_ratio == 1, where the
         # reference's attention model still consumes the stream (attn_model.py:44) and every coin comes out 1
-        if input_dict["ss_ratio"] == 1:
+        # (the SCST rollout takes no caption and draws no coins: ``rollout`` hands them over as ``_use_cap``)
+        if input_dict["ss_ratio"] == 1 and not rollout:
             for _ in range(T):
                 random.random()
-        st = super()._prepare(input_dict)     # st["use_cap"]: the T coins
+        st = super()._prepare(input_dict, rollout)     # st["use_cap"]: the T coins
         st["tags"] = None if tags is None else K.upload(tags, st["cap"].device, torch.int32)
         return st
 
@@ -87,9 +92,14 @@ class AttnGruTrainEngine(TrainEngine):
               "ac_mean_with_lens")
         was = dec.training
         dec.training = not st["eval"]     # a model in eval(): every dropout probability 0, as TrainEngine does
+        ro = st.get("rollout")
         try:
-            st["bah"] = dec.train_forward(attn_emb, fc_emb, lens, st["cap"], st["use_cap"], st.get("tags"), model.start_idx,
-                                          seed_dev=self._seed_ptr)
+            if ro is None:
+                st["bah"] = dec.train_forward(attn_emb, fc_emb, lens, st["cap"], st["use_cap"], st.get("tags"),
+                                              model.start_idx, seed_dev=self._seed_ptr)
+            else:
+                st["bah"] = dec.train_rollout(attn_emb, fc_emb, lens, st["T"], ro["temp"], ro["seed"], st.get("tags"),
+                                              ro["forced"], model.start_idx, model.end_idx, seed_dev=self._seed_ptr)
         finally:
             dec.training = was
 
@@ -118,7 +128,51 @@ class AttnGruTrainEngine(TrainEngine):
         self._launch_backward_gru(sv)
 
     def rollout(self, input_dict):
-        raise NotImplementedError("AttnGruTrainEngine: the SCST rollout covers TransformerModel only")
+        """The sampled rollout of self-critical sequence training, ``TrainEngine.rollout``'s contract: the train-mode encoder
+        (frozen Cnn14 with its dropout and SpecAugment, the bi-GRU with saved gates; ``_cnn_attn`` honoured), ``fc_emb`` by
+        ``ac_mean_with_lens``, then ``max_length`` decoder steps with no caption (``train_rollout``).  All steps always run.
+
+        ``input_dict``: wav / wav_len / specaug as for mode "train", ``temporal_tag`` for the temporal model; ``max_length``
+        (default the model's), ``temp`` (1.0); ``dropout_seed`` as in ``forward``; ``seed``: the sampler's 64-bit seed
+        (default: the dropout seed of this call); ``_scst_words`` (parity hook, int64 N x T): these words instead of the
+        draws, the finished-row rule still applies.  No ``cap`` is needed and no scheduled-sampling coin is drawn.
+        Returns ``logit`` (N, T, V), ``seq`` (int64), ``seq_i32`` and ``sampled_logprob`` (N, T) on the device, and
+        ``embed``, ``attn_weight``, ``state``, ``attn_emb_len`` as ``forward`` does; ``backward`` works as after ``forward``."""
+        model = self.model
+        T = int(input_dict.get("max_length", model.max_length))
+        temp = float(input_dict.get("temp", 1.0))
+        if T < 1:
+            raise ValueError("rollout: max_length must be at least 1")
+        if not (math.isfinite(temp) and temp > 0):
+            raise ValueError(f"rollout: temp must be finite and > 0, got {temp}")
+        wav = input_dict["wav"]
+        if not wav.is_cuda:
+            raise _lib.HipLibraryError("the training step needs tensors on a ROCm device; there is no CPU fallback")
+        N = wav.shape[0]
+        cap = torch.zeros(N, T + 1, device=wav.device, dtype=torch.int64)    # never read: no step takes a caption word
+        d = {k: v for k, v in input_dict.items() if k != "cap_len"}
+        d.update(cap=cap, ss_ratio=0.0, _use_cap=[0] * T)
+        base_seed = int(input_dict.get("dropout_seed", self.seed))
+        state = random.getstate()     # TrainEngine._prepare draws a coin per step before it looks at _use_cap
+        try:
+            st = self._prepare(d, rollout=True)
+        finally:
+            random.setstate(state)
+        seed = int(input_dict["seed"]) if input_dict.get("seed") is not None else base_seed
+        forced = input_dict.get("_scst_words")
+        if forced is not None:
+            forced = torch.as_tensor(forced).to(device=wav.device, dtype=torch.int32).contiguous()
+            if tuple(forced.shape) != (N, T):
+                raise ValueError(f"_scst_words must be ({N}, {T})")
+        ro = st.get("rollout")
+        if ro is None:
+            ro = st["rollout"] = {"seed": torch.zeros(1, device=wav.device, dtype=torch.int64)}
+        from .sampling import seed_word
+        ro["seed"].copy_(torch.tensor([seed_word(seed & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))   # read on the device
+        ro.update(temp=temp, forced=forced)
+        self._launch_forward(st)
+        self._saved = st
+        return self._outputs(st)
 
     def step(self, *args, **kwargs):
         raise NotImplementedError("AttnGruTrainEngine: the fused step (device-side loss, clip, Adam, graph capture) covers "

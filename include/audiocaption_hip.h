@@ -555,6 +555,24 @@ int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const f
                          int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
                          int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
                          float* ws, void* stream);
+/* The sampled rollout of self-critical sequence training (rl_model.py:35-38 over base.py:152-170): the chain of
+ * ac_bah_train_forward for T = max_length steps with no caption.  Step 0 feeds start_idx (the tag's embedding when tags !=
+ * NULL), step t > 0 the word step t - 1 stored in seq; in_dropout's mask index is the same (t * B + b) * E + e.  After the
+ * classifier of step t the pick is ac_scst_pick: clip b draws from softmax(log_softmax(logit[b][t]) / temp) with the plain
+ * sampler at Philox counter (t, b) under sample_seed_dev (one uint64 on the device), or takes forced[b * forced_ld + t]
+ * (forced != NULL: int32 on the device, forced_ld >= T); a clip that has stored end_idx keeps storing end_idx, and every
+ * step runs.  seq [B][T] int32 gets the stored words, logprob [B][T] = log_softmax(logit)[word before the rule] / temp;
+ * logit, embed, attn_weight, state as ac_bah_train_forward writes them.  scratch: 2 B ints.  The workspace has
+ * ac_bah_train_forward's size and layout, so ac_bah_train_backward (same w, attn_emb, fc_emb, mem_len, B, Tm, T and
+ * dropout arguments) consumes it unchanged.  AC_ERR_ARG before anything is launched: a NULL pointer (forced may be NULL),
+ * T < 1, temp not finite or <= 0, forced_ld < T, tags given to a decoder without tags or missing for one with them, the
+ * limits of ac_bah_train_workspace_floats. */
+int ac_bah_train_rollout(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const int* tags, int B, int Tm, int T, int start_idx, int end_idx, float temp,
+                         const uint64_t* sample_seed_dev, const int* forced, long forced_ld, float drop_p,
+                         unsigned long long drop_seed, const unsigned long long* seed_dev, int* seq, int* scratch,
+                         float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
+                         void* stream);
 /* Where the backward ADDS the gradient of each tensor of the ac_bah_weights struct - same names and shapes (temb may be NULL when
  * n_tags == 0).  The buffers may be slices of one flat gradient buffer; the caller clears them. */
 typedef struct {
