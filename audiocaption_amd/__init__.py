@@ -15,7 +15,9 @@ from .rl_model import ScstWrapper
 from .cider import Cider
 from .caption_metrics import Bleu, Rouge
 from .kd_loss import SupKdLoss, TokenLevelKdLoss
+from .kd_wrapper import ContraEncoderKdWrapper, ContraMseEncoderKdWrapper, MseEncoderKdWrapper
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
            "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
-           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss", "init_model_from_config", "cnn14rnn_trm_config"]
+           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss",
+           "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config"]

@@ -157,6 +157,9 @@ SIGNATURES = {
     "ac_scst_loss": (_I, [_P, _P, _L, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     # token-level knowledge distillation (csrc/kd.hip)
     "ac_kd_loss": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _F, _P, _P]),
+    # encoder-level knowledge distillation (csrc/enc_kd.hip)
+    "ac_enc_kd_workspace_floats": (_L, [_I, _I]),
+    "ac_enc_kd_loss": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     # CIDEr-D on token ids (csrc/cider.hip)
     "ac_cider_workspace_bytes": (_L, [_L, _I, _I, _I]),
     "ac_cider_scores": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _I, _I, _P, _L, _P, _I, _I, _P, _I, _P, _P, _I, _F, _P, _L, _P,

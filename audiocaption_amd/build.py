@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libaudiocaption_hip.so")
 STAMP = LIB + ".stamp"
-SOURCES = ["logmel.hip", "conv3x3.hip", "conv3x3_winograd.hip", "conv3x3_wino1d.hip", "conv3x3_wino43.hip", "conv3x3_block1_w4.hip", "conv3x3_skinny.hip", "gemm.hip", "gru.hip", "decoder.hip", "decoder_wide.hip", "decoder_cluster.hip", "sample.hip", "ensemble.hip", "attn_gru.hip", "attn_gru_train.hip", "sed.hip", "train.hip", "scst.hip", "kd.hip", "cider.hip", "capmetrics.hip", "effnet.hip", "effnet_fused.hip", "pw_gemm.hip", "ingest.hip", "probe.hip"]
+SOURCES = ["logmel.hip", "conv3x3.hip", "conv3x3_winograd.hip", "conv3x3_wino1d.hip", "conv3x3_wino43.hip", "conv3x3_block1_w4.hip", "conv3x3_skinny.hip", "gemm.hip", "gru.hip", "decoder.hip", "decoder_wide.hip", "decoder_cluster.hip", "sample.hip", "ensemble.hip", "attn_gru.hip", "attn_gru_train.hip", "sed.hip", "train.hip", "scst.hip", "kd.hip", "enc_kd.hip", "cider.hip", "capmetrics.hip", "effnet.hip", "effnet_fused.hip", "pw_gemm.hip", "ingest.hip", "probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-Wno-unused-result"]
 # Every source is built WITHOUT the packed-f32 VALU instructions (v_pk_fma_f32, v_pk_add_f32 ...).  With them the per-row
@@ -33,7 +33,9 @@ NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # csrc/sed.hip: the temporal-tag pair rule repeats the reference's float64 arithmetic rounding by rounding (frame * 0.01, then
 # the differences); with the default -ffp-contract=fast the backend fuses the product into the subtraction (v_fma_f64) and
 # exact ties between segment durations fall the other way.
-EXTRA_FLAGS = {"sed.hip": ["-ffp-contract=off"]}
+# csrc/enc_kd.hip: a logit logit_scale * cos must be the same float wherever it is formed (the row maximum, the diagonal
+# term, the gradient); fused into a subtraction in one place it is not, and one clip's contrastive loss is no longer 0.
+EXTRA_FLAGS = {"sed.hip": ["-ffp-contract=off"], "enc_kd.hip": ["-ffp-contract=off"]}
 
 def _hipcc():
     for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):

@@ -4,6 +4,10 @@
 ``Cnn14RnnEncoder`` is accepted as an alias because the reference's own Clotho config names it
 (eg_configs/clotho_v2/waveform/cnn14rnn_trm.yaml:9) although that class does not exist in the
 reference module (SURVEY.md "Key facts").
+
+Both composites carry ``fc_emb_size`` (512 for the bi-GRU, the Transformer encoder's ``d_model``), which the
+encoder-distillation wrappers read (kd_wrapper.py).  This is an extension: the reference's composite encoders lack the
+attribute, so its wrappers can only be constructed over encoders that define it.
 """
 import inspect
 
@@ -34,6 +38,10 @@ class CrnnEncoder(nn.Module):
         super().__init__()
         self.cnn = cnn
         self.rnn = rnn
+        # width of ``fc_emb`` (the RNN's masked mean: 512 for the bi-GRU of this path), read by the encoder-distillation
+        # wrappers (kd_wrapper.py).  An extension: the reference's composite encoders do not define it.
+        if hasattr(rnn, "embed_dim"):
+            self.fc_emb_size = rnn.embed_dim
         self._skip_fc = _accepts_skip_fc(cnn)
         self.freeze_cnn_bn = False
         if freeze_cnn:
@@ -76,6 +84,9 @@ class Cnn14TransformerEncoder(nn.Module):
         super().__init__()
         self.cnn = cnn
         self.trm = transformer
+        # width of ``fc_emb`` (the cls row), for the encoder-distillation wrappers; an extension, as in CrnnEncoder
+        if hasattr(transformer, "d_model"):
+            self.fc_emb_size = transformer.d_model
         self._skip_fc = _accepts_skip_fc(cnn)
         self.freeze_cnn_bn = False
         if freeze_cnn:

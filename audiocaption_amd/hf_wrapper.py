@@ -3,7 +3,7 @@
 ``Effb2TrmConfig`` / ``Effb2TrmCaptioningModel`` mirror ``captioning.models.hf_wrapper`` (hf_wrapper.py:1115-1181): the same
 config keys and defaults, the same module tree -
 
-    Effb2TrmCaptioningModel.model        ContraEncoderKdWrapper   (hf_wrapper.py:1071-1112)
+    Effb2TrmCaptioningModel.model        ContraEncoderKdWrapper   (hf_wrapper.py:1071-1112; kd_wrapper.py here)
         .model                           TransformerModel(EfficientNetB2(), TransformerDecoder(tie_weights=True))
         .stdnt_proj / .tchr_proj / .logit_scale     knowledge-distillation heads: in the checkpoint, unused at inference
 
@@ -25,7 +25,6 @@ model), so ``demo.py``-style callers can use the Cnn14Rnn-Trm captioner without 
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import kernels as K
 from .attn_model import TemporalSeq2SeqAttnModel
@@ -33,12 +32,13 @@ from .cnn_encoder import Cnn14Encoder
 from .config import merge_load_state_dict
 from .crnn_trm_encoder import Cnn14RnnEncoder
 from .effnet_encoder import EfficientNetB2
+from .kd_wrapper import ContraEncoderKdWrapper   # noqa: F401 - hf_wrapper.py:1071-1112 defines it here; kd_wrapper.py holds all three
 from .mel import MelSpectrogramBuffers, MelTables
 from .rnn_decoder import TemporalBahAttnDecoder, check_temporal_tag
 from .rnn_encoder import RnnEncoder
 from .sed_model import Cnn8rnnSedModel
 from .transformer_decoder import TransformerDecoder
-from .transformer_model import CaptionMetaMixin, TransformerModel
+from .transformer_model import TransformerModel
 
 try:   # the real base classes when the package is there (it is an optional dependency of the reference as well)
     from transformers import PretrainedConfig, PreTrainedModel
@@ -73,45 +73,6 @@ def _input_dict(device, audio, audio_length, sample_method, beam_size, max_lengt
     if sample_method == "beam":
         d["beam_size"] = beam_size
     return d
-
-
-class ContraEncoderKdWrapper(nn.Module, CaptionMetaMixin):
-    """hf_wrapper.py:1071-1112.  Holds the captioner plus the contrastive knowledge-distillation heads that exist in the
-    published state dict.  Inference passes straight through to the captioner (HIP path); with ``tchr_output`` in the input
-    dict the symmetric contrastive loss between the projected clip embedding and the teacher's embedding is added as
-    ``enc_kd_loss`` (hf_wrapper.py:1095-1111) - a few torch ops on ``fc_emb``, outside the accelerated path.
-
-    The loss is HEAD-ONLY here: ``fc_emb`` comes out of the HIP encoder detached, so ``enc_kd_loss`` trains
-    ``stdnt_proj`` / ``tchr_proj`` / ``logit_scale`` and sends no gradient into the encoder.  Distilling INTO the encoder
-    (the reference's recipe: mode "train", encoder_output_dict merged into the training output, base.py:133) needs the
-    encoder's backward, which this path does not build (SURVEY section 8 scope): mode "train" with ``tchr_output`` raises
-    ``NotImplementedError`` instead of returning a loss that silently trains nothing but the heads."""
-
-    def __init__(self, model, shared_dim, tchr_dim):
-        super().__init__()
-        self.model = model
-        self.tchr_dim = tchr_dim
-        fc = model.encoder.fc_emb_size if hasattr(model, "encoder") else model.fc_emb_size
-        self.stdnt_proj = nn.Linear(fc, shared_dim)
-        self.tchr_proj = nn.Linear(tchr_dim, shared_dim)
-        self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
-
-    def forward(self, input_dict):
-        if "tchr_output" in input_dict and input_dict.get("mode") == "train" and not input_dict.get("unsup", False):
-            raise NotImplementedError(
-                "ContraEncoderKdWrapper: encoder knowledge distillation in mode='train' needs the gradient of enc_kd_loss "
-                "with respect to the encoder (hf_wrapper.py:1095-1111 on top of base.py:133); the accelerated training "
-                "step returns no fc_emb and the HIP encoder has no backward.  Use mode='inference' (or unsup=True) for a "
-                "head-only loss")
-        out = self.model.encoder(input_dict) if input_dict.get("unsup", False) else self.model(input_dict)
-        if "tchr_output" in input_dict:
-            # CLIP-style loss: cosine similarities of every (student clip, teacher clip) pair, scaled, matched on the diagonal
-            student = F.normalize(self.stdnt_proj(out["fc_emb"]), dim=-1)
-            teacher = F.normalize(self.tchr_proj(input_dict["tchr_output"]["embedding"]), dim=-1)
-            sim = self.logit_scale * (student @ teacher.t())
-            target = torch.arange(sim.shape[0], device=sim.device)
-            out["enc_kd_loss"] = 0.5 * (F.cross_entropy(sim, target) + F.cross_entropy(sim.t(), target))
-        return out
 
 
 class Effb2TrmConfig(PretrainedConfig):

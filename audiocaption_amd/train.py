@@ -22,7 +22,9 @@ row space with every pass run on the words drawn so far, feeding the same backwa
 
 ``TrainEngine`` is the fast path (``engine.step(batch)``); ``TransformerModel.forward`` with ``mode="train"`` goes
 through the same engine and returns ``logit`` attached to torch.autograd by ONE bridge node, so the reference's
-runner (``loss.backward()``, any torch optimizer) works unchanged.  The attention-GRU captioners train through
+runner (``loss.backward()``, any torch optimizer) works unchanged.  That forward also returns the clip embedding
+``fc_emb`` behind the same node, and ``backward`` takes its gradient beside ``dlogit``: encoder-level knowledge
+distillation (enc_kd.py, kd_wrapper.py); the fused ``step`` computes neither.  The attention-GRU captioners train through
 ``train_attn_gru.AttnGruTrainEngine``, this engine with the decoder half replaced (autograd route only).
 """
 import os
@@ -945,17 +947,36 @@ class TrainEngine:
         return out
 
     def forward(self, input_dict):
-        """The reference's ``model(input_dict)`` for mode "train": returns ``logit`` (N, T, V) [+ ``seq``] as fresh
-        device tensors and keeps what the backward needs.  On a model in ``eval()`` - a frozen teacher, a validation loss -
-        the same kernels run with every dropout probability 0 and SpecAugment off, and nothing is kept."""
+        """The reference's ``model(input_dict)`` for mode "train": returns ``logit`` (N, T, V) [+ ``seq``] and the clip
+        embedding ``fc_emb`` (N, A) (base.py:133 merges the encoder's outputs into the training output) as fresh device
+        tensors and keeps what the backward needs.  On a model in ``eval()`` - a frozen teacher (its ``fc_emb`` is
+        run_kd.py:44's ``tchr_output["embedding"]``), a validation loss - the same kernels run with every dropout
+        probability 0 and SpecAugment off, and nothing is kept."""
         st = self._prepare(input_dict)
         self._launch_forward(st)
+        fc_emb = self._launch_fc_emb(st)
         self._saved = None if st["eval"] else st      # a model in eval(): no backward state (``backward`` raises)
         out = self._outputs(st)
         out["logit"] = out["logit"].clone()
+        out["fc_emb"] = fc_emb.clone()
         if "seq" in out:
             out["seq"] = out["seq"].to(torch.int64)
         return out
+
+    def _launch_fc_emb(self, st):
+        """``fc_emb`` (N, A) of the forward just launched, as a view of the workspace: the masked mean of the last GRU
+        layer's output over each clip's valid frames (rnn_encoder.py:44), or the cls row of each clip of the Transformer
+        encoder's output (transformer_encoder.py:116).  Only ``forward`` computes it; the fused ``step`` does not."""
+        lib, ws = self.lib, st["ws"]
+        s = _lib.stream()
+        N, Tq, A = st["N"], st["Tq"], self.enc_width
+        fc = ws.f("fc_emb", N, A)
+        if self.enc_kind == "trm":
+            check(lib.ac_gather_rows(st["enc"]["out"], self._enc_layout(st)["row0"], fc, N, A, s), "ac_gather_rows(fc_emb)")
+        else:
+            check(lib.ac_mean_with_lens(st["attn_emb"], st["small"].data_ptr() + 8, fc, N, Tq, A, 0, s),
+                  "ac_mean_with_lens(fc_emb)")
+        return ws.tensor("fc_emb")[:N * A].view(N, A)
 
     # ---- SCST rollout (rl_model.py:35-38: the model in train() mode, sample_method "sample") --------------------------
     def rollout(self, input_dict):
@@ -1009,17 +1030,53 @@ class TrainEngine:
         return out
 
     # ---- backward -----------------------------------------------------------------------------------------
-    def backward(self, dlogit):
+    def backward(self, dlogit, dfc_emb=None):
         """d(loss)/d(parameters) of the last forward into the (zeroed) flat gradient buffer, given d(loss)/d(logit)
-        (N, T, V).  The kernels accumulate (split-K atomics, bias column sums), so the buffer is cleared first."""
+        (N, T, V).  The kernels accumulate (split-K atomics, bias column sums), so the buffer is cleared first.
+
+        ``dfc_emb`` (N, A): d(loss)/d(fc_emb) of ``forward``'s clip embedding (encoder-level distillation, enc_kd.py); it
+        joins the encoder-output gradient after the decoder's backward has written it.  ``dlogit`` may then be None (a
+        loss on ``fc_emb`` alone): the decoder's backward is skipped and its gradients are exactly zero."""
         sv = self._saved
         if sv is None:
             raise RuntimeError("TrainEngine.backward without a forward")
+        if dlogit is None and dfc_emb is None:
+            raise ValueError("TrainEngine.backward: neither dlogit nor dfc_emb")
         self._saved = None
-        dlogit = dlogit.contiguous()
-        if dlogit.dtype != torch.float32:
-            dlogit = dlogit.float()
-        self._launch_backward(sv, dlogit.data_ptr())
+
+        def f32(t):
+            return None if t is None else t.contiguous().float()
+        dlogit, dfc_emb = f32(dlogit), f32(dfc_emb)
+        if dfc_emb is None:
+            return self._launch_backward(sv, dlogit.data_ptr())
+        if tuple(dfc_emb.shape) != (sv["N"], self.enc_width):
+            raise ValueError(f"TrainEngine.backward: dfc_emb {tuple(dfc_emb.shape)}, expected {(sv['N'], self.enc_width)}")
+        self._launch_backward_fc(sv, None if dlogit is None else dlogit.data_ptr(), dfc_emb.data_ptr())
+
+    def _enc_dout(self, sv):
+        """(name, rows) of the buffer the encoder's backward reads d(loss)/d(its output) from."""
+        return ("enc_dout", sv["N"] * sv["Tm"]) if self.enc_kind == "trm" else ("gru_dout", sv["N"] * sv["Tq"])
+
+    def _launch_backward_fc(self, sv, dl, dfc):
+        """The backward with a gradient on ``fc_emb``: the decoder's half (or, without ``dl``, zeros in its place), then
+        ``dfc`` added to d(loss)/d(encoder output) - spread over each clip's valid frames (``ac_bah_mean_lens_bwd``) or added
+        to each clip's cls row -, then the encoder's half."""
+        lib, ws = self.lib, sv["ws"]
+        N, Tq, A = sv["N"], sv["Tq"], self.enc_width
+        name, rows = self._enc_dout(sv)
+        dout = ws.f(name, rows, A)
+        if dl is not None:
+            self._launch_backward(sv, dl, "head")
+        else:
+            self.flat.grad.zero_()
+            ws.tensor(name)[:rows * A].zero_()
+        s = _lib.stream()
+        if self.enc_kind == "trm":
+            check(lib.ac_scatter_add_rows(dfc, self._enc_layout(sv)["row0"], dout, N, A, s), "ac_scatter_add_rows(dfc_emb)")
+        else:
+            check(lib.ac_bah_mean_lens_bwd(dfc, sv["small"].data_ptr() + 8, dout, N, Tq, A, A, s),
+                  "ac_bah_mean_lens_bwd(dfc_emb)")
+        self._launch_backward_enc(sv)
 
     def _launch_backward(self, sv, dl, part="all"):
         """``part``: "all", or the two halves of it - "head" (classifier, decoder layers, audio memory, attn_proj: every
@@ -1470,6 +1527,23 @@ class _TrainBridge(torch.autograd.Function):
         return (None, None) + tuple(ctx.engine.flat.grad_views)
 
 
+class _TrainBridgeFc(torch.autograd.Function):
+    """``_TrainBridge`` with the clip embedding as a second output: ``(logit, fc_emb)`` in, ``(dlogit, dfc_emb)`` back.
+    A gradient may arrive on either output or on both; an output no loss used comes back as None (not as zeros), so
+    a plain captioning loss takes exactly ``_TrainBridge``'s route."""
+
+    @staticmethod
+    def forward(ctx, engine, logit, fc_emb, *params):
+        ctx.engine = engine
+        ctx.set_materialize_grads(False)
+        return logit.view_as(logit), fc_emb.view_as(fc_emb)
+
+    @staticmethod
+    def backward(ctx, dlogit, dfc_emb):
+        ctx.engine.backward(dlogit, dfc_emb)
+        return (None, None, None) + tuple(ctx.engine.flat.grad_views)
+
+
 def train_forward(model, input_dict):
     """``TransformerModel.forward`` for ``mode == "train"`` (base.py:73-112 -> train_forward)."""
     engine = getattr(model, "_train_engine", None)
@@ -1478,5 +1552,5 @@ def train_forward(model, input_dict):
     out = engine.forward(input_dict)
     # a model in eval() (a distillation teacher, a validation loss): plain logits, no bridge node, nothing to back-propagate
     if model.training and torch.is_grad_enabled():
-        out["logit"] = _TrainBridge.apply(engine, out["logit"], *engine.flat.params)
+        out["logit"], out["fc_emb"] = _TrainBridgeFc.apply(engine, out["logit"], out["fc_emb"], *engine.flat.params)
     return out

@@ -7,7 +7,8 @@ The encoder half is the engine's own - the frozen Cnn14 forward, the 3-layer bi-
 Between the two sits the decoder of csrc/attn_gru_train.hip (``rnn_decoder.BahAttnCatFcDecoder.train_forward`` /
 ``train_backward``): ``fc_emb`` is the mean of the GRU output over each clip's valid frames (``ac_mean_with_lens``), and in
 the backward the decoder's ``d fc_emb`` goes back into every valid frame (``ac_bah_mean_lens_bwd``) on top of its
-``d attn_emb``; the total lands in ``gru_dout``.
+``d attn_emb``; the total lands in ``gru_dout``.  ``forward`` returns that ``fc_emb`` as well, and a gradient arriving on
+it from outside the decoder (encoder-level distillation, enc_kd.py) is added to the decoder's ``d fc_emb`` first.
 
 ``model(input_dict)`` with ``mode="train"`` (``train_forward`` below) returns ``logit`` attached to autograd by one
 bridge node, so the reference runner's ``loss.backward()``, ``clip_grad_norm_`` and any torch optimiser - or
@@ -31,7 +32,7 @@ from . import _lib
 from . import kernels as K
 from ._lib import check
 from .rnn_decoder import check_temporal_tag
-from .train import H, OP_CNN_BLOCK, TrainEngine, _TrainBridge
+from .train import H, OP_CNN_BLOCK, TrainEngine, _TrainBridgeFc
 
 
 class AttnGruTrainEngine(TrainEngine):
@@ -110,7 +111,14 @@ class AttnGruTrainEngine(TrainEngine):
         out["attn_weight"] = out["attn_weight"][:, :int(st["lens_host"].max())]
         return out
 
-    def _launch_backward(self, sv, dl, part="all"):
+    def _launch_fc_emb(self, st):
+        N, A = st["N"], self.enc_width
+        return st["ws"].tensor("bah_fc")[:N * A].view(N, A)     # the decoder's own input (``_launch_forward``)
+
+    def _launch_backward(self, sv, dl, part="all", dfc=None):
+        """``dfc`` (address, optional): d(loss)/d(fc_emb) from outside the decoder (encoder-level distillation), added to
+        the decoder's own ``bah_dfc`` before it is spread over the frames; ``dl`` None: no gradient on ``logit`` - the
+        decoder's backward is skipped, its gradients stay exactly zero."""
         if part != "all":
             raise NotImplementedError("AttnGruTrainEngine: the backward runs in one piece")
         lib, fp, dec = self.lib, self.flat, self.model.decoder
@@ -123,9 +131,24 @@ class AttnGruTrainEngine(TrainEngine):
         dout = ws.f("gru_dout", N * Tq, A)        # where _launch_backward_gru reads d(loss)/d(GRU output)
         d_fc = ws.f("bah_dfc", N, A)
         saved = sv.pop("bah")["saved"]
-        dec.train_backward(saved, dl, dec.grad_struct(lambda name: fp.g("decoder." + name)), dout, d_fc)
+        if dl is not None:
+            dec.train_backward(saved, dl, dec.grad_struct(lambda name: fp.g("decoder." + name)), dout, d_fc)
+        else:
+            ws.tensor("gru_dout")[:N * Tq * A].zero_()
+            ws.tensor("bah_dfc")[:N * A].zero_()
+        if dfc is not None:
+            check(lib.ac_scatter_add_rows(dfc, self._clip_rows(sv), d_fc, N, A, s), "ac_scatter_add_rows(dfc_emb)")
         check(lib.ac_bah_mean_lens_bwd(d_fc, saved["len"].data_ptr(), dout, N, Tq, A, A, s), "ac_bah_mean_lens_bwd")
         self._launch_backward_gru(sv)
+
+    def _clip_rows(self, sv):
+        """0 .. N-1 on the device (the identity row table of the ``dfc_emb`` add), built once per batch shape."""
+        if sv.get("clip_rows") is None:
+            sv["clip_rows"] = torch.arange(sv["N"], dtype=torch.int32, device=sv["cap"].device)
+        return sv["clip_rows"].data_ptr()
+
+    def _launch_backward_fc(self, sv, dl, dfc):
+        self._launch_backward(sv, dl, dfc=dfc)
 
     def rollout(self, input_dict):
         """The sampled rollout of self-critical sequence training, ``TrainEngine.rollout``'s contract: the train-mode encoder
@@ -196,5 +219,5 @@ def train_forward(model, input_dict):
     out["sampled_logprob"] = out["sampled_logprob"].cpu()
     # a model in eval() or under no_grad: plain logits, no bridge node
     if model.training and torch.is_grad_enabled():
-        out["logit"] = _TrainBridge.apply(engine, out["logit"], *engine.flat.params)
+        out["logit"], out["fc_emb"] = _TrainBridgeFc.apply(engine, out["logit"], out["fc_emb"], *engine.flat.params)
     return out

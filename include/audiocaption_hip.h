@@ -770,6 +770,30 @@ int ac_scst_loss(const float* logit, const int* seq, long seq_ld, const float* r
 int ac_kd_loss(const float* logit, const float* tchr_logit, const long long* tgt, long tgt_ld, const int* tgt_len, int N,
                int T, int V, float smoothing, float temp, float sup_weight, float inv_count, float* row_sup, float* row_kd,
                float* loss, float* dlogit, float gscale, const float* gscale_dev, void* stream);
+/* ---- encoder-level knowledge distillation (kd_wrapper.py:56-226, hf_wrapper.py:1095-1111; csrc/enc_kd.hip) ----------
+ * ac_enc_kd_loss: the loss head of MseEncoderKdWrapper / ContraEncoderKdWrapper / ContraMseEncoderKdWrapper behind the two
+ * projections, forward and backward in f32 (replaces F.normalize, the similarity product, the two F.cross_entropy, F.mse_loss
+ * and their autograd: kd_wrapper.py:105-109, 147-155, 210-224).  s [B][ld_s] / t [B][ld_t]: the student's / teacher's
+ * projected embedding, width D; kind = AC_ENC_KD_CONTRA and / or AC_ENC_KD_MSE, AC_ENC_KD_L2NORM = the MSE term on the
+ * normalised rows (l2_norm=True).  With n(x) = x / max(||x||_2, 1e-12):
+ *   loss[1] = 0.5 * (CE(L, diag) + CE(L^T, diag)), each a mean over B, L = logit_scale[0] * n(s) n(t)^T (logit_scale is one
+ *             float in device memory, used as it is, not exponentiated); 0 without AC_ENC_KD_CONTRA;
+ *   loss[2] = mean over B*D of (a - b)^2, (a, b) = (n(s), n(t)) with AC_ENC_KD_L2NORM, (s, t) without; 0 without AC_ENC_KD_MSE;
+ *   loss[0] = loss[1] + loss[2].
+ * ds / dt [B][D] (dense) and dscale[1] (each optional) are WRITTEN with gscale [* gscale_dev[0]] times the gradient of
+ * loss[0]; dscale[0] = 0 without AC_ENC_KD_CONTRA.  A row below the 1e-12 clamp gets dy / 1e-12; a row is normalised once
+ * (kd_wrapper.py:216 normalises a second time, which changes neither value nor gradient above the clamp).  The soft-maxes
+ * are max-subtracted.  No atomics (bit-identical on every call), no host synchronisation, at most four launches (two
+ * without AC_ENC_KD_CONTRA).  1 <= B <= 512, 1 <= D <= 4096, ld_s, ld_t >= D, any 4-byte aligned base pointers, gscale
+ * finite; everything else is AC_ERR_ARG before anything is launched.  ws: ac_enc_kd_workspace_floats(B, D) floats (-1 for a
+ * B or D out of range), owned by the caller. */
+#define AC_ENC_KD_CONTRA 1
+#define AC_ENC_KD_MSE 2
+#define AC_ENC_KD_L2NORM 4
+long ac_enc_kd_workspace_floats(int B, int D);
+int ac_enc_kd_loss(const float* s, long ld_s, const float* t, long ld_t, int B, int D, int kind, const float* logit_scale,
+                   float* loss, float* ds, float* dt, float* dscale, float gscale, const float* gscale_dev, float* ws,
+                   void* stream);
 /* ---- CIDEr-D on token ids (csrc/cider.hip): the SCST reward without a trip through the host -----------------------
  * The metric as pycocoevalcap's cider_scorer.py computes it (n-grams of 1 .. order words, order = 4 and sigma = 6 there;
  * document frequencies counted over the keys of THIS call's references, hypotheses not counted):
