@@ -14,10 +14,11 @@ from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
 from .cider import Cider
 from .caption_metrics import Bleu, Rouge
+from .diversity import Diversity
 from .kd_loss import SupKdLoss, TokenLevelKdLoss
 from .kd_wrapper import ContraEncoderKdWrapper, ContraMseEncoderKdWrapper, MseEncoderKdWrapper
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
            "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
-           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "TokenLevelKdLoss", "SupKdLoss",
+           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
            "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config"]

@@ -170,6 +170,9 @@ SIGNATURES = {
                             _P]),
     "ac_rouge_l_scores": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _I, _P, _I, _P, _P, _P, _L, _P, _P, _P,
                                _P]),
+    # Self-BLEU, distinct n-grams and richness on token ids (csrc/diversity.hip)
+    "ac_diversity_workspace_bytes": (_L, [_I, _I]),
+    "ac_diversity_scores": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "ac_gru_layer_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_gru_layer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_swa_update": (_I, [_P, _P, _L, _I, _P]),

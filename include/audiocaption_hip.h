@@ -858,6 +858,32 @@ int ac_rouge_l_scores(const int* const* hyp, int sets, long hyp_ld, int N, int T
                       int sentences, int max_ref_words, const int* key_off, int keys, const int* row_key,
                       const int* first_row, void* workspace, long workspace_bytes, int* lcs, double* scores, double* mean,
                       void* stream);
+/* ---- Diversity of a set of captions on token ids (csrc/diversity.hip): Self-BLEU, distinct n-grams, richness ----------
+ * hyp: ONE plane of device memory, int32 [N][hyp_ld], T (1 .. AC_CIDER_MAX_HYP_WORDS) words per row, 2 <= N,
+ * N * T <= 2^26.  The sentence of a row follows the rule of ac_cider_scores: start_idx skipped, cut at the first end_idx,
+ * each word w range-checked against [0, vocab_size) and then replaced by canon[w] (device, int32 [vocab_size]); a word
+ * outside the range is never used as an index and makes EVERY float output of the call NaN and every integer output -1.
+ * With c_i(g) the occurrences of n-gram g (n = 1 .. 4) in sentence i of L_i words:
+ *   Self-BLEU of sentence i = nltk's sentence_bleu(all other sentences, sentence i, weights 1/4 each, smoothing method1):
+ *     num[n] = sum over the distinct g of i of min(c_i(g), max_{j != i} c_j(g));  den[n] = max(1, L_i - n + 1 or 0);
+ *     ref_len = the length among the OTHER sentences closest to L_i, of two equally close the smaller;
+ *     0 when num[1] == 0; else bp * exp(sum_n 0.25 * log(p[n])), p[n] = num[n] / den[n], or 0.1 / den[n] when num[n] == 0,
+ *     bp = 1 when L_i > ref_len, else exp(1 - ref_len / L_i);
+ *   richness[n] = mean over the sentences with an n-gram of (mean over the sentence's distinct g of log(1 / (docs(g) / N))),
+ *     docs(g) the sentences that contain g (NaN when no sentence has an n-gram); richness = sum_n richness[n] * 0.25.
+ * Outputs, all in device memory:
+ *   stats         int32 [N][10] = L_i, ref_len, den[4], num[4]
+ *   sent_distinct int32 [N][4]  = distinct n-grams of sentence i, n = 1 .. 4
+ *   totals        int32 [5]     = total words, distinct n-grams of the corpus for n = 1 .. 4
+ *   self_bleu     f64 [N]
+ *   summary       f64 [6]       = mean Self-BLEU, richness[1 .. 4], richness
+ * workspace: 256-byte aligned, ac_diversity_workspace_bytes(N, T) bytes (a multiple of 256; AC_ERR_ARG beyond the limits
+ * above).  Whole n-grams are compared word by word in one table, every count is an integer, float64 enters in the closed
+ * formulas above and in sums of fixed order: a call is bitwise repeatable.  AC_ERR_ARG beyond any limit, nothing launched. */
+long ac_diversity_workspace_bytes(int N, int T);
+int ac_diversity_scores(const int* hyp, long hyp_ld, int N, int T, int start_idx, int end_idx, const int* canon,
+                        int vocab_size, void* workspace, long workspace_bytes, int* stats, int* sent_distinct, int* totals,
+                        double* self_bleu, double* summary, void* stream);
 /* ac_gru_layer that also keeps (r, z, n, W_hn h + b_hn) per (clip, step, direction): save [B][T][2][4H]. */
 int ac_gru_layer_train(const float* gx, const float* whhT, const float* bhh, const int* lens, float* out, float* save,
                        int B, int T, int hidden, void* stream);
