@@ -7,8 +7,10 @@ from .crnn_trm_encoder import Cnn14RnnEncoder, CrnnEncoder
 from .rnn_encoder import RnnEncoder
 from .transformer_decoder import TransformerDecoder
 from .transformer_model import CaptionModel, TransformerModel
-from .rnn_decoder import BahAttnCatFcDecoder, RnnDecoder, Seq2SeqAttention, TemporalBahAttnDecoder
-from .attn_model import Seq2SeqAttnModel, TemporalSeq2SeqAttnModel
+from .rnn_decoder import (BahAttnCatFcDecoder, ConditionalBahAttnDecoder, RnnDecoder, Seq2SeqAttention,
+                          SpecificityBahAttnDecoder, TemporalBahAttnDecoder)
+from .attn_model import ConditionalSeq2SeqAttnModel, Seq2SeqAttnModel, TemporalSeq2SeqAttnModel
+from .loss import SpecificityLossWrapper
 from .sed_model import Cnn8rnnSedModel
 from .ensemble import EnsembleModel
 from .rl_model import ScstWrapper
@@ -20,5 +22,6 @@ from .kd_wrapper import ContraEncoderKdWrapper, ContraMseEncoderKdWrapper, MseEn
 
 __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "TransformerDecoder",
            "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
-           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
+           "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "ConditionalBahAttnDecoder", "SpecificityBahAttnDecoder",
+           "ConditionalSeq2SeqAttnModel", "SpecificityLossWrapper", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
            "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config"]

@@ -34,7 +34,7 @@ class AcTrmWeights(ctypes.Structure):
 
 class AcBahWeights(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
-        "emb_dim", "d_model", "attn_size", "attn_emb_dim", "fc_emb_dim", "vocab", "n_tags", "reserved")] + [
+        "emb_dim", "d_model", "attn_size", "attn_emb_dim", "fc_emb_dim", "vocab", "n_tags", "variant")] + [
         (n, ctypes.c_void_p) for n in ("emb", "temb", "w_ih", "w_hh", "b_ih", "b_hh", "attn_w", "attn_b", "attn_v",
                                        "fc_w", "fc_b", "ctx_w", "ctx_b", "cls_w", "cls_b")]
 
@@ -110,6 +110,7 @@ SIGNATURES = {
     # Bahdanau-attention GRU decoder (csrc/attn_gru.hip)
     "ac_bah_workspace_floats": (_L, [_BP, _I, _I, _I, _I]),
     "ac_bah_memory": (_I, [_BP, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ac_bah_memory_cond": (_I, [_BP, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ac_bah_step_logits": (_I, [_BP, _P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _P, _P]),
     "ac_bah_greedy": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_bah_sample": (_I, [_BP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
@@ -121,7 +122,13 @@ SIGNATURES = {
     "ac_bah_train_rollout": (_I, [_BP, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _L, _F, _U64, _P, _P, _P, _P, _P, _P, _P,
                                   _P, _P, _P]),
     "ac_bah_train_backward": (_I, [_BP, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),
+    "ac_bah_train_forward_cond": (_I, [_BP, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P]),
+    "ac_bah_train_backward_cond": (_I, [_BP, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),
     "ac_bah_mean_lens_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    # specificity loss (csrc/spec_loss.hip)
+    "ac_specificity_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "ac_specificity_loss_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     # sound-event tagger (csrc/sed.hip)
     "ac_pool_avgmax": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ac_sed_head": (_I, [_P, _P, _P, _P, _L, _I, _P]),

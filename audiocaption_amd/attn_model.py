@@ -27,6 +27,11 @@ Self-critical sequence training: ``rl_model.ScstWrapper`` wraps these models ove
 this file's greedy search (with ``_seq_on_device`` the result also carries ``seq_dev``, the decoder's device copy of the
 words); its sampled rollout is ``AttnGruTrainEngine.rollout``.
 
+``ConditionalSeq2SeqAttnModel`` (attn_model.py:191-223) over a ``ConditionalBahAttnDecoder`` or a
+``SpecificityBahAttnDecoder``: ``input_dict["condition"]`` holds one float per clip (required; any finite value) and goes
+once per batch into the decoder's ``memory`` - the beam rows of a clip share it.  Greedy, sampled and beam search and
+``mode="train"`` as above; ``ScstWrapper``, ``EnsembleModel`` membership, ``dbs`` and ``forward_async`` are refused.
+
 Not on this path (NotImplementedError): ``sample_method="dbs"`` (the reference's own diverse beam search raises for both
 attention models), ``mode="train"`` and SCST over any other encoder, ``forward_async``, the fused ``TrainEngine.step`` and
 knowledge distillation for these models; ``EnsembleModel`` takes ``TransformerModel`` members only.
@@ -38,7 +43,8 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
-from .rnn_decoder import BahAttnCatFcDecoder, TemporalBahAttnDecoder, check_temporal_tag
+from .rnn_decoder import (BahAttnCatFcDecoder, ConditionalBahAttnDecoder, SpecificityBahAttnDecoder, TemporalBahAttnDecoder,
+                          check_condition, check_temporal_tag)
 from .transformer_model import CaptionModel
 from . import kernels as K
 
@@ -51,6 +57,8 @@ class Seq2SeqAttnModel(CaptionModel):
         super().__init__(encoder, decoder, **kwargs)
         if decoder.n_tags and not isinstance(self, TemporalSeq2SeqAttnModel):
             raise NotImplementedError("a TemporalBahAttnDecoder needs temporal_tag: wrap it in TemporalSeq2SeqAttnModel")
+        if decoder.variant and not isinstance(self, ConditionalSeq2SeqAttnModel):
+            raise NotImplementedError(f"a {type(decoder).__name__} needs condition: wrap it in ConditionalSeq2SeqAttnModel")
 
     def forward(self, input_dict):
         if input_dict["mode"] == "train":
@@ -87,12 +95,16 @@ class Seq2SeqAttnModel(CaptionModel):
         """The clips' temporal tags, validated, on the host (None: the decoder takes none)."""
         return None
 
+    def _side(self, input_dict):
+        """What the decoder's ``memory`` takes next to the audio memory."""
+        return input_dict["fc_emb"]
+
     # ---- greedy / sampling (base.py:152-218 with attn_model.py:60-92) -----------------------------------------
     def _stepwise(self, input_dict, sampler=None):
         dec = self.decoder
         attn_emb = input_dict["attn_emb"]
         tags = self._tags(input_dict, attn_emb.shape[0])
-        mem = dec.memory(attn_emb, input_dict["fc_emb"], input_dict["attn_emb_len"], 1, int(input_dict["max_length"]))
+        mem = dec.memory(attn_emb, self._side(input_dict), input_dict["attn_emb_len"], 1, int(input_dict["max_length"]))
         if tags is not None:
             tags = K.upload(tags, attn_emb.device, torch.int32)
         if sampler is None:
@@ -131,7 +143,7 @@ class Seq2SeqAttnModel(CaptionModel):
             raise ValueError(f"beam search needs a finite temp > 0 (got {temp})")
         V, d, R, ld, cap = self.vocab_size, dec.d_model, B * beam, L + 1, beam * L
         tags = self._tags(input_dict, B)
-        mem = dec.memory(attn_emb, input_dict["fc_emb"], input_dict["attn_emb_len"], beam, L)
+        mem = dec.memory(attn_emb, self._side(input_dict), input_dict["attn_emb_len"], beam, L)
         if tags is not None:
             tags = K.upload(tags, dev, torch.int32)
         i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
@@ -200,3 +212,23 @@ class TemporalSeq2SeqAttnModel(Seq2SeqAttnModel):
 
     def _tags(self, input_dict, B):
         return check_temporal_tag(input_dict.get("temporal_tag"), B)
+
+
+class ConditionalSeq2SeqAttnModel(Seq2SeqAttnModel):
+    """``Seq2SeqAttnModel`` over a condition-controlled decoder: ``input_dict["condition"]`` holds one float per clip, fed to
+    every decoder step (attn_model.py:191-223)."""
+
+    compatible_decoders = (ConditionalBahAttnDecoder, SpecificityBahAttnDecoder)
+
+    def __init__(self, encoder, decoder, **kwargs):
+        super().__init__(encoder, decoder, **kwargs)
+        self.train_forward_keys.append("condition")
+        self.inference_forward_keys.append("condition")
+
+    def _inference_dict(self, input_dict, encoder_output_dict):
+        forward_dict = super()._inference_dict(input_dict, encoder_output_dict)
+        forward_dict["condition"] = input_dict.get("condition")
+        return forward_dict
+
+    def _side(self, input_dict):
+        return check_condition(input_dict.get("condition"), input_dict["attn_emb"].shape[0])

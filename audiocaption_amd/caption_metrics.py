@@ -149,3 +149,15 @@ def eval_prediction(key2refs, key2pred, scorers, per_audio=False):
                 scores = scores[min(3, len(scores) - 1)]
             output["per_audio"][name] = dict(zip(key2refs.keys(), scores))
     return output
+
+
+def specificity(predictions, word_to_specificity):
+    """The reference's specificity score (python_scripts/eval/specificity.py:13-22), on the host: the mean over
+    ``predictions`` of the summed specificities of a caption's whitespace-separated words.  ``predictions``: captions as
+    strings, or the ``{"tokens": caption}`` records of the reference's prediction files.  A word that is not in
+    ``word_to_specificity`` raises KeyError, as there."""
+    totals = []
+    for prediction in predictions:
+        caption = prediction["tokens"] if isinstance(prediction, dict) else prediction
+        totals.append(sum(word_to_specificity[word] for word in caption.split()))
+    return sum(totals) / len(totals)

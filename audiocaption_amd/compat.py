@@ -27,14 +27,14 @@ HOT_MODULES = {
 }
 # single classes patched into (or stubbed for) modules that also hold things outside the path
 HOT_CLASSES = {
-    "captioning.losses.loss": ("audiocaption_amd.loss", ["LabelSmoothingLoss"]),
+    "captioning.losses.loss": ("audiocaption_amd.loss", ["LabelSmoothingLoss", "SpecificityLossWrapper"]),
     "captioning.losses.kd_loss": ("audiocaption_amd.kd_loss", ["TokenLevelKdLoss", "SupKdLoss"]),
     "captioning.utils.lr_scheduler": ("audiocaption_amd.lr_scheduler", ["ExponentialDecayScheduler"]),
 }
 
 
 def install(training=True):
-    """``training``: also route ``LabelSmoothingLoss``, the token-level distillation losses (``TokenLevelKdLoss``,
+    """``training``: also route ``LabelSmoothingLoss``, ``SpecificityLossWrapper``, the token-level distillation losses (``TokenLevelKdLoss``,
     ``SupKdLoss``) and ``ExponentialDecayScheduler`` (the reference's own scheduler cannot be constructed on torch >= 2.2,
     lr_scheduler.py:16) to this package."""
     for pkg in ("captioning", "captioning.models", "captioning.losses", "captioning.utils"):

@@ -23,6 +23,10 @@ ALIASES = {
     "captioning.models.crnn_trm_encoder.Cnn14TransformerEncoder": "audiocaption_amd.crnn_trm_encoder.Cnn14TransformerEncoder",
     "captioning.models.rl_model.ScstWrapper": "audiocaption_amd.rl_model.ScstWrapper",
     "captioning.losses.loss.LabelSmoothingLoss": "audiocaption_amd.loss.LabelSmoothingLoss",
+    "captioning.models.attn_model.ConditionalSeq2SeqAttnModel": "audiocaption_amd.attn_model.ConditionalSeq2SeqAttnModel",
+    "captioning.models.rnn_decoder.ConditionalBahAttnDecoder": "audiocaption_amd.rnn_decoder.ConditionalBahAttnDecoder",
+    "captioning.models.rnn_decoder.SpecificityBahAttnDecoder": "audiocaption_amd.rnn_decoder.SpecificityBahAttnDecoder",
+    "captioning.losses.loss.SpecificityLossWrapper": "audiocaption_amd.loss.SpecificityLossWrapper",
     "captioning.utils.lr_scheduler.ExponentialDecayScheduler": "audiocaption_amd.lr_scheduler.ExponentialDecayScheduler",
 }
 

@@ -16,6 +16,17 @@
 // ek (the key projection W_enc attn_emb + b_attn) and gf (the fc part of the input gates, W_ih[:, 2E:3E] fc_proj(fc_emb) +
 // b_ih) do not depend on the step: ac_bah_memory computes them once per batch.  No other algebraic fold is used.
 // tanhf / expf are the accurate library forms; no cross-workgroup waits anywhere.
+//
+// The condition-controlled decoders (ConditionalBahAttnDecoder rnn_decoder.py:276-336, SpecificityBahAttnDecoder :519-575)
+// are the same chain under ac_bah_weights.variant (ac_bah.h); one float per clip, cond, takes fc_emb's place and
+// ac_bah_memory_cond computes their gf:
+//   BAH_COND   gf = W_ih[:, 2E:3E] ((1 - cond) W_c[0] + cond W_c[1]) + b_ih; the step is unchanged
+//   BAH_SPEC   xin = [embed | c] is [R][E + A]: the attention kernel writes the context straight into it, there is no
+//              ctx_proj product, gi = xin W_ih[:, :E+A]^T, and gf = cond W_ih[:, E+A] + b_ih.
+// weight_ih_l0 of BAH_SPEC has the odd row pitch E + A + 1, which would put the gi product on ac_gemm's unaligned general
+// kernel.  The host therefore repacks it whenever it rebuilds the struct (rnn_decoder.py weights()): w_ih is an aligned
+// [3d][E + A] block and fc_w the [3d] last column.  The training backward writes the gradient into the parameter's real
+// layout (ac_gemm's C stores are scalar, any ldc).
 #include "ac_bah.h"
 
 namespace {
@@ -23,7 +34,7 @@ namespace {
 // The workspace, in floats: the once-per-batch part (ek, gf), the per-step buffers, the buffers of a whole search.
 struct BahWs {
   float *ek, *pfc, *gf;          // [B*Tm][S], [B][E], [B][3d]
-  float *hg, *ctx, *xin, *gi;    // [R][S + 3d], [R][A], [R][2E], [R][3d]
+  float *hg, *ctx, *xin, *gi;    // [R][S + 3d], [R][A], [R][bah_xw], [R][3d]
   float* state[2];               // [R][d] each
   int *tok, *unfinished;         // [R][max_len + 1], [R]
   unsigned char* mask;           // [R][max_len + 1]
@@ -40,7 +51,7 @@ BahWs bah_carve(const ac_bah_weights* w, float* base, int B, int R, int Tm, int 
   s.gf = take((size_t)B * 3 * d);
   s.hg = take((size_t)R * (S + 3 * d));
   s.ctx = take((size_t)R * A);
-  s.xin = take((size_t)R * 2 * E);
+  s.xin = take((size_t)R * bah_xw(w));
   s.gi = take((size_t)R * 3 * d);
   s.state[0] = take((size_t)R * d);
   s.state[1] = take((size_t)R * d);
@@ -59,7 +70,8 @@ struct AttnP {
   const int* words; long word_stride;
   const int* tags;                   // [B] or null
   const int* stop;                   // null, or a word that reads 0 once the search is over
-  float *ctx, *xin;                  // [R][A], [R][2E]
+  float *ctx; long ld_ctx;           // row r's context at ctx + r * ld_ctx, A values
+  float *xin; long ld_xin;           // row r's input embedding at xin + r * ld_xin, E values
   float* attn_out; long attn_row, attn_frame;   // weight of (row r, frame t) at attn_out + r * attn_row + t * attn_frame
   int row_div, Tm, S, A, E, V, n_tags;
 };
@@ -91,7 +103,7 @@ __global__ __launch_bounds__(256) void bah_attn_kernel(AttnP p) {
       wd = wd < 0 ? 0 : (wd >= p.V ? p.V - 1 : wd);
       src = p.emb + (size_t)wd * p.E;
     }
-    for (int e = tid; e < p.E; e += 256) p.xin[(size_t)r * 2 * p.E + e] = src[e];
+    for (int e = tid; e < p.E; e += 256) p.xin[(size_t)r * p.ld_xin + e] = src[e];
   }
   __syncthreads();
   const float* ek = p.ek + (size_t)clip * p.Tm * p.S;
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(256) void bah_attn_kernel(AttnP p) {
   for (int a = tid; a < p.A; a += 256) {
     float acc = 0.f;
     for (int t = 0; t < nt; ++t) acc = fmaf(s_w[t], mem[(size_t)t * p.A + a], acc);
-    p.ctx[(size_t)r * p.A + a] = acc;
+    p.ctx[(size_t)r * p.ld_ctx + a] = acc;
   }
 }
 
@@ -170,19 +182,20 @@ struct StepIo {
 int bah_step(const ac_bah_weights* w, const BahWs& s, const float* attn_emb, const int* mem_len, int R, int row_div, int Tm,
              const StepIo& io, void* stream) {
   const int E = w->emb_dim, d = w->d_model, S = w->attn_size, A = w->attn_emb_dim, V = w->vocab;
-  const long ld_hg = S + 3L * d;
+  const long ld_hg = S + 3L * d, xw = bah_xw(w);
+  const bool spec = w->variant == BAH_SPEC;
   // W_h h (the decoder-state columns of h2attn come first, hf_wrapper.py:1401) and W_hh h + b_hh
   if (gemm(io.state_in, d, w->attn_w, d + A, nullptr, s.hg, ld_hg, R, S, d, stream) != AC_OK) return AC_ERR_LAUNCH;
   if (gemm(io.state_in, d, w->w_hh, d, w->b_hh, s.hg + S, ld_hg, R, 3 * d, d, stream) != AC_OK) return AC_ERR_LAUNCH;
   AttnP a;
   a.hg = s.hg; a.ld_hg = ld_hg; a.ek = s.ek; a.attn_emb = attn_emb; a.v = w->attn_v; a.mem_len = mem_len;
   a.emb = w->emb; a.temb = w->temb; a.words = io.words; a.word_stride = io.word_stride; a.tags = io.tags; a.stop = io.stop;
-  a.ctx = s.ctx; a.xin = s.xin; a.attn_out = io.attn_out; a.attn_row = io.attn_row; a.attn_frame = io.attn_frame;
+  a.ctx = spec ? s.xin + E : s.ctx; a.ld_ctx = spec ? xw : A; a.xin = s.xin; a.ld_xin = xw; a.attn_out = io.attn_out; a.attn_row = io.attn_row; a.attn_frame = io.attn_frame;
   a.row_div = row_div; a.Tm = Tm; a.S = S; a.A = A; a.E = E; a.V = V; a.n_tags = w->n_tags;
   hipLaunchKernelGGL(bah_attn_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, a);
   if (ac_check_launch() != AC_OK) return AC_ERR_LAUNCH;
-  if (gemm(s.ctx, A, w->ctx_w, A, w->ctx_b, s.xin + E, 2L * E, R, E, A, stream) != AC_OK) return AC_ERR_LAUNCH;
-  if (gemm(s.xin, 2L * E, w->w_ih, 3L * E, nullptr, s.gi, 3L * d, R, 3 * d, 2 * E, stream) != AC_OK) return AC_ERR_LAUNCH;
+  if (!spec && gemm(s.ctx, A, w->ctx_w, A, w->ctx_b, s.xin + E, xw, R, E, A, stream) != AC_OK) return AC_ERR_LAUNCH;
+  if (gemm(s.xin, xw, w->w_ih, bah_ld_ih(w), nullptr, s.gi, 3L * d, R, 3 * d, (int)xw, stream) != AC_OK) return AC_ERR_LAUNCH;
   GateP g;
   g.gi = s.gi; g.gf = s.gf; g.hg = s.hg + S; g.ld_hg = ld_hg; g.h_in = io.state_in; g.h_out = io.state_out;
   g.embed = io.embed; g.ld_embed = io.ld_embed; g.stop = io.stop; g.R = R; g.d = d; g.row_div = row_div;
@@ -314,7 +327,8 @@ long ac_bah_workspace_floats(const ac_bah_weights* w, int B, int R, int Tm, int 
 
 int ac_bah_memory(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, int B, int R, int Tm, int max_len,
                   float* ws, void* stream) {
-  if (!bah_shape_ok(w) || !attn_emb || !fc_emb || !ws || B <= 0 || R < B || Tm <= 0 || Tm > BAH_MAX_TM || max_len <= 0)
+  if (!bah_shape_ok(w) || w->variant != BAH_CATFC || !attn_emb || !fc_emb || !ws || B <= 0 || R < B || Tm <= 0 ||
+      Tm > BAH_MAX_TM || max_len <= 0)
     return AC_ERR_ARG;
   const int E = w->emb_dim, d = w->d_model, S = w->attn_size, A = w->attn_emb_dim, F = w->fc_emb_dim;
   const BahWs c = bah_carve(w, ws, B, R, Tm, max_len);
@@ -322,6 +336,17 @@ int ac_bah_memory(const ac_bah_weights* w, const float* attn_emb, const float* f
   if (gemm(attn_emb, A, w->attn_w + d, d + A, w->attn_b, c.ek, S, B * Tm, S, A, stream) != AC_OK) return AC_ERR_LAUNCH;
   if (gemm(fc_emb, F, w->fc_w, F, w->fc_b, c.pfc, E, B, E, F, stream) != AC_OK) return AC_ERR_LAUNCH;
   return gemm(c.pfc, E, w->w_ih + 2 * E, 3L * E, w->b_ih, c.gf, 3L * d, B, 3 * d, E, stream);
+}
+
+int ac_bah_memory_cond(const ac_bah_weights* w, const float* attn_emb, const float* cond, int B, int R, int Tm, int max_len,
+                       float* ws, void* stream) {
+  if (!bah_shape_ok(w) || w->variant == BAH_CATFC || !attn_emb || !cond || !ws || B <= 0 || R < B || Tm <= 0 ||
+      Tm > BAH_MAX_TM || max_len <= 0)
+    return AC_ERR_ARG;
+  const int d = w->d_model, S = w->attn_size, A = w->attn_emb_dim;
+  const BahWs c = bah_carve(w, ws, B, R, Tm, max_len);
+  if (gemm(attn_emb, A, w->attn_w + d, d + A, w->attn_b, c.ek, S, B * Tm, S, A, stream) != AC_OK) return AC_ERR_LAUNCH;
+  return bah_cond_gates(w, cond, c.pfc, c.gf, B, stream);
 }
 
 int ac_bah_step_logits(const ac_bah_weights* w, const float* attn_emb, const int* mem_len, int B, int R, int row_div,

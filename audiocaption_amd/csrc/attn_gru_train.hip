@@ -26,6 +26,15 @@
 // recurrence (dlogit W_cls in front; every weight gradient, bias column sum and the embedding scatter behind) runs once
 // over all B T rows.  The per-step products have M = B rows and run in exact f32 like bah_step's; the products over all
 // rows go through ac_gemm_bf16x3, which keeps the small ones on the exact-f32 kernels.
+//
+// The condition-controlled variants (ac_bah.h; ac_bah_train_forward_cond / ac_bah_train_backward_cond, cond [B] in fc_emb's
+// place) run the same chain with xin bah_xw(w) wide.  BAH_SPEC has no ctx_proj: the context is xin[:, E:E+A], dctx is that
+// slice of dxin.  Their own gradients, all off the recurrence, from dgf = sum_t dgi[t]:
+//   BAH_COND   d cond_emb = dgf W_ih[:, 2E:3E];  d condition_embedding.weight[k] += sum_b ([1 - c_b, c_b][k]) d cond_emb[b]
+//   BAH_SPEC   d W_ih[:, E+A] += sum_b c_b dgf[b]
+// Neither reads fc_emb (d_fc_emb is written as zeros) and cond is data (no gradient).  W_ih of BAH_SPEC is read from the
+// host's aligned [3d][E+A] pack; its gradient goes into the parameter's real layout: g->w_ih [3d][E+A+1] with the odd pitch
+// as ldc of the weight-gradient product, g->fc_w = g->w_ih + E + A the last column, pitch E+A+1.
 #include "ac_bah.h"
 #include "ac_drop.h"
 
@@ -36,10 +45,10 @@ constexpr int BAH_KMAX = BAH_MAX_DIM / 64;   // attention columns a lane of a 64
 // The workspace, in floats: the once-per-batch part, what the forward keeps, what the backward fills.
 struct TrainWs {
   float *ek, *pfc, *gf;                                   // [B*Tm][S], [B][E], [B][3d]
-  float *hg, *w, *ctx, *xin, *gates, *h_all, *embed, *gi; // [T][B][S+3d], [T][B][Tm], [T][B][A], [T][B][2E], [T][B][3d],
+  float *hg, *w, *ctx, *xin, *gates, *h_all, *embed, *gi; // [T][B][S+3d], [T][B][Tm], [T][B][A], [T][B][xw], [T][B][3d],
                                                           // [T+1][B][d], [B][T][d], [B][3d]
   int* tok;                                               // [T][B]: the input word; -1 - tag at the tag step
-  float *dhc, *dgi, *dgh, *dxin, *dq, *dv;                // [B][T][d], [T][B][3d] x 2, [T][B][2E], [T][B][S] x 2
+  float *dhc, *dgi, *dgh, *dxin, *dq, *dv;                // [B][T][d], [T][B][3d] x 2, [T][B][xw], [T][B][S] x 2
   float *dctx, *dh, *dek, *dgf, *dpfc;                    // [B][A], [B][d], [B*Tm][S], [B][3d], [B][E]
   size_t total;
 };
@@ -56,7 +65,7 @@ TrainWs train_carve(const ac_bah_weights* w, float* base, int B, int Tm, int T) 
   s.hg = take(R * (S + 3 * d));
   s.w = take(R * Tm);
   s.ctx = take(R * A);
-  s.xin = take(R * 2 * E);
+  s.xin = take(R * bah_xw(w));
   s.gates = take(R * 3 * d);
   s.h_all = take((R + B) * d);
   s.embed = take(R * d);
@@ -65,7 +74,7 @@ TrainWs train_carve(const ac_bah_weights* w, float* base, int B, int Tm, int T) 
   s.dhc = take(R * d);
   s.dgi = take(R * 3 * d);
   s.dgh = take(R * 3 * d);
-  s.dxin = take(R * 2 * E);
+  s.dxin = take(R * bah_xw(w));
   s.dq = take(R * S);
   s.dv = take(R * S);
   s.dctx = take((size_t)B * A);
@@ -90,7 +99,9 @@ struct TAttnP {
   const int64_t* seq;                    // [B][T]: the arg-max of the steps so far
   const int* words; long words_ld;       // rollout: [B][words_ld], the words ac_scst_pick stored; null otherwise
   int* tok;                              // this step's [B]
-  float *ctx, *xin, *w;                  // this step's [B][A], [B][2E], [B][Tm]
+  float *ctx; long ld_ctx;               // this step's context of clip b at ctx + b * ld_ctx, A values
+  float *xin; long ld_xin;               // this step's input embedding of clip b at xin + b * ld_xin, E values
+  float* w;                              // this step's [B][Tm]
   float* attn_out;                       // weight of (clip b, frame tm) at attn_out + (b * Tm + tm) * T
   Drop drop;
   int use_cap, t, T, B, start_idx, Tm, S, A, E, V, n_tags;
@@ -127,7 +138,7 @@ __global__ __launch_bounds__(256) void bah_train_attn_kernel(TAttnP p) {
     }
     if (tid == 0) p.tok[b] = code;
     const uint64_t i0 = ((uint64_t)p.t * p.B + b) * p.E;    // in_dropout's mask index: (step, clip, feature)
-    for (int e = tid; e < p.E; e += 256) p.xin[(size_t)b * 2 * p.E + e] = src[e] * p.drop.mask(i0 + e);
+    for (int e = tid; e < p.E; e += 256) p.xin[(size_t)b * p.ld_xin + e] = src[e] * p.drop.mask(i0 + e);
   }
   __syncthreads();
   const float* ek = p.ek + (size_t)b * p.Tm * p.S;
@@ -163,7 +174,7 @@ __global__ __launch_bounds__(256) void bah_train_attn_kernel(TAttnP p) {
   for (int a = tid; a < p.A; a += 256) {
     float acc = 0.f;
     for (int t = 0; t < nt; ++t) acc = fmaf(s_w[t], mem[(size_t)t * p.A + a], acc);
-    p.ctx[(size_t)b * p.A + a] = acc;
+    p.ctx[(size_t)b * p.ld_ctx + a] = acc;
   }
 }
 
@@ -256,7 +267,8 @@ __global__ __launch_bounds__(256) void bah_train_gate_bwd_kernel(TGateBP p) {
 
 struct TAttnBP {
   const float* hg; long ld_hg;                   // clip b's W_h h_t
-  const float *ek, *attn_emb, *v, *w, *dctx;     // [B][Tm][S], [B][Tm][A], [S], the step's [B][Tm], [B][A]
+  const float *ek, *attn_emb, *v, *w;            // [B][Tm][S], [B][Tm][A], [S], the step's [B][Tm]
+  const float* dctx; long ld_dctx;               // clip b's d(loss)/d(context) at dctx + b * ld_dctx, A values
   const int* mem_len;
   float *dq, *dv;                                // the step's [B][S]
   float *d_attn_emb, *dek;                       // [B][Tm][A], [B][Tm][S]: accumulated over the steps
@@ -280,7 +292,7 @@ __global__ __launch_bounds__(256) void bah_train_attn_bwd_kernel(TAttnBP p) {
     s_q[a] = p.hg[(size_t)b * p.ld_hg + a];
     s_v[a] = p.v[a];
   }
-  for (int c = tid; c < p.A; c += 256) s_dc[c] = p.dctx[(size_t)b * p.A + c];
+  for (int c = tid; c < p.A; c += 256) s_dc[c] = p.dctx[(size_t)b * p.ld_dctx + c];
   __syncthreads();
   const float* wrow = p.w + (size_t)b * p.Tm;
   const float* mem = p.attn_emb + (size_t)b * p.Tm * p.A;
@@ -346,14 +358,14 @@ __global__ __launch_bounds__(256) void bah_train_attn_bwd_kernel(TAttnBP p) {
 
 // d(word_embedding) / d(temporal_embedding) += dxin[:, :E] * in_dropout's mask, row (step, clip) into the row of its input
 __global__ __launch_bounds__(256) void bah_train_embed_bwd_kernel(const float* dxin, const int* tok, float* demb, float* dtemb,
-                                                                  long rows, int E, Drop drop) {
+                                                                  long rows, int E, long ld_dxin, Drop drop) {
   const long i = blockIdx.x * 256L + threadIdx.x;
   if (i >= rows * E) return;
   const long row = i / E;
   const int e = (int)(i % E);
   const int code = tok[row];
   float* dst = code < 0 ? dtemb + (size_t)(-1 - code) * E : demb + (size_t)code * E;
-  atomicAdd(dst + e, dxin[(size_t)row * 2 * E + e] * drop.mask((uint64_t)i));
+  atomicAdd(dst + e, dxin[(size_t)row * ld_dxin + e] * drop.mask((uint64_t)i));
 }
 
 // backward of fc_emb = mean over the valid frames of attn_emb[:, :, :F]
@@ -405,8 +417,37 @@ bool train_dims_ok(const ac_bah_weights* w, int B, int Tm, int T, float drop_p) 
 }
 
 bool grads_ok(const ac_bah_weights* w, const ac_bah_grads* g) {
-  return g && g->emb && g->w_ih && g->w_hh && g->b_ih && g->b_hh && g->attn_w && g->attn_b && g->attn_v && g->fc_w &&
-         g->fc_b && g->ctx_w && g->ctx_b && g->cls_w && g->cls_b && (!w->n_tags || g->temb);
+  if (!g || !g->emb || !g->w_ih || !g->w_hh || !g->b_ih || !g->b_hh || !g->attn_w || !g->attn_b || !g->attn_v || !g->fc_w ||
+      !g->cls_w || !g->cls_b || (w->n_tags && !g->temb))
+    return false;
+  // a slot the variant does not use is NULL in the gradient struct as it is in the weight struct
+  if (w->variant == BAH_CATFC) return g->fc_b && g->ctx_w && g->ctx_b;
+  if (w->variant == BAH_COND) return !g->fc_b && g->ctx_w && g->ctx_b && !g->temb;
+  return !g->fc_b && !g->ctx_w && !g->ctx_b && !g->temb;
+}
+
+// d condition_embedding.weight [2][E] += [1 - c, c]^T-weighted sum over the clips of d cond_emb [B][E]
+__global__ __launch_bounds__(256) void bah_cond_emb_bwd_kernel(const float* cond, const float* dpfc, float* dcw, int B, int E) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  float a0 = 0.f, a1 = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float c = cond[b], g = dpfc[(size_t)b * E + e];
+    a0 = fmaf(1.0f - c, g, a0);
+    a1 = fmaf(c, g, a1);
+  }
+  dcw[e] += a0;
+  dcw[E + e] += a1;
+}
+
+// d W_ih[:, E + A] (element j at dcol + j * ld) += sum_b c_b dgf[b][j]
+__global__ __launch_bounds__(256) void bah_cond_col_bwd_kernel(const float* cond, const float* dgf, float* dcol, long ld,
+                                                               int B, int n) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  float a = 0.f;
+  for (int b = 0; b < B; ++b) a = fmaf(cond[b], dgf[(size_t)b * n + j], a);
+  dcol[(size_t)j * ld] += a;
 }
 
 #define BAH_TRY(call) do { if ((call) != AC_OK) return AC_ERR_LAUNCH; } while (0)
@@ -422,7 +463,8 @@ struct Rollout {
 };
 
 // The forward chain of T steps; the arguments have been checked.  ro == null: scheduled sampling on cap / the arg-max.
-int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+// `side` is fc_emb [B][F] (BAH_CATFC) or cond [B] (the conditional variants).
+int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const float* side, const int* mem_len,
                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
                         const int64_t* seq_in, int64_t* seq, const Rollout* ro, float* logit, float* logprob, float* embed,
@@ -430,11 +472,16 @@ int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const fl
   const int E = w->emb_dim, d = w->d_model, S = w->attn_size, A = w->attn_emb_dim, F = w->fc_emb_dim, V = w->vocab;
   hipStream_t s = (hipStream_t)stream;
   const TrainWs c = train_carve(w, ws, B, Tm, T);
-  const long ld_hg = S + 3L * d;
-  // once per batch, as ac_bah_memory: the key projection and the fc part of the input gates
+  const long ld_hg = S + 3L * d, xw = bah_xw(w);
+  const bool spec = w->variant == BAH_SPEC;
+  // once per batch, as ac_bah_memory / ac_bah_memory_cond: the key projection and the fc or condition part of the input gates
   BAH_TRY(gemm(attn_emb, A, w->attn_w + d, d + A, w->attn_b, c.ek, S, B * Tm, S, A, stream));
-  BAH_TRY(gemm(fc_emb, F, w->fc_w, F, w->fc_b, c.pfc, E, B, E, F, stream));
-  BAH_TRY(gemm(c.pfc, E, w->w_ih + 2 * E, 3L * E, w->b_ih, c.gf, 3L * d, B, 3 * d, E, stream));
+  if (w->variant == BAH_CATFC) {
+    BAH_TRY(gemm(side, F, w->fc_w, F, w->fc_b, c.pfc, E, B, E, F, stream));
+    BAH_TRY(gemm(c.pfc, E, w->w_ih + 2 * E, 3L * E, w->b_ih, c.gf, 3L * d, B, 3 * d, E, stream));
+  } else {
+    BAH_TRY(bah_cond_gates(w, side, c.pfc, c.gf, B, stream));
+  }
   if (hipMemsetAsync(c.h_all, 0, (size_t)B * d * sizeof(float), s) != hipSuccess) return AC_ERR_LAUNCH;
   const Drop drop = make_drop(drop_p, drop_seed, seed_dev);
   for (int t = 0; t < T; ++t) {
@@ -442,8 +489,9 @@ int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const fl
     const float* h_in = c.h_all + r0 * d;
     float* h_out = c.h_all + (r0 + B) * d;
     float* hg = c.hg + r0 * ld_hg;
-    float* xin = c.xin + r0 * 2 * E;
-    float* ctx = c.ctx + r0 * A;
+    float* xin = c.xin + r0 * xw;
+    float* ctx = spec ? xin + E : c.ctx + r0 * A;
+    const long ld_ctx = spec ? xw : A;
     BAH_TRY(gemm(h_in, d, w->attn_w, d + A, nullptr, hg, ld_hg, B, S, d, stream));
     BAH_TRY(gemm(h_in, d, w->w_hh, d, w->b_hh, hg + S, ld_hg, B, 3 * d, d, stream));
     TAttnP a;
@@ -451,13 +499,13 @@ int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const fl
     a.emb = w->emb; a.temb = w->temb; a.tags = (t == 0 && w->n_tags) ? tags : nullptr;
     a.cap = cap; a.cap_ld = cap_ld; a.seq = seq_in; a.tok = c.tok + r0;
     a.words = ro ? ro->seq : nullptr; a.words_ld = T;
-    a.ctx = ctx; a.xin = xin; a.w = c.w + r0 * Tm; a.attn_out = attn_weight + t; a.drop = drop;
+    a.ctx = ctx; a.ld_ctx = ld_ctx; a.xin = xin; a.ld_xin = xw; a.w = c.w + r0 * Tm; a.attn_out = attn_weight + t; a.drop = drop;
     a.use_cap = ro ? 0 : use_cap[t] != 0; a.t = t; a.T = T; a.B = B; a.start_idx = start_idx;
     a.Tm = Tm; a.S = S; a.A = A; a.E = E; a.V = V; a.n_tags = w->n_tags;
     hipLaunchKernelGGL(bah_train_attn_kernel, dim3(B), dim3(256), 0, s, a);
     BAH_TRY(ac_check_launch());
-    BAH_TRY(gemm(ctx, A, w->ctx_w, A, w->ctx_b, xin + E, 2L * E, B, E, A, stream));
-    BAH_TRY(gemm(xin, 2L * E, w->w_ih, 3L * E, nullptr, c.gi, 3L * d, B, 3 * d, 2 * E, stream));
+    if (!spec) BAH_TRY(gemm(ctx, A, w->ctx_w, A, w->ctx_b, xin + E, xw, B, E, A, stream));
+    BAH_TRY(gemm(xin, xw, w->w_ih, bah_ld_ih(w), nullptr, c.gi, 3L * d, B, 3 * d, (int)xw, stream));
     TGateP g;
     g.gi = c.gi; g.gf = c.gf; g.hg = hg + S; g.ld_hg = ld_hg; g.h_in = h_in; g.h_out = h_out;
     g.gates = c.gates + r0 * 3 * d; g.embed_ws = c.embed + (size_t)t * d; g.embed_out = embed + (size_t)t * d;
@@ -480,56 +528,20 @@ int train_forward_steps(const ac_bah_weights* w, const float* attn_emb, const fl
   return AC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-long ac_bah_train_workspace_floats(const ac_bah_weights* w, int B, int Tm, int T) {
-  if (!train_dims_ok(w, B, Tm, T, 0.f)) return -1;
-  return (long)train_carve(w, nullptr, B, Tm, T).total;
-}
-
-int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
-                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
-                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
-                         int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
-                         float* ws, void* stream) {
-  if (!train_dims_ok(w, B, Tm, T, drop_p) || !attn_emb || !fc_emb || !mem_len || !cap || cap_ld < T || !use_cap || !seq ||
-      !logit || !logprob || !embed || !attn_weight || !state || !ws || (w->n_tags == 0) != (tags == nullptr))
-    return AC_ERR_ARG;
-  return train_forward_steps(w, attn_emb, fc_emb, mem_len, cap, cap_ld, use_cap, tags, B, Tm, T, start_idx, drop_p, drop_seed,
-                             seed_dev, seq, seq, nullptr, logit, logprob, embed, attn_weight, state, ws, stream);
-}
-
-int ac_bah_train_rollout(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
-                         const int* tags, int B, int Tm, int T, int start_idx, int end_idx, float temp,
-                         const uint64_t* sample_seed_dev, const int* forced, long forced_ld, float drop_p,
-                         unsigned long long drop_seed, const unsigned long long* seed_dev, int* seq, int* scratch,
-                         float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
-                         void* stream) {
-  if (T < 1 || !train_dims_ok(w, B, Tm, T, drop_p) || !attn_emb || !fc_emb || !mem_len || !sample_seed_dev || !seq ||
-      !scratch || !logit || !logprob || !embed || !attn_weight || !state || !ws || !isfinite(temp) || !(temp > 0.f) ||
-      (forced && forced_ld < T) || (w->n_tags == 0) != (tags == nullptr) ||
-      ac_sample_check(w->vocab, AC_SAMPLE_PLAIN, 0, 1.0f, temp) != AC_OK)
-    return AC_ERR_ARG;
-  Rollout ro;
-  ro.seq = seq; ro.scratch = scratch; ro.forced = forced; ro.forced_ld = forced_ld; ro.sample_seed_dev = sample_seed_dev;
-  ro.temp = temp; ro.end_idx = end_idx;
-  return train_forward_steps(w, attn_emb, fc_emb, mem_len, nullptr, 0, nullptr, tags, B, Tm, T, start_idx, drop_p, drop_seed,
-                             seed_dev, nullptr, nullptr, &ro, logit, logprob, embed, attn_weight, state, ws, stream);
-}
-
-int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* fc_emb,
-                          const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
-                          unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
-                          float* d_fc_emb, float* ws, void* stream) {
-  if (!train_dims_ok(w, B, Tm, T, drop_p) || !grads_ok(w, g) || !attn_emb || !fc_emb || !mem_len || !dlogit ||
+// The backward through time; `side` as in train_forward_steps.
+int train_backward_steps(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* side,
+                         const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
+                         unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
+                         float* d_fc_emb, float* ws, void* stream) {
+  if (!train_dims_ok(w, B, Tm, T, drop_p) || !grads_ok(w, g) || !attn_emb || !side || !mem_len || !dlogit ||
       !d_attn_emb || !d_fc_emb || !ws)
     return AC_ERR_ARG;
   const int E = w->emb_dim, d = w->d_model, S = w->attn_size, A = w->attn_emb_dim, F = w->fc_emb_dim, V = w->vocab;
   hipStream_t s = (hipStream_t)stream;
   const TrainWs c = train_carve(w, ws, B, Tm, T);
-  const long ld_hg = S + 3L * d, R = (long)T * B;
+  const long ld_hg = S + 3L * d, R = (long)T * B, xw = bah_xw(w), ld_ih = bah_ld_ih(w);
+  const bool spec = w->variant == BAH_SPEC;
+  const long ld_gih = spec ? xw + 1 : ld_ih;     // the row pitch of the weight_ih_l0 gradient: the parameter's own
   // the classifier's input gradient for every (clip, step) at once, in dlogit's (clip, step) row order
   BAH_TRY(dx_rows(dlogit, V, w->cls_w, d, c.dhc, d, (int)R, V, d, 0.0f, stream));
   if (hipMemsetAsync(c.dh, 0, (size_t)B * d * sizeof(float), s) != hipSuccess ||
@@ -541,7 +553,7 @@ int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const 
     const float* hg = c.hg + r0 * ld_hg;
     float* dgi = c.dgi + r0 * 3 * d;
     float* dgh = c.dgh + r0 * 3 * d;
-    float* dxin = c.dxin + r0 * 2 * E;
+    float* dxin = c.dxin + r0 * xw;
     float* dq = c.dq + r0 * S;
     TGateBP gb;
     gb.dhc = c.dhc + (size_t)t * d; gb.ld_dhc = (long)T * d; gb.gates = c.gates + r0 * 3 * d;
@@ -549,11 +561,11 @@ int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const 
     gb.B = B; gb.d = d;
     hipLaunchKernelGGL(bah_train_gate_bwd_kernel, dim3((unsigned)(((long)B * d + 255) / 256)), dim3(256), 0, s, gb);
     BAH_TRY(ac_check_launch());
-    BAH_TRY(dx_step(dgi, 3L * d, w->w_ih, 3L * E, dxin, 2L * E, B, 3 * d, 2 * E, 0.0f, stream));
-    BAH_TRY(dx_step(dxin + E, 2L * E, w->ctx_w, A, c.dctx, A, B, E, A, 0.0f, stream));
+    BAH_TRY(dx_step(dgi, 3L * d, w->w_ih, ld_ih, dxin, xw, B, 3 * d, (int)xw, 0.0f, stream));
+    if (!spec) BAH_TRY(dx_step(dxin + E, xw, w->ctx_w, A, c.dctx, A, B, E, A, 0.0f, stream));
     TAttnBP ab;
     ab.hg = hg; ab.ld_hg = ld_hg; ab.ek = c.ek; ab.attn_emb = attn_emb; ab.v = w->attn_v; ab.w = c.w + r0 * Tm;
-    ab.dctx = c.dctx; ab.mem_len = mem_len; ab.dq = dq; ab.dv = c.dv + r0 * S; ab.d_attn_emb = d_attn_emb; ab.dek = c.dek;
+    ab.dctx = spec ? dxin + E : c.dctx; ab.ld_dctx = spec ? xw : A; ab.mem_len = mem_len; ab.dq = dq; ab.dv = c.dv + r0 * S; ab.d_attn_emb = d_attn_emb; ab.dek = c.dek;
     ab.Tm = Tm; ab.S = S; ab.A = A;
     hipLaunchKernelGGL(bah_train_attn_bwd_kernel, dim3(B), dim3(256), 0, s, ab);
     BAH_TRY(ac_check_launch());
@@ -569,10 +581,11 @@ int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const 
   // GRU: W_hh, b_hh; the embedding and context columns of W_ih
   BAH_TRY(dw_rows(c.dgh, 3L * d, c.h_all, d, g->w_hh, d, R, 3 * d, d, stream));
   BAH_TRY(ac_colsum(c.dgh, 3L * d, g->b_hh, R, 3 * d, stream));
-  BAH_TRY(dw_rows(c.dgi, 3L * d, c.xin, 2L * E, g->w_ih, 3L * E, R, 3 * d, 2 * E, stream));
-  // ctx_proj
-  BAH_TRY(dw_rows(c.dxin + E, 2L * E, c.ctx, A, g->ctx_w, A, R, E, A, stream));
-  BAH_TRY(ac_colsum(c.dxin + E, 2L * E, g->ctx_b, R, E, stream));
+  BAH_TRY(dw_rows(c.dgi, 3L * d, c.xin, xw, g->w_ih, ld_gih, R, 3 * d, (int)xw, stream));
+  if (!spec) {   // ctx_proj
+    BAH_TRY(dw_rows(c.dxin + E, xw, c.ctx, A, g->ctx_w, A, R, E, A, stream));
+    BAH_TRY(ac_colsum(c.dxin + E, xw, g->ctx_b, R, E, stream));
+  }
   // attention: the decoder-state columns of h2attn, v
   BAH_TRY(dw_rows(c.dq, S, c.h_all, d, g->attn_w, d + A, R, S, d, stream));
   BAH_TRY(ac_colsum(c.dv, S, g->attn_v, R, S, stream));
@@ -580,18 +593,102 @@ int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const 
   BAH_TRY(dw_rows(c.dek, S, attn_emb, A, g->attn_w + d, d + A, (long)B * Tm, S, A, stream));
   BAH_TRY(ac_colsum(c.dek, S, g->attn_b, (long)B * Tm, S, stream));
   BAH_TRY(dx_rows(c.dek, S, w->attn_w + d, d + A, d_attn_emb, A, B * Tm, S, A, 1.0f, stream));
-  // gf = W_ih[:, 2E:] fc_proj(fc_emb) + b_ih is shared by the steps: dgf = sum_t dgi[t]
+  // gf (the fc or condition part of the input gates, + b_ih) is shared by the steps: dgf = sum_t dgi[t]
   BAH_TRY(ac_sum_replicas(c.dgi, c.dgf, (long)B * 3 * d, T, stream));
   BAH_TRY(ac_colsum(c.dgf, 3L * d, g->b_ih, B, 3 * d, stream));
-  BAH_TRY(dw_rows(c.dgf, 3L * d, c.pfc, E, g->w_ih + 2 * E, 3L * E, B, 3 * d, E, stream));
-  BAH_TRY(dx_step(c.dgf, 3L * d, w->w_ih + 2 * E, 3L * E, c.dpfc, E, B, 3 * d, E, 0.0f, stream));
-  BAH_TRY(dw_rows(c.dpfc, E, fc_emb, F, g->fc_w, F, B, E, F, stream));
-  BAH_TRY(ac_colsum(c.dpfc, E, g->fc_b, B, E, stream));
-  BAH_TRY(dx_step(c.dpfc, E, w->fc_w, F, d_fc_emb, F, B, E, F, 0.0f, stream));
+  if (spec) {
+    hipLaunchKernelGGL(bah_cond_col_bwd_kernel, dim3((3 * d + 255) / 256), dim3(256), 0, s, side, c.dgf, g->fc_w, ld_gih, B,
+                       3 * d);
+    BAH_TRY(ac_check_launch());
+  } else {
+    BAH_TRY(dw_rows(c.dgf, 3L * d, c.pfc, E, g->w_ih + 2 * E, 3L * E, B, 3 * d, E, stream));
+    BAH_TRY(dx_step(c.dgf, 3L * d, w->w_ih + 2 * E, 3L * E, c.dpfc, E, B, 3 * d, E, 0.0f, stream));
+  }
+  if (w->variant == BAH_CATFC) {
+    BAH_TRY(dw_rows(c.dpfc, E, side, F, g->fc_w, F, B, E, F, stream));
+    BAH_TRY(ac_colsum(c.dpfc, E, g->fc_b, B, E, stream));
+    BAH_TRY(dx_step(c.dpfc, E, w->fc_w, F, d_fc_emb, F, B, E, F, 0.0f, stream));
+  } else {
+    if (w->variant == BAH_COND) {
+      hipLaunchKernelGGL(bah_cond_emb_bwd_kernel, dim3((E + 255) / 256), dim3(256), 0, s, side, c.dpfc, g->fc_w, B, E);
+      BAH_TRY(ac_check_launch());
+    }
+    if (hipMemsetAsync(d_fc_emb, 0, (size_t)B * F * sizeof(float), s) != hipSuccess) return AC_ERR_LAUNCH;   // never read
+  }
   // the embedding tables
   hipLaunchKernelGGL(bah_train_embed_bwd_kernel, dim3((unsigned)((R * E + 255) / 256)), dim3(256), 0, s, c.dxin, c.tok,
-                     g->emb, g->temb, R, E, make_drop(drop_p, drop_seed, seed_dev));
+                     g->emb, g->temb, R, E, xw, make_drop(drop_p, drop_seed, seed_dev));
   return ac_check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+long ac_bah_train_workspace_floats(const ac_bah_weights* w, int B, int Tm, int T) {
+  if (!train_dims_ok(w, B, Tm, T, 0.f)) return -1;
+  return (long)train_carve(w, nullptr, B, Tm, T).total;
+}
+
+int ac_bah_train_forward(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const long long* cap, long cap_ld, const int* use_cap, const int* tags, int B, int Tm, int T,
+                         int start_idx, float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev,
+                         int64_t* seq, float* logit, float* logprob, float* embed, float* attn_weight, float* state,
+                         float* ws, void* stream) {
+  if (!train_dims_ok(w, B, Tm, T, drop_p) || w->variant != BAH_CATFC || !attn_emb || !fc_emb || !mem_len || !cap ||
+      cap_ld < T || !use_cap || !seq || !logit || !logprob || !embed || !attn_weight || !state || !ws ||
+      (w->n_tags == 0) != (tags == nullptr))
+    return AC_ERR_ARG;
+  return train_forward_steps(w, attn_emb, fc_emb, mem_len, cap, cap_ld, use_cap, tags, B, Tm, T, start_idx, drop_p, drop_seed,
+                             seed_dev, seq, seq, nullptr, logit, logprob, embed, attn_weight, state, ws, stream);
+}
+
+int ac_bah_train_forward_cond(const ac_bah_weights* w, const float* attn_emb, const float* cond, const int* mem_len,
+                              const long long* cap, long cap_ld, const int* use_cap, int B, int Tm, int T, int start_idx,
+                              float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev, int64_t* seq,
+                              float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
+                              void* stream) {
+  if (!train_dims_ok(w, B, Tm, T, drop_p) || w->variant == BAH_CATFC || !attn_emb || !cond || !mem_len || !cap ||
+      cap_ld < T || !use_cap || !seq || !logit || !logprob || !embed || !attn_weight || !state || !ws)
+    return AC_ERR_ARG;
+  return train_forward_steps(w, attn_emb, cond, mem_len, cap, cap_ld, use_cap, nullptr, B, Tm, T, start_idx, drop_p, drop_seed,
+                             seed_dev, seq, seq, nullptr, logit, logprob, embed, attn_weight, state, ws, stream);
+}
+
+int ac_bah_train_rollout(const ac_bah_weights* w, const float* attn_emb, const float* fc_emb, const int* mem_len,
+                         const int* tags, int B, int Tm, int T, int start_idx, int end_idx, float temp,
+                         const uint64_t* sample_seed_dev, const int* forced, long forced_ld, float drop_p,
+                         unsigned long long drop_seed, const unsigned long long* seed_dev, int* seq, int* scratch,
+                         float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
+                         void* stream) {
+  if (T < 1 || !train_dims_ok(w, B, Tm, T, drop_p) || w->variant != BAH_CATFC || !attn_emb || !fc_emb || !mem_len ||
+      !sample_seed_dev || !seq || !scratch || !logit || !logprob || !embed || !attn_weight || !state || !ws || !isfinite(temp) || !(temp > 0.f) ||
+      (forced && forced_ld < T) || (w->n_tags == 0) != (tags == nullptr) ||
+      ac_sample_check(w->vocab, AC_SAMPLE_PLAIN, 0, 1.0f, temp) != AC_OK)
+    return AC_ERR_ARG;
+  Rollout ro;
+  ro.seq = seq; ro.scratch = scratch; ro.forced = forced; ro.forced_ld = forced_ld; ro.sample_seed_dev = sample_seed_dev;
+  ro.temp = temp; ro.end_idx = end_idx;
+  return train_forward_steps(w, attn_emb, fc_emb, mem_len, nullptr, 0, nullptr, tags, B, Tm, T, start_idx, drop_p, drop_seed,
+                             seed_dev, nullptr, nullptr, &ro, logit, logprob, embed, attn_weight, state, ws, stream);
+}
+
+int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* fc_emb,
+                          const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
+                          unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
+                          float* d_fc_emb, float* ws, void* stream) {
+  if (!w || w->variant != BAH_CATFC) return AC_ERR_ARG;
+  return train_backward_steps(w, g, attn_emb, fc_emb, mem_len, dlogit, B, Tm, T, drop_p, drop_seed, seed_dev, d_attn_emb,
+                              d_fc_emb, ws, stream);
+}
+
+int ac_bah_train_backward_cond(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* cond,
+                               const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
+                               unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
+                               float* d_fc_emb, float* ws, void* stream) {
+  if (!w || w->variant == BAH_CATFC) return AC_ERR_ARG;
+  return train_backward_steps(w, g, attn_emb, cond, mem_len, dlogit, B, Tm, T, drop_p, drop_seed, seed_dev, d_attn_emb,
+                              d_fc_emb, ws, stream);
 }
 
 int ac_bah_mean_lens_bwd(const float* d_fc_emb, const int* lens, float* d_attn_emb, int B, int Tm, int A, int F,

@@ -194,6 +194,35 @@ def bah_decoder_state(prefix="", vocab_size=4981, emb_dim=512, d_model=512, attn
     return out
 
 
+def cond_decoder_state(kind, prefix="", vocab_size=4981, emb_dim=512, d_model=512, attn_size=512, attn_emb_dim=512,
+                       seed=BASE_SEED, end_scale=3.0, **unused):
+    """ConditionalBahAttnDecoder (``kind`` "cond", rnn_decoder.py:276-299) / SpecificityBahAttnDecoder ("spec",
+    rnn_decoder.py:519-540) tensors, drawn by ``bah_decoder_state``'s rules: no ``fc_proj``; "cond" has
+    ``condition_embedding.weight`` (2, E) of std 1 like the word embeddings; "spec" has no ``ctx_proj`` and a GRU input of
+    E + A + 1 columns."""
+    E, d, S, A = emb_dim, d_model, attn_size, attn_emb_dim
+    n_in = 3 * E if kind == "cond" else E + A + 1
+    spec = [("word_embedding.weight", (vocab_size, E), 1.0),
+            ("model.weight_ih_l0", (3 * d, n_in), 1.0 / math.sqrt(n_in)),
+            ("model.weight_hh_l0", (3 * d, d), 1.0 / math.sqrt(d)),
+            ("attn.h2attn.weight", (S, d + A), 1.0 / math.sqrt(d + A)),
+            ("attn.v", (S,), 4.0 / math.sqrt(S)),
+            ("classifier.weight", (vocab_size, d), 4.0 / math.sqrt(d))]
+    biases = [("model.bias_ih_l0", 3 * d), ("model.bias_hh_l0", 3 * d), ("attn.h2attn.bias", S), ("classifier.bias", vocab_size)]
+    if kind == "cond":
+        spec += [("ctx_proj.weight", (E, A), 1.0 / math.sqrt(A)), ("condition_embedding.weight", (2, E), 1.0)]
+        biases.append(("ctx_proj.bias", E))
+    elif kind != "spec":
+        raise ValueError(f"kind {kind!r}: 'cond' or 'spec'")
+    out = {}
+    for name, shape, std in spec:
+        out[prefix + name] = _normal(prefix + kind + "." + name, shape, std, seed)
+    for name, n in biases:
+        out[prefix + name] = _uniform(prefix + kind + "." + name, (n,), -0.1, 0.1, seed)
+    out[prefix + "classifier.weight"][2] *= np.float32(end_scale)
+    return out
+
+
 SED_CHANNELS = [1, 64, 128, 256, 512]
 
 

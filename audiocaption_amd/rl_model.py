@@ -106,8 +106,11 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
 
     def __init__(self, model):
         super().__init__()
-        from .attn_model import Seq2SeqAttnModel
+        from .attn_model import ConditionalSeq2SeqAttnModel, Seq2SeqAttnModel
         from .crnn_trm_encoder import CrnnEncoder
+        if isinstance(model, ConditionalSeq2SeqAttnModel):
+            raise NotImplementedError("ScstWrapper: self-critical training is not built for ConditionalSeq2SeqAttnModel (the "
+                                      "condition-controlled decoders have no sampled rollout)")
         self._attn_gru = isinstance(model, Seq2SeqAttnModel) and isinstance(model.encoder, CrnnEncoder)
         if not (isinstance(model, TransformerModel) or self._attn_gru):
             over = f" over {model.encoder.__class__.__name__}" if isinstance(model, Seq2SeqAttnModel) else ""

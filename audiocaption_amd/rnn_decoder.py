@@ -15,6 +15,11 @@ regenerated in the backward.  ``train_rollout`` is the sampled rollout of self-c
 (``ac_bah_train_rollout``): the same chain with no caption, each step on the word the step before drew, and the same kept
 state.  The models of ``attn_model.py`` reach all three through ``train_attn_gru.AttnGruTrainEngine``.
 
+``ConditionalBahAttnDecoder`` (rnn_decoder.py:276-336) and ``SpecificityBahAttnDecoder`` (rnn_decoder.py:519-575) are the
+condition-controlled decoders: one float per clip, ``condition``, takes ``fc_emb``'s place in ``memory``, ``train_forward``
+and ``forward`` (``ac_bah_memory_cond``, ``ac_bah_train_forward_cond`` / ``ac_bah_train_backward_cond``); the searches
+and the step are the same C calls.  Neither reads ``fc_emb``.  ``train_rollout`` (SCST) is not built for them.
+
 Built: ``rnn_type="GRU"``, ``num_layers=1``, unidirectional; emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim each a
 multiple of 32 up to 1024; vocab_size <= 16384.  Anything else raises NotImplementedError in the constructor.
 """
@@ -72,6 +77,8 @@ class BahAttnCatFcDecoder(RnnDecoder):
     """GRU over cat(word embedding, ctx_proj(attention context), fc_proj(fc_emb)) (rnn_decoder.py:159-216)."""
 
     n_tags = 0
+    variant = 0        # ac_bah_weights.variant
+    ENTRY = {"memory": "ac_bah_memory", "train_forward": "ac_bah_train_forward", "train_backward": "ac_bah_train_backward"}
 
     def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
         super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs)
@@ -106,28 +113,41 @@ class BahAttnCatFcDecoder(RnnDecoder):
         w = _lib.AcBahWeights()
         w.emb_dim, w.d_model, w.attn_size = self.emb_dim, self.d_model, self.attn_size
         w.attn_emb_dim, w.fc_emb_dim, w.vocab, w.n_tags = self.attn_emb_dim, self.fc_emb_dim, self.vocab_size, self.n_tags
+        w.variant = self.variant
         w.emb = P(self.word_embedding.weight)
         if self.n_tags:
             w.temb = P(self.temporal_embedding.weight)
-        w.w_ih, w.w_hh = P(self.model.weight_ih_l0), P(self.model.weight_hh_l0)
+        w.w_hh = P(self.model.weight_hh_l0)
         w.b_ih, w.b_hh = P(self.model.bias_ih_l0), P(self.model.bias_hh_l0)
         w.attn_w, w.attn_b, w.attn_v = P(self.attn.h2attn.weight), P(self.attn.h2attn.bias), P(self.attn.v)
-        w.fc_w, w.fc_b = P(self.fc_proj.weight), P(self.fc_proj.bias)
-        w.ctx_w, w.ctx_b = P(self.ctx_proj.weight), P(self.ctx_proj.bias)
+        self._input_weights(w, P)
         w.cls_w, w.cls_b = P(self.classifier.weight), P(self.classifier.bias)
         self._w, self._w_key, self._w_keep = w, key, keep
         return w
+
+    def _input_weights(self, w, P):
+        """The slots that depend on what the GRU input is made of (``ac_bah_weights.variant``)."""
+        w.w_ih = P(self.model.weight_ih_l0)
+        w.fc_w, w.fc_b = P(self.fc_proj.weight), P(self.fc_proj.bias)
+        w.ctx_w, w.ctx_b = P(self.ctx_proj.weight), P(self.ctx_proj.bias)
+
+    def _side(self, side, attn_emb):
+        """The once-per-batch input next to the audio memory, checked, on the device: ``fc_emb`` (N, F)."""
+        fc_emb = f32c(side)
+        ptr(fc_emb)
+        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
+            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
+                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        return fc_emb
 
     def memory(self, attn_emb, fc_emb, attn_emb_len, rows_per_clip=1, max_length=20):
         """Once per batch: the workspace with the key projection and the fc part of the input gates (``ac_bah_memory``).
         Returns the handle ``step`` / ``greedy`` / ``sample`` take."""
         lib = _lib.load()
         w = self.weights()
-        attn_emb, fc_emb = f32c(attn_emb), f32c(fc_emb)
-        ptr(attn_emb), ptr(fc_emb)   # a CPU tensor is refused here, before anything is uploaded
-        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
-            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
-                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        attn_emb = f32c(attn_emb)
+        ptr(attn_emb)                # a CPU tensor is refused here, before anything is uploaded
+        fc_emb = self._side(fc_emb, attn_emb)
         B, Tm, _ = attn_emb.shape
         if Tm > MAX_FRAMES:
             raise NotImplementedError(f"{Tm} frames of audio memory: the attention kernel holds at most {MAX_FRAMES}")
@@ -139,8 +159,9 @@ class BahAttnCatFcDecoder(RnnDecoder):
         mem = {"attn_emb": attn_emb, "len": K.upload(attn_emb_len, dev, torch.int32), "B": B, "R": R, "Tm": Tm,
                "max_length": int(max_length), "row_div": int(rows_per_clip),
                "ws": torch.empty(n, device=dev, dtype=torch.float32)}
-        check(lib.ac_bah_memory(ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), B, R, Tm, int(max_length), ptr(mem["ws"]),
-                                stream()), "ac_bah_memory")
+        check(getattr(lib, self.ENTRY["memory"])(ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), B, R, Tm, int(max_length),
+                                                 ptr(mem["ws"]), stream()), self.ENTRY["memory"])
+        mem["side"] = fc_emb
         return mem
 
     def step(self, mem, state_in, state_out, words=None, word_stride=1, tags=None, logit=None, ldl=None, embed=None,
@@ -209,11 +230,9 @@ class BahAttnCatFcDecoder(RnnDecoder):
         from .train import OP_BAH_IN
         lib = _lib.load()
         w = self.weights()
-        attn_emb, fc_emb = f32c(attn_emb), f32c(fc_emb)
-        ptr(attn_emb), ptr(fc_emb), ptr(cap)
-        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim or fc_emb.shape != (attn_emb.shape[0], self.fc_emb_dim):
-            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} / fc_emb {tuple(fc_emb.shape)} do not fit attn_emb_dim "
-                             f"{self.attn_emb_dim} / fc_emb_dim {self.fc_emb_dim}")
+        attn_emb = f32c(attn_emb)
+        ptr(attn_emb), ptr(cap)
+        fc_emb = self._side(fc_emb, attn_emb)
         B, Tm, _ = attn_emb.shape
         if Tm > MAX_FRAMES:
             raise NotImplementedError(f"{Tm} frames of audio memory: the attention kernels hold at most {MAX_FRAMES}")
@@ -242,11 +261,13 @@ class BahAttnCatFcDecoder(RnnDecoder):
                "attn_weight": torch.empty(B, Tm, T, **f32), "state": torch.empty(1, B, self.d_model, **f32)}
         saved = {"w": w, "attn_emb": attn_emb, "fc_emb": fc_emb, "len": lens, "B": B, "Tm": Tm, "T": T, "p": p, "seed": seed,
                  "seed_dev": seed_dev, "ws": torch.empty(n, **f32)}
-        check(lib.ac_bah_train_forward(
-            ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), ptr(lens), ptr(cap), cap.shape[1], (ctypes.c_int * T)(*use_cap),
-            ptr(tags), B, Tm, T, int(start_idx), p, seed, seed_dev, ptr(out["seq"]), ptr(out["logit"]),
+        args = [ctypes.byref(w), ptr(attn_emb), ptr(fc_emb), ptr(lens), ptr(cap), cap.shape[1], (ctypes.c_int * T)(*use_cap)]
+        if not self.variant:       # the conditional entry point takes no tags
+            args.append(ptr(tags))
+        check(getattr(lib, self.ENTRY["train_forward"])(
+            *args, B, Tm, T, int(start_idx), p, seed, seed_dev, ptr(out["seq"]), ptr(out["logit"]),
             ptr(out["sampled_logprob"]), ptr(out["embed"]), ptr(out["attn_weight"]), ptr(out["state"]), ptr(saved["ws"]),
-            stream()), "ac_bah_train_forward")
+            stream()), self.ENTRY["train_forward"])
         out["saved"] = saved
         return out
 
@@ -334,10 +355,10 @@ class BahAttnCatFcDecoder(RnnDecoder):
         def P(x):
             return ptr(x) if torch.is_tensor(x) else ctypes.c_void_p(x)
 
-        check(lib.ac_bah_train_backward(
+        check(getattr(lib, self.ENTRY["train_backward"])(
             ctypes.byref(saved["w"]), ctypes.byref(grads), ptr(saved["attn_emb"]), ptr(saved["fc_emb"]), ptr(saved["len"]),
             P(dlogit), B, Tm, T, saved["p"], saved["seed"], saved["seed_dev"], P(d_attn_emb), P(d_fc_emb), ptr(saved["ws"]),
-            stream()), "ac_bah_train_backward")
+            stream()), self.ENTRY["train_backward"])
         return named, d_attn_emb, d_fc_emb
 
     def _tags(self, input_dict, n):
@@ -350,7 +371,8 @@ class BahAttnCatFcDecoder(RnnDecoder):
         attn_emb = input_dict["attn_emb"]
         dev = attn_emb.device
         N, Tm = attn_emb.shape[0], attn_emb.shape[1]
-        mem = self.memory(attn_emb, input_dict["fc_emb"], input_dict["attn_emb_len"], 1, 1)
+        side = check_condition(input_dict.get("condition"), N) if self.variant else input_dict["fc_emb"]
+        mem = self.memory(attn_emb, side, input_dict["attn_emb_len"], 1, 1)
         state = input_dict.get("state")
         state_in = f32c(state).reshape(N, self.d_model) if state is not None else torch.zeros(N, self.d_model, device=dev)
         word = input_dict["word"]
@@ -392,3 +414,82 @@ class TemporalBahAttnDecoder(BahAttnCatFcDecoder):
 
     def _tags(self, input_dict, n):
         return check_temporal_tag(input_dict.get("temporal_tag"), n) if input_dict["t"] == 0 else None
+
+
+def check_condition(condition, n):
+    """``condition`` as float32 (n,) on the host; raises ValueError unless it holds n finite floating-point values (any
+    finite value: a specificity is a sentence sum, not confined to 0..1)."""
+    if condition is None:
+        raise ValueError("condition is required: one float per clip")
+    condition = torch.as_tensor(condition).detach().cpu()
+    if not condition.dtype.is_floating_point or condition.numel() != n:
+        raise ValueError(f"condition must hold {n} floats (got dtype {condition.dtype}, {condition.numel()} values)")
+    condition = condition.reshape(n).to(torch.float32)
+    if n and not bool(torch.isfinite(condition).all()):
+        raise ValueError(f"condition must be finite (got {condition.tolist()})")
+    return condition
+
+
+def _identity(x):
+    return x
+
+
+class ConditionalBahAttnDecoder(BahAttnCatFcDecoder):
+    """GRU over cat(word embedding, ctx_proj(attention context), cond_emb) with cond_emb = (1 - condition) *
+    condition_embedding.weight[0] + condition * condition_embedding.weight[1] (rnn_decoder.py:276-336).  There is no
+    ``fc_proj``; ``fc_emb`` is not read.  Where ``BahAttnCatFcDecoder``'s methods take ``fc_emb`` this one takes
+    ``condition``: n floats, host values or a tensor (``check_condition``)."""
+
+    variant = 1
+    ENTRY = {"memory": "ac_bah_memory_cond", "train_forward": "ac_bah_train_forward_cond",
+             "train_backward": "ac_bah_train_backward_cond"}
+    GRAD_FIELDS = tuple((f, "condition_embedding.weight" if f == "fc_w" else n) for f, n in BahAttnCatFcDecoder.GRAD_FIELDS
+                        if f not in ("temb", "fc_b"))
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs)
+        del self.fc_proj
+        self.condition_embedding = nn.Embedding(2, emb_dim)
+
+    def _input_weights(self, w, P):
+        w.w_ih = P(self.model.weight_ih_l0)
+        w.fc_w = P(self.condition_embedding.weight)
+        w.ctx_w, w.ctx_b = P(self.ctx_proj.weight), P(self.ctx_proj.bias)
+
+    def _side(self, side, attn_emb):
+        if attn_emb.dim() != 3 or attn_emb.shape[2] != self.attn_emb_dim:
+            raise ValueError(f"attn_emb {tuple(attn_emb.shape)} does not fit attn_emb_dim {self.attn_emb_dim}")
+        return check_condition(side, attn_emb.shape[0]).to(attn_emb.device)
+
+    def train_rollout(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}: the SCST rollout is not built for the condition-controlled decoders")
+
+
+class SpecificityBahAttnDecoder(ConditionalBahAttnDecoder):
+    """GRU over cat(word embedding, attention context, condition): E + A + 1 input columns, the context at its full width
+    and the condition as one raw column (rnn_decoder.py:519-575).  No ``fc_proj``, no ``ctx_proj`` (the reference's
+    identity), no ``condition_embedding``.
+
+    ``weight_ih_l0`` has the odd row pitch E + A + 1.  ``weights()`` repacks it whenever it rebuilds the struct: the first
+    E + A columns as an aligned (3d, E + A) block for the input-gate product, the last column on its own; the gradient is
+    written into the parameter's own layout (``grad_struct``)."""
+
+    variant = 2
+    GRAD_FIELDS = tuple((f, n) for f, n in BahAttnCatFcDecoder.GRAD_FIELDS if f not in ("temb", "fc_w", "fc_b", "ctx_w", "ctx_b"))
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, d_model, **kwargs)
+        del self.ctx_proj, self.condition_embedding
+        self.ctx_proj = _identity
+        self.model = nn.GRU(input_size=self.emb_dim + self.attn_emb_dim + 1, hidden_size=self.d_model, batch_first=True,
+                            num_layers=1, bidirectional=False)
+
+    def _input_weights(self, w, P):
+        xw = self.emb_dim + self.attn_emb_dim
+        w.w_ih = P(self.model.weight_ih_l0[:, :xw])     # P copies a strided slice into a contiguous block
+        w.fc_w = P(self.model.weight_ih_l0[:, xw])
+
+    def grad_struct(self, address_of):
+        g = super().grad_struct(address_of)
+        g.fc_w = ctypes.c_void_p(address_of("model.weight_ih_l0") + 4 * (self.emb_dim + self.attn_emb_dim))
+        return g

@@ -20,6 +20,10 @@ contract (``rl_model.ScstWrapper`` drives it): the same train-mode encoder, then
 caption, each on the word the step before drew (``BahAttnCatFcDecoder.train_rollout``, ``ac_bah_train_rollout``).  It keeps
 the state of a ``forward``, so ``backward`` and the bridge node work after it; it draws no scheduled-sampling coins.
 
+``ConditionalSeq2SeqAttnModel`` trains the same way: its decoders take ``input_dict["condition"]`` (one float per clip,
+checked in ``_prepare``) where the others take ``fc_emb``; they read no ``fc_emb``, so their ``d fc_emb`` is exactly zero.
+``rollout`` is refused for it.
+
 Not built for these models: the fused ``step`` (device-side loss, clip, Adam, graph capture, the split all-reduce), graph
 capture or an early exit of the rollout, and the Cnn14 look-ahead.
 """
@@ -31,7 +35,7 @@ import torch
 from . import _lib
 from . import kernels as K
 from ._lib import check
-from .rnn_decoder import check_temporal_tag
+from .rnn_decoder import check_condition, check_temporal_tag
 from .train import H, OP_CNN_BLOCK, TrainEngine, _TrainBridgeFc
 
 
@@ -61,7 +65,14 @@ class AttnGruTrainEngine(TrainEngine):
         if input_dict["ss_ratio"] == 1 and not rollout:
             for _ in range(T):
                 random.random()
+        cond = None
+        if self.model.decoder.variant:
+            if rollout:
+                raise NotImplementedError("AttnGruTrainEngine: the SCST rollout is not built for the condition-controlled "
+                                          "decoders")
+            cond = check_condition(input_dict.get("condition"), input_dict["cap"].shape[0])
         st = super()._prepare(input_dict, rollout)     # st["use_cap"]: the T coins
+        st["cond"] = cond
         st["tags"] = None if tags is None else K.upload(tags, st["cap"].device, torch.int32)
         return st
 
@@ -96,7 +107,8 @@ class AttnGruTrainEngine(TrainEngine):
         ro = st.get("rollout")
         try:
             if ro is None:
-                st["bah"] = dec.train_forward(attn_emb, fc_emb, lens, st["cap"], st["use_cap"], st.get("tags"),
+                st["bah"] = dec.train_forward(attn_emb, st["cond"] if dec.variant else fc_emb, lens, st["cap"],
+                                              st["use_cap"], st.get("tags"),
                                               model.start_idx, seed_dev=self._seed_ptr)
             else:
                 st["bah"] = dec.train_rollout(attn_emb, fc_emb, lens, st["T"], ro["temp"], ro["seed"], st.get("tags"),

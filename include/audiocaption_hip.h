@@ -482,7 +482,8 @@ int ac_ens_beam_step_select(const float* const* logits, int n_models, long ld, i
  * tanhf / expf.  ek = W_enc attn_emb + b_attn [B][Tm][S] and gf = W_ih[:, 2E:3E] fc_proj(fc_emb) + b_ih [B][3d] do not
  * depend on the step: ac_bah_memory computes them once per batch into the workspace. */
 typedef struct {
-  int32_t emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim, vocab, n_tags, reserved;
+  int32_t emb_dim, d_model, attn_size, attn_emb_dim, fc_emb_dim, vocab, n_tags;
+  int32_t variant;     /* 0: the decoder above; 1 / 2: the condition-controlled decoders below            */
   const float* emb;    /* word_embedding.weight     [V][E]                                      */
   const float* temb;   /* temporal_embedding.weight [4][E] (NULL when n_tags == 0)              */
   const float* w_ih;   /* model.weight_ih_l0        [3d][3E]: columns embed | p_ctx | p_fc      */
@@ -500,6 +501,19 @@ typedef struct {
   const float* cls_b;  /* classifier.bias   [V]    */
 } ac_bah_weights;
 
+/* Condition-controlled decoders (ConditionalBahAttnDecoder rnn_decoder.py:276-336, SpecificityBahAttnDecoder :519-575): one
+ * float per clip, cond (any finite value), in fc_emb's place.  The struct keeps its layout; a slot the variant does not use
+ * must be NULL, n_tags 0, and every entry point checks that.
+ *   variant 1  GRU input [embed | ctx_proj(c) | (1 - cond) W_c[0] + cond W_c[1]]; fc_w = condition_embedding.weight [2][E],
+ *              fc_b NULL.  Only gf differs: W_ih[:, 2E:3E] cond_emb + b_ih.
+ *   variant 2  GRU input [embed | c | cond], E + A + 1 wide, no ctx_proj: w_ih = the first E + A columns of weight_ih_l0
+ *              repacked to an aligned [3d][E + A] block, fc_w = its last column [3d]; fc_b, ctx_w, ctx_b NULL.
+ *              gf = cond W_ih[:, E + A] + b_ih.
+ * ac_bah_memory_cond (cond [B] on the device) replaces ac_bah_memory; ac_bah_workspace_floats, ac_bah_step_logits,
+ * ac_bah_greedy, ac_bah_sample and ac_bah_beam_gather serve every variant.  The entry points that take fc_emb refuse
+ * variants 1 and 2, the _cond ones refuse variant 0 (AC_ERR_ARG). */
+int ac_bah_memory_cond(const ac_bah_weights* w, const float* attn_emb, const float* cond, int B, int R, int Tm, int max_len,
+                       float* ws, void* stream);
 /* Workspace floats of a batch of B clips decoded over R >= B rows (R = B for greedy / sampled search, B * beam for beam
  * search); the same (B, R, Tm, max_len) go to every call that shares the workspace.  16-byte aligned. */
 long ac_bah_workspace_floats(const ac_bah_weights* w, int B, int R, int Tm, int max_len);
@@ -589,10 +603,36 @@ int ac_bah_train_backward(const ac_bah_weights* w, const ac_bah_grads* g, const 
                           const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
                           unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
                           float* d_fc_emb, float* ws, void* stream);
+/* The same two for variants 1 and 2 (no tags, no rollout): cond [B] instead of fc_emb.  The gradient struct follows the
+ * weight struct - unused slots NULL; variant 1: fc_w = where d condition_embedding.weight [2][E] is added; variant 2: w_ih =
+ * the gradient of weight_ih_l0 in the parameter's REAL layout [3d][E + A + 1] (not the pack's), fc_w = w_ih + E + A, its
+ * last column at row pitch E + A + 1.  cond gets no gradient; d_fc_emb [B][F] is written as zeros. */
+int ac_bah_train_forward_cond(const ac_bah_weights* w, const float* attn_emb, const float* cond, const int* mem_len,
+                              const long long* cap, long cap_ld, const int* use_cap, int B, int Tm, int T, int start_idx,
+                              float drop_p, unsigned long long drop_seed, const unsigned long long* seed_dev, int64_t* seq,
+                              float* logit, float* logprob, float* embed, float* attn_weight, float* state, float* ws,
+                              void* stream);
+int ac_bah_train_backward_cond(const ac_bah_weights* w, const ac_bah_grads* g, const float* attn_emb, const float* cond,
+                               const int* mem_len, const float* dlogit, int B, int Tm, int T, float drop_p,
+                               unsigned long long drop_seed, const unsigned long long* seed_dev, float* d_attn_emb,
+                               float* d_fc_emb, float* ws, void* stream);
 /* Backward of fc_emb = mean_with_lens(attn_emb)[:, :F] (rnn_encoder.py:44): d_attn_emb[b][t][c] += d_fc_emb[b][c] / lens[b]
  * for t < lens[b], c < F <= A. */
 int ac_bah_mean_lens_bwd(const float* d_fc_emb, const int* lens, float* d_attn_emb, int B, int Tm, int A, int F,
                          void* stream);
+
+/* ---- specificity loss (captioning/losses/loss.py:195-219 SpecificityLossWrapper's condition term; csrc/spec_loss.hip) ----
+ * logit [N][T][V] (contiguous), word_spec [V], tgt_len [N] int32 (the caption lengths WITH <eos>: position t counts when
+ * t < tgt_len[n] - 1), cond [N].  s[n][t] = sum_v softmax(logit[n][t])_v word_spec[v]; c[n] = sum over the counted t of s,
+ * divided by tgt_len[n] - 1 when mean_reduce != 0 (mean_with_lens; the caller refuses tgt_len < 2 there);
+ * loss[0] = mean_n (c[n] - cond[n])^2.  Kept for the backward: row_s [N*T] (0 at positions not counted), row_lse [N*T],
+ * diff [N] = c - cond.  The backward WRITES dlogit [N][T][V] = g_dev[0] (2 / N) diff[n] scale[n] p_v (word_spec[v] - s),
+ * exact zeros in the rows not counted.  No atomics; AC_ERR_ARG for a NULL pointer or a non-positive size. */
+int ac_specificity_loss(const float* logit, const float* word_spec, const int* tgt_len, const float* cond, int N, int T,
+                        int V, int mean_reduce, float* row_s, float* row_lse, float* diff, float* loss, void* stream);
+int ac_specificity_loss_bwd(const float* logit, const float* word_spec, const int* tgt_len, const float* row_s,
+                            const float* row_lse, const float* diff, const float* g_dev, int N, int T, int V,
+                            int mean_reduce, float* dlogit, void* stream);
 
 /* ---- sound-event tagger (Cnn8rnnSedModel, hf_wrapper.py:1791-1859; csrc/sed.hip) ------------------------------------
  * The tagger's convolutions run on the Cnn14 conv kernels above in mode 0; these entries are what they lack.
