@@ -21,8 +21,6 @@ sentence rule, the canonical-id table and the cache of packed references are tho
 Not built, and not part of ``eval_prediction``: the PTB tokenizer (input is taken as tokenized, the reference's
 ``pretokenized=True``), METEOR and SPICE (Java), SPIDEr (needs SPICE) and FENSE (a language model).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -54,18 +52,13 @@ class _StringMetric(PackedScorer):
         lib = _lib.load()
         dev = canon.device
         self._check_references(batch)
-        sets, ints, pointers = self._device_inputs(batch, words, start_idx, end_idx, canon, vocab_size)
-        S, K = len(sets), batch.first_row.shape[0]
+        S, keep, planes, refs = self._device_inputs(batch, words, start_idx, end_idx, canon, vocab_size)
+        K = batch.first_row.shape[0]
         need = lib.ac_capmetrics_workspace_bytes(K, S)
         if need < 0:
             raise _lib.HipLibraryError(f"ac_capmetrics_workspace_bytes refused ({K} keys, {S} sets)")
         workspace = self._workspace_of(need, dev)
-        hyp = (ctypes.c_void_p * S)(*[w.data_ptr() for w in sets])
-        p_words, p_sent, p_key, p_row, p_first = pointers
-        shared = (ctypes.cast(hyp, ctypes.c_void_p), S, sets[0].stride(0), batch.row_key.shape[0], sets[0].shape[1],
-                  int(start_idx), int(end_idx), ptr(canon), int(vocab_size), p_words, batch.words.shape[0], p_sent,
-                  batch.sent_off.shape[0] - 1, batch.max_ref_words, p_key, K, p_row, p_first)
-        out = self._launch(lib, batch, S, dev, shared, (ptr(workspace), workspace.numel()))
+        out = self._launch(lib, batch, S, dev, planes + refs, (ptr(workspace), workspace.numel()))
         out["keys"] = batch.keys
         return out
 

@@ -105,12 +105,33 @@ class PackedScorer:
         self._refs = (None, {})   # (key2refs, {key: [ids of each reference]})
         self.packed_keys = 0      # keys packed since the last clear (a key is packed once per key2refs)
 
-    def pack_ids(self, key2refs, vocabulary, vocab_size, keys):
-        """The PackedBatch of ``keys`` (one per row) under ``vocabulary`` and the canonical-id table (host)."""
+    def _canon(self, vocabulary, vocab_size, dev=None):
+        """The canonical-id table of ``vocabulary``, built once per vocabulary (another vocabulary clears every cache):
+        the host array, or with ``dev`` its copy on that device, uploaded once per device."""
         vocab_size = int(vocab_size)
         if self._vocab is None or self._vocab[0] is not vocabulary or self._vocab[1] != vocab_size:
             self.clear_cache()
             self._vocab = (vocabulary, vocab_size) + canonical_ids(vocabulary, vocab_size) + ({},)
+        if dev is not None and dev not in self._vocab[4]:
+            self._vocab[4][dev] = torch.from_numpy(self._vocab[3]).to(dev)
+        return self._vocab[3] if dev is None else self._vocab[4][dev]
+
+    @staticmethod
+    def _device_of(tensors):
+        """The device of the first of ``tensors`` that lives on one, else the current one."""
+        on_dev = [w.device for w in tensors if w.is_cuda]
+        return on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+
+    def _refuse_foreign_ids(self, w, vocab_size, start_idx, end_idx, what="word id"):
+        """ValueError for an id in ``w`` that is neither in the vocabulary nor start / end, if ``w`` is held on the host: a
+        host copy can be checked; on the device the kernel answers a bad id with NaN."""
+        if not w.is_cuda and not bool((((w >= 0) & (w < vocab_size)) | (w == start_idx) | (w == end_idx)).all()):
+            raise ValueError(f"{self._who}: a {what} outside [0, {vocab_size})")
+
+    def pack_ids(self, key2refs, vocabulary, vocab_size, keys):
+        """The PackedBatch of ``keys`` (one per row) under ``vocabulary`` and the canonical-id table (host)."""
+        vocab_size = int(vocab_size)
+        canon = self._canon(vocabulary, vocab_size)
         if self._refs[0] is not key2refs:
             self._refs = (key2refs, {})
         word2id, cache = self._vocab[2], self._refs[1]
@@ -124,22 +145,17 @@ class PackedScorer:
 
         batch = PackedBatch(list(keys), refs_of_key, 0, self._who)
         batch.n_words = vocab_size + len(self._oov)
-        return batch, self._vocab[3]
+        return batch, canon
 
     def _pack_for_ids(self, key2refs, vocabulary, vocab_size, keys, words):
-        """``(batch, hypothesis tensors, canon on the device)`` for ``score_ids``: the device is that of the first
-        hypothesis set that lives on one, else the current one."""
+        """``(batch, hypothesis tensors, canon on the device)`` for ``score_ids``."""
         words = [torch.as_tensor(w) for w in words]
-        on_dev = [w.device for w in words if w.is_cuda]
-        dev = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+        dev = self._device_of(words)
         keys = list(keys)
         if words[0].dim() != 2 or words[0].shape[0] != len(keys):
             raise ValueError(f"{self._who}: {len(keys)} keys for hypothesis words of shape {tuple(words[0].shape)}")
-        batch, canon = self.pack_ids(key2refs, vocabulary, vocab_size, keys)
-        canon_dev = self._vocab[4].get(dev)
-        if canon_dev is None:
-            canon_dev = self._vocab[4][dev] = torch.from_numpy(canon).to(dev)
-        return batch, words, canon_dev
+        batch, _ = self.pack_ids(key2refs, vocabulary, vocab_size, keys)
+        return batch, words, self._canon(vocabulary, vocab_size, dev)
 
     def _pack_strings(self, references, hypothesis):
         """pycocoevalcap's arguments as ``(batch, rows, start_idx, end_idx, vocab_size)``: one row per key in the order of
@@ -170,8 +186,10 @@ class PackedScorer:
 
     def _device_inputs(self, batch, words, start_idx, end_idx, canon, vocab_size):
         """Everything the host can check, raised as ValueError before the first launch, then the hypothesis sets as int32
-        planes of one length and stride on the device of ``canon`` and the references in one upload:
-        ``(sets, ints, (ref_words, sent_off, key_off, row_key, first_row) pointers)``; ``ints`` owns that memory."""
+        planes of one length and stride on the device of ``canon`` and the references in one upload.  Returns
+        ``(S, keep, planes, refs)``: the leading arguments every scorer's entry point takes, in two runs (``planes``: the
+        hypothesis sets up to ``vocab_size``; ``refs``: the packed references; ``ac_cider_scores`` takes ``n_words``
+        between them), and ``keep``, which owns the memory they point to."""
         who = self._who
         dev = canon.device
         N = batch.row_key.shape[0]
@@ -189,10 +207,7 @@ class PackedScorer:
                 raise ValueError(f"{who}: hypothesis words must be ({N} rows, length), got {tuple(w.shape)}")
             if w.shape[1] > MAX_HYP_WORDS:
                 raise ValueError(f"{who}: hypotheses of {w.shape[1]} words; the kernels take {MAX_HYP_WORDS}")
-            if not w.is_cuda:      # a host copy can be checked; on the device the kernel answers a bad id with NaN
-                ok = ((w >= 0) & (w < vocab_size)) | (w == start_idx) | (w == end_idx)
-                if not bool(ok.all()):
-                    raise ValueError(f"{who}: a hypothesis word id outside [0, {vocab_size})")
+            self._refuse_foreign_ids(w, vocab_size, start_idx, end_idx, "hypothesis word id")
             sets.append(w.to(device=dev, dtype=torch.int32))
         T = sets[0].shape[1]
         if any(w.shape[1] != T for w in sets):
@@ -203,8 +218,13 @@ class PackedScorer:
         host = np.concatenate((batch.words, batch.sent_off, batch.key_off, batch.row_key, batch.first_row))
         ints = torch.from_numpy(host).to(dev)          # the one upload
         base = ints.data_ptr()
-        at = np.cumsum([0, W, M + 1, K + 1, N])
-        return sets, ints, tuple(ctypes.c_void_p(base + 4 * int(o)) for o in at)
+        p_words, p_sent, p_key, p_row, p_first = (ctypes.c_void_p(base + 4 * int(o)) for o in np.cumsum([0, W, M + 1, K + 1, N]))
+        S = len(sets)
+        hyp = (ctypes.c_void_p * S)(*[w.data_ptr() for w in sets])
+        planes = (ctypes.cast(hyp, ctypes.c_void_p), S, sets[0].stride(0), N, T, int(start_idx), int(end_idx), ptr(canon),
+                  int(vocab_size))
+        refs = (p_words, W, p_sent, M, batch.max_ref_words, p_key, K, p_row, p_first)
+        return S, (sets, ints, hyp), planes, refs
 
     def _workspace_of(self, need, dev):
         if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
@@ -233,21 +253,15 @@ class Cider(PackedScorer):
         first launch: what the host can see raises ValueError here, and the entry point checks its limits again."""
         lib = _lib.load()
         dev = canon.device
-        sets, ints, (p_words, p_sent, p_key, p_row, p_first) = self._device_inputs(batch, words, start_idx, end_idx, canon,
-                                                                                   vocab_size)
-        T = sets[0].shape[1]
-        S, N, K = len(sets), batch.row_key.shape[0], batch.first_row.shape[0]
-        M, W = batch.sent_off.shape[0] - 1, batch.words.shape[0]
+        S, keep, planes, refs = self._device_inputs(batch, words, start_idx, end_idx, canon, vocab_size)
+        N, K, M, W = batch.row_key.shape[0], batch.first_row.shape[0], batch.sent_off.shape[0] - 1, batch.words.shape[0]
         need = lib.ac_cider_workspace_bytes(W, M, K, S)
         if need < 0:
             raise _lib.HipLibraryError(f"ac_cider_workspace_bytes refused ({W} words, {M} sentences, {K} keys, {S} sets)")
         workspace = self._workspace_of(need, dev)
         scores = torch.empty(S, N, device=dev, dtype=torch.float32)
         reward = torch.empty(N, device=dev, dtype=torch.float32) if S >= 2 else None
-        hyp = (ctypes.c_void_p * S)(*[w.data_ptr() for w in sets])
-        check(lib.ac_cider_scores(ctypes.cast(hyp, ctypes.c_void_p), S, sets[0].stride(0), N, T, int(start_idx), int(end_idx),
-                                  ptr(canon), int(vocab_size), batch.n_words, p_words, W, p_sent, M, batch.max_ref_words,
-                                  p_key, K, p_row, p_first, self._n, self._sigma, ptr(workspace), workspace.numel(),
+        check(lib.ac_cider_scores(*planes, batch.n_words, *refs, self._n, self._sigma, ptr(workspace), workspace.numel(),
                                   ptr(scores), ptr(reward), stream()), "ac_cider_scores")
         return scores, reward
 

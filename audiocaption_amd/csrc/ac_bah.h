@@ -46,14 +46,6 @@ long bah_ld_ih(const ac_bah_weights* w) { return w->variant == BAH_SPEC ? bah_xw
 
 size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }   // every carved array starts 16-byte aligned
 
-__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();   // sh may still be read by a previous call
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return is_max ? fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) : (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // Y[M][N] = X[M][K] W[N][K]^T + bias on the exact-f32 MFMA GEMM of csrc/train.hip
 int gemm(const float* X, long ldx, const float* W, long ldw, const float* bias, float* Y, long ldy, int M, int N, int K,
          void* stream) {

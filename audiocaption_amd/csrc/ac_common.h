@@ -58,6 +58,43 @@ __device__ __forceinline__ float wave_max(float v) {
   v = row16_max(v);
   return fmaxf(fmaxf(lane_read(v, 0), lane_read(v, 16)), fmaxf(lane_read(v, 32), lane_read(v, 48)));
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Reductions over a workgroup of exactly 256 threads (four waves).  Every thread calls, the result lands in every
+// thread; sh is 4 words of LDS (per value), and the leading barrier is there because sh may still be read by a previous
+// call.  The order of the additions is fixed: lanes by wave_sum, then (wave 0 + wave 1) + (wave 2 + wave 3).
+__device__ __forceinline__ float block_max256(float v, float* sh) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+__device__ __forceinline__ float block_sum256(float v, float* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// K sums at once, each in place, behind one pair of barriers
+template <typename T, int K>
+__device__ __forceinline__ void block_sums256(T (&v)[K], T (*sh)[4]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
+}
 
 // swish / sigmoid on the transcendental unit: v_exp_f32 and v_rcp_f32 (1 ulp each), 6 instructions instead of the ~25 of
 // expf + an IEEE division.  EfficientNet applies one swish per activation, which made the accurate form the largest VALU

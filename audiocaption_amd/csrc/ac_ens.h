@@ -23,21 +23,6 @@ __device__ __forceinline__ int ens_col(int tid, int i) {
   return STRIDED ? (tid + 256 * (i >> 2)) * 4 + (i & 3) : tid * NPT + i;
 }
 
-__device__ __forceinline__ float ens_block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float ens_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // x[i] = m[ens_col(tid, i)], -inf beyond V.  sh: 4 words of LDS.  All 256 threads must call it.
 template <int NPT, bool STRIDED>
 __device__ __forceinline__ void ens_mean(const EnsPlanes& e, int r, int V, float (&x)[NPT], float* sh) {
@@ -64,11 +49,11 @@ __device__ __forceinline__ void ens_mean(const EnsPlanes& e, int r, int V, float
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NPT; ++i) mx = fmaxf(mx, y[i]);
-    mx = ens_block_max(mx, sh);
+    mx = block_max256(mx, sh);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NPT; ++i) s += expf(y[i] - mx);   // exp(-inf) = 0 beyond V
-    const float lse = mx + logf(ens_block_sum(s, sh));
+    const float lse = mx + logf(block_sum256(s, sh));
 #pragma unroll
     for (int i = 0; i < NPT; ++i) x[i] += y[i] - lse;
   }

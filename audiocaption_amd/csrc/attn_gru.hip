@@ -119,14 +119,14 @@ __global__ __launch_bounds__(256) void bah_attn_kernel(AttnP p) {
   __syncthreads();
   float m = -INFINITY;
   for (int t = tid; t < p.Tm; t += 256) m = fmaxf(m, s_w[t]);
-  m = block_reduce(m, s_red, true);
+  m = block_max256(m, s_red);
   float sum = 0.f;
   for (int t = tid; t < p.Tm; t += 256) {
     const float e = expf(s_w[t] - m);
     s_w[t] = e;
     sum += e;
   }
-  sum = block_reduce(sum, s_red, false);
+  sum = block_sum256(sum, s_red);
   for (int t = tid; t < p.Tm; t += 256) {
     const float wgt = s_w[t] / sum;
     s_w[t] = wgt;

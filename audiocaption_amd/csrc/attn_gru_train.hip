@@ -154,14 +154,14 @@ __global__ __launch_bounds__(256) void bah_train_attn_kernel(TAttnP p) {
   __syncthreads();
   float m = -INFINITY;
   for (int t = tid; t < p.Tm; t += 256) m = fmaxf(m, s_w[t]);
-  m = block_reduce(m, s_red, true);
+  m = block_max256(m, s_red);
   float sum = 0.f;
   for (int t = tid; t < p.Tm; t += 256) {
     const float e = expf(s_w[t] - m);
     s_w[t] = e;
     sum += e;
   }
-  sum = block_reduce(sum, s_red, false);
+  sum = block_sum256(sum, s_red);
   for (int t = tid; t < p.Tm; t += 256) {
     const float wgt = s_w[t] / sum;
     s_w[t] = wgt;
@@ -219,13 +219,13 @@ __global__ __launch_bounds__(256) void bah_train_pick_kernel(const float* logit,
     const float x = lg[v];
     if (x > best) { best = x; bi = v; }
   }
-  const float m = block_reduce(best, s_red, true);
+  const float m = block_max256(best, s_red);
   // the smallest index that holds the maximum (indices below 2^24 are exact in f32)
   float c = (best == m && bi < V) ? -(float)bi : -INFINITY;
-  c = block_reduce(c, s_red, true);
+  c = block_max256(c, s_red);
   float sum = 0.f;
   for (int v = tid; v < V; v += 256) sum += expf(lg[v] - m);
-  sum = block_reduce(sum, s_red, false);
+  sum = block_sum256(sum, s_red);
   if (tid == 0) {
     seq[(size_t)b * ld_out] = c > -INFINITY ? (int64_t)(-c) : 0;
     logprob[(size_t)b * ld_out] = -logf(sum);
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void bah_train_attn_bwd_kernel(TAttnBP p) {
   // softmax backward over the valid frames: dscore_tm = w_tm (dw_tm - sum_k w_k dw_k)
   float part = 0.f;
   for (int tm = tid; tm < nt; tm += 256) part = fmaf(wrow[tm], s_ds[tm], part);
-  const float dot = block_reduce(part, s_red, false);
+  const float dot = block_sum256(part, s_red);
   for (int tm = tid; tm < nt; tm += 256) s_ds[tm] = len > 0 ? wrow[tm] * (s_ds[tm] - dot) : 0.f;
   __syncthreads();
   // score_tm = sum_a v_a tanh(q_a + ek[tm][a]), tanh recomputed; a lane owns columns lane, lane + 64, ...

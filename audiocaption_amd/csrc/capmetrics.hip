@@ -1,7 +1,8 @@
 // BLEU-1..4 and ROUGE-L on token ids, as pycocoevalcap's bleu_scorer.py (option "closest") and rouge.py (beta 1.2)
 // compute them on words: the two string metrics of the reference's evaluation (train_eval/base.py) that need neither
-// Java nor a language model.  They read what ac_cider_scores reads (csrc/cider.hip): hypothesis planes behind a host
-// array of device pointers, the sentence rule of model_util.py:117-164, canonical ids, packed references per key.
+// Java nor a language model.  Their arguments - hypothesis planes behind a host array of device pointers, packed references
+// per key - their sentence rule and the count of an n-gram at its first occurrence are those of ac_ngram.h; this file owns
+// the matching against the references, the LCS and the closed formulas.
 //
 //   bleu_key_kernel     one workgroup per (key, set): the hypothesis in LDS; tf of every distinct hypothesis n-gram at its
 //                       first occurrence; each reference staged in LDS in turn and counted against, the maximum kept per
@@ -16,8 +17,7 @@
 // only in the closed formulas on those integers and in one sum of fixed order (a thread's strided keys, then the threads
 // in order), so a call is bitwise repeatable.  A reference word is only ever compared, a hypothesis word indexes `canon`
 // after its range check: nothing here is indexed by a word.
-#include "ac_common.h"
-#include "../../include/audiocaption_hip.h"
+#include "ac_ngram.h"
 
 #include <math.h>
 
@@ -27,20 +27,7 @@ constexpr int kThreads = 256;
 constexpr int kMaxOrder = 4;
 constexpr int kHypWords64 = AC_CIDER_MAX_HYP_WORDS / 64;
 
-struct MetricArgs {
-  const int* hyp[AC_CIDER_MAX_SETS];
-  long hyp_ld;
-  int sets, N, T, start_idx, end_idx;
-  const int* canon;
-  int vocab_size;
-  const int* words;      // [W] reference words, canonical ids
-  int W;
-  const int* sent_off;   // [M + 1]
-  int M;
-  const int* key_off;    // [K + 1] first sentence of each key
-  int K;
-  const int* row_key;    // [N]
-  const int* first_row;  // [K]
+struct MetricArgs : HypView, RefView {
   int order;
   double* key_score;     // workspace: BLEU [sets][K][4], ROUGE-L [sets][K]
   int* ints;             // BLEU stats [sets][K][2 + 2 * order]; ROUGE-L lcs [sets][M]
@@ -48,50 +35,18 @@ struct MetricArgs {
   double* total;         // BLEU corpus [sets][order]; ROUGE-L mean [sets]
 };
 
-__device__ __forceinline__ bool sentence_range(const MetricArgs& a, int s, int* begin, int* end) {
-  const int b = a.sent_off[s], e = a.sent_off[s + 1];
-  *begin = b;
-  *end = e;
-  return b >= 0 && e >= b && e <= a.W && e - b <= AC_CIDER_MAX_REF_WORDS;
-}
-
-__device__ __forceinline__ bool key_range(const MetricArgs& a, int k, int* s0, int* s1) {
-  const int b = a.key_off[k], e = a.key_off[k + 1];
-  *s0 = b;
-  *s1 = e;
-  return b >= 0 && e > b && e <= a.M;
-}
-
-// The sentence of the key's first row into hw (LDS, AC_CIDER_MAX_HYP_WORDS ints): start skipped, cut at the first end,
-// canonical ids.  raw / can: LDS staging of T ints each.  Returns the length, or -1 for a word outside the vocabulary
-// (which is never used as an index) or a first_row outside the batch.  Every thread of the workgroup calls it.
-__device__ int load_hypothesis(const MetricArgs& a, int k, int set, int* hw, int* raw, int* can, int* sh_len) {
-  const int row = a.first_row[k];
-  const bool row_ok = row >= 0 && row < a.N;
-  if (row_ok)
-    for (int t = threadIdx.x; t < a.T; t += kThreads) {
-      const int w = a.hyp[set][(long)row * a.hyp_ld + t];
-      raw[t] = w;
-      can[t] = w >= 0 && w < a.vocab_size ? a.canon[w] : -1;
+// The hypothesis of key k and its references, as far as both kernels refuse them alike: a sentence that does not fit the
+// LDS staging, a key without a sentence.  Returns the hypothesis' length (load_key_sentence), or -1; uniform over the
+// workgroup, every thread of which calls it.
+__device__ int load_key(const MetricArgs& a, int k, int set, int* hw, int* raw, int* can, int* sh_len, int* s0, int* s1) {
+  const int L = load_key_sentence(a, a, k, set, hw, raw, can, sh_len);
+  bool ok = L >= 0 && key_range(a, k, s0, s1) && *s1 > *s0;
+  if (ok)
+    for (int s = *s0; s < *s1; ++s) {
+      int b, e;
+      ok = ok && sentence_range(a, s, &b, &e) && e - b <= AC_CIDER_MAX_REF_WORDS;
     }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int L = 0;
-    bool bad = !row_ok;
-    for (int t = 0; row_ok && t < a.T; ++t) {
-      const int w = raw[t];
-      if (w == a.end_idx) break;
-      if (w == a.start_idx) continue;
-      if (w < 0 || w >= a.vocab_size) {
-        bad = true;
-        break;
-      }
-      hw[L++] = can[t];
-    }
-    *sh_len = bad ? -1 : L;
-  }
-  __syncthreads();
-  return *sh_len;
+  return ok ? L : -1;
 }
 
 // bleu_scorer.py, one sentence or the corpus: b_k = prod_{j <= k} (correct[j] + tiny) / (guess[j] + small),
@@ -119,15 +74,9 @@ __global__ __launch_bounds__(kThreads) void bleu_key_kernel(MetricArgs a) {
   const int width = 2 + 2 * a.order;
   int* stats = a.ints + ((long)set * a.K + k) * width;
   double* score = a.key_score + ((long)set * a.K + k) * kMaxOrder;
-  const int L = load_hypothesis(a, k, set, hw, tf[0], tf[1], &sh_len);
   int s0, s1;
-  bool ok = L >= 0 && key_range(a, k, &s0, &s1);
-  if (ok)
-    for (int s = s0; s < s1; ++s) {
-      int b, e;
-      ok = ok && sentence_range(a, s, &b, &e);
-    }
-  if (!ok) {   // (uniform over the workgroup: every thread read the same words)
+  const int L = load_key(a, k, set, hw, tf[0], tf[1], &sh_len, &s0, &s1);
+  if (L < 0) {
     for (int i = threadIdx.x; i < width; i += kThreads) stats[i] = -1;
     if (threadIdx.x < kMaxOrder) score[threadIdx.x] = NAN;
     return;
@@ -136,16 +85,8 @@ __global__ __launch_bounds__(kThreads) void bleu_key_kernel(MetricArgs a) {
   if (threadIdx.x < kMaxOrder) sh_correct[threadIdx.x] = 0;
   for (int n = 0; n < a.order; ++n)
     for (int p = threadIdx.x; p + n < L; p += kThreads) {
-      int count = 0;
-      bool first = true;
-      for (int q = 0; q + n < L; ++q) {
-        bool same = true;
-        for (int i = 0; i <= n; ++i) same = same && hw[q + i] == hw[p + i];
-        if (same) {
-          ++count;
-          first = first && q >= p;
-        }
-      }
+      bool first;
+      const int count = gram_count(hw, L, p, n + 1, &first);
       tf[n][p] = first ? count : 0;
       mx[n][p] = 0;
     }
@@ -250,15 +191,9 @@ __global__ __launch_bounds__(kThreads) void rouge_key_kernel(MetricArgs a) {
   __shared__ double best[kThreads / 64][2];
   const int k = blockIdx.x, set = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int L = load_hypothesis(a, k, set, hw, raw, can, &sh_len);
   int s0, s1;
-  bool ok = L >= 0 && key_range(a, k, &s0, &s1);
-  if (ok)
-    for (int s = s0; s < s1; ++s) {
-      int b, e;
-      ok = ok && sentence_range(a, s, &b, &e);
-    }
-  if (!ok) {
+  const int L = load_key(a, k, set, hw, raw, can, &sh_len, &s0, &s1);
+  if (L < 0) {
     if (threadIdx.x == 0) a.key_score[(long)set * a.K + k] = NAN;
     return;
   }
@@ -334,27 +269,17 @@ __global__ __launch_bounds__(kThreads) void rouge_finish_kernel(MetricArgs a) {
   }
 }
 
-inline long align256(long b) { return (b + 255) & ~255L; }
-
-constexpr long kMaxRefWordsTotal = 1L << 26;   // as csrc/cider.hip
-
 // what both entry points check, and the arguments both kernels share
 int fill(MetricArgs* a, const int* const* hyp, int sets, long hyp_ld, int N, int T, int start_idx, int end_idx,
          const int* canon, int vocab_size, const int* ref_words, long total_words, const int* sent_off, int sentences,
          int max_ref_words, const int* key_off, int keys, const int* row_key, const int* first_row, void* workspace,
          long workspace_bytes, const void* ints, const void* scores, const void* total) {
-  if (!hyp || sets <= 0 || sets > AC_CIDER_MAX_SETS || N <= 0 || T <= 0 || T > AC_CIDER_MAX_HYP_WORDS || hyp_ld < T ||
-      !canon || vocab_size <= 0 || !ref_words || total_words < 0 || total_words > kMaxRefWordsTotal || !sent_off ||
-      sentences <= 0 || max_ref_words < 0 || max_ref_words > AC_CIDER_MAX_REF_WORDS || !key_off || keys <= 0 ||
-      keys > sentences || !row_key || !first_row || !workspace || ((uintptr_t)workspace & 255) || !ints || !scores || !total)
+  const int rc = fill_views(a, a, hyp, sets, hyp_ld, N, T, start_idx, end_idx, canon, vocab_size, ref_words, total_words,
+                            sent_off, sentences, max_ref_words, key_off, keys, row_key, first_row);
+  if (rc != AC_OK) return rc;
+  if (!workspace || ((uintptr_t)workspace & 255) || !ints || !scores || !total ||
+      workspace_bytes < align256(8L * kMaxOrder * sets * keys))
     return AC_ERR_ARG;
-  for (int s = 0; s < sets; ++s)
-    if (!hyp[s]) return AC_ERR_ARG;
-  if (workspace_bytes < align256(8L * kMaxOrder * sets * keys)) return AC_ERR_ARG;
-  for (int s = 0; s < sets; ++s) a->hyp[s] = hyp[s];
-  a->hyp_ld = hyp_ld; a->sets = sets; a->N = N; a->T = T; a->start_idx = start_idx; a->end_idx = end_idx;
-  a->canon = canon; a->vocab_size = vocab_size; a->words = ref_words; a->W = (int)total_words; a->sent_off = sent_off;
-  a->M = sentences; a->key_off = key_off; a->K = keys; a->row_key = row_key; a->first_row = first_row;
   a->key_score = (double*)workspace; a->ints = (int*)ints; a->scores = (double*)scores; a->total = (double*)total;
   return AC_OK;
 }

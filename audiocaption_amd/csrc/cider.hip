@@ -2,10 +2,10 @@
 // document frequencies from the scored batch's own references) on token ids, for the reward of self-critical sequence
 // training: score(sampled) and score(greedy) per clip, and their difference, without a trip through the host.
 //
-// A distinct n-gram of the references is identified by the slot it holds in one open-addressing table.  A slot stores
-// the position of one occurrence of the n-gram in the flat reference words (position * 4 + words - 1); a probe compares
-// the WORDS at that position with its own, so two n-grams share a slot only if they are equal, whatever the hash does.
-// Everything after the table is integer equality of slots:
+// A distinct n-gram of the references is identified by the slot it holds in one table over the flat reference words;
+// the table, the sentence rule, the counts at a first occurrence and the view of the packed arguments are those of
+// ac_ngram.h.  This file owns the document frequencies, every tf * idf formula and the similarity.  Everything after the
+// table is integer equality of slots:
 //
 //   cider_insert_kernel  one workgroup per reference sentence: slot of every n-gram occurrence (atomicCAS claims)
 //   cider_df_kernel      one workgroup per key: df[slot] += 1 for the key's first occurrence of each slot (integer atomicAdd)
@@ -15,10 +15,9 @@
 //   cider_scatter_kernel score of a row = score of its key; reward = set 0 - set 1
 //
 // Floating-point sums run over positions in a fixed order (a thread's strided positions, then the wave and workgroup
-// tree of block_sum), and the integer atomics commute, so a call is bitwise repeatable; which occurrence represents an
+// tree of block_sum256), and the integer atomics commute, so a call is bitwise repeatable; which occurrence represents an
 // n-gram in the table does depend on timing, and nothing downstream depends on it.
-#include "ac_common.h"
-#include "../../include/audiocaption_hip.h"
+#include "ac_ngram.h"
 
 #include <math.h>
 
@@ -26,21 +25,8 @@ namespace {
 
 constexpr int kThreads = 256;
 
-struct CiderArgs {
-  const int* hyp[AC_CIDER_MAX_SETS];
-  long hyp_ld;
-  int sets, N, T, start_idx, end_idx;
-  const int* canon;
-  int vocab_size, n_words;
-  const int* words;   // [W] reference words, canonical ids
-  int W;
-  const int* sent_off;   // [M + 1]
-  int M;
-  const int* key_off;   // [K + 1] first sentence of each key
-  int K;
-  const int* row_key;    // [N]
-  const int* first_row;  // [K]
-  int order;
+struct CiderArgs : HypView, RefView {
+  int n_words, order;
   float inv_2sigma2;
   // workspace
   int* rep;   // [mask + 1] representative occurrence of the slot's n-gram, -1 = empty
@@ -55,45 +41,6 @@ struct CiderArgs {
   float* reward;     // [N] or NULL
 };
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ unsigned gram_hash(const int* w, int len) {
-  unsigned h = 0x811C9DC5u ^ (unsigned)len;
-  for (int i = 0; i < len; ++i) h = (h ^ (unsigned)w[i]) * 0x01000193u;
-  h ^= h >> 15;
-  h *= 0x2C1B3C6Du;
-  return h ^ (h >> 12);
-}
-
-// does the slot's representative (an occurrence in the reference words) spell the `len` words at w?
-__device__ __forceinline__ bool gram_is(const int* words, int rep, const int* w, int len) {
-  if ((rep & 3) != len - 1) return false;
-  const int* r = words + (rep >> 2);
-  for (int i = 0; i < len; ++i)
-    if (r[i] != w[i]) return false;
-  return true;
-}
-
-__device__ __forceinline__ bool sentence_range(const CiderArgs& a, int s, int* begin, int* end) {
-  const int b = a.sent_off[s], e = a.sent_off[s + 1];
-  *begin = b;
-  *end = e;
-  return b >= 0 && e >= b && e <= a.W;
-}
-
-__device__ __forceinline__ bool key_range(const CiderArgs& a, int k, int* s0, int* s1) {
-  const int b = a.key_off[k], e = a.key_off[k + 1];
-  *s0 = b;
-  *s1 = e;
-  return b >= 0 && e >= b && e <= a.M;
-}
-
 __global__ __launch_bounds__(kThreads) void cider_insert_kernel(CiderArgs a) {
   int b, e;
   if (!sentence_range(a, blockIdx.x, &b, &e)) {
@@ -104,18 +51,7 @@ __global__ __launch_bounds__(kThreads) void cider_insert_kernel(CiderArgs a) {
     if (a.words[p] < 0 || a.words[p] >= a.n_words) a.bad[0] = 1;
     for (int n = 0; n < a.order; ++n) {
       int slot = -1;
-      if (p + n < e) {
-        const int id = p * 4 + n;
-        unsigned h = gram_hash(a.words + p, n + 1) & a.mask;
-        for (unsigned probe = 0; probe <= a.mask; ++probe) {   // (the table is at most half full)
-          const int v = atomicCAS(&a.rep[h], -1, id);
-          if (v == -1 || gram_is(a.words, v, a.words + p, n + 1)) {
-            slot = (int)h;
-            break;
-          }
-          h = (h + 1) & a.mask;
-        }
-      }
+      if (p + n < e) slot = gram_claim(a.rep, a.mask, a.words, a.words + p, n + 1, p * 4 + n);
       a.occ[(long)n * a.W + p] = slot;
     }
   }
@@ -164,20 +100,15 @@ __global__ __launch_bounds__(kThreads) void cider_ref_kernel(CiderArgs a) {
       const int slot = sl[p];
       float w = 0.f;
       if (slot >= 0) {
-        int tf = 0;
-        bool first = true;
-        for (int q = 0; q < L; ++q)
-          if (sl[q] == slot) {
-            ++tf;
-            first = first && q >= p;
-          }
+        bool first;
+        const int tf = slot_count(sl, L, p, &first);
         const int df = a.df[slot];
         w = (float)tf * (log_k - logf((float)(df > 1 ? df : 1)));
         if (first) sq += w * w;
       }
       a.refw[(long)n * a.W + b + p] = w;
     }
-    sq = block_sum(sq, red);
+    sq = block_sum256(sq, red);
     if (threadIdx.x == 0) a.refnorm[s * 4 + n] = sqrtf(sq);
   }
 }
@@ -187,41 +118,12 @@ __global__ __launch_bounds__(kThreads) void cider_hyp_kernel(CiderArgs a) {
   __shared__ int hslot[4][AC_CIDER_MAX_HYP_WORDS];
   __shared__ float hwt[4][AC_CIDER_MAX_HYP_WORDS];   // tf * idf at the first occurrence of an n-gram, 0 at its repeats
   __shared__ float red[4];
-  __shared__ int sh_len, sh_bad;
+  __shared__ int sh_len;
   const int k = blockIdx.x, set = blockIdx.y;
-  // the row and the canonical ids of its words come in with one load per thread (staged in hslot, which is written for
-  // good only later); one thread then walks them in LDS: start skipped, cut at the first end
-  const int row = a.first_row[k];
-  const bool row_ok = row >= 0 && row < a.N;
-  int* raw = hslot[0];
-  int* can = hslot[1];   // -1: not a vocabulary id
-  if (row_ok)
-    for (int t = threadIdx.x; t < a.T; t += kThreads) {
-      const int w = a.hyp[set][(long)row * a.hyp_ld + t];
-      raw[t] = w;
-      can[t] = w >= 0 && w < a.vocab_size ? a.canon[w] : -1;
-    }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int L = 0, bad = !row_ok;
-    for (int t = 0; row_ok && t < a.T; ++t) {
-      const int w = raw[t];
-      if (w == a.end_idx) break;
-      if (w == a.start_idx) continue;
-      if (w < 0 || w >= a.vocab_size) {
-        bad = 1;
-        break;
-      }
-      hw[L++] = can[t];
-    }
-    sh_len = L;
-    sh_bad = bad;
-  }
-  __syncthreads();
-  const int L = sh_len;
+  // (the row is staged in hslot[0] and hslot[1], which are written for good only later)
+  const int L = load_key_sentence(a, a, k, set, hw, hslot[0], hslot[1], &sh_len);
   int s0, s1;
-  const bool bad = sh_bad || !key_range(a, k, &s0, &s1);
-  if (bad) {
+  if (L < 0 || !key_range(a, k, &s0, &s1)) {
     if (threadIdx.x == 0) a.key_score[set * a.K + k] = NAN;
     return;
   }
@@ -230,34 +132,16 @@ __global__ __launch_bounds__(kThreads) void cider_hyp_kernel(CiderArgs a) {
   for (int n = 0; n < a.order; ++n) {
     float sq = 0.f;
     for (int p = threadIdx.x; p + n < L; p += kThreads) {
-      int tf = 0;
-      bool first = true;
-      for (int q = 0; q + n < L; ++q) {
-        bool same = true;
-        for (int i = 0; i <= n; ++i) same = same && hw[q + i] == hw[p + i];
-        if (same) {
-          ++tf;
-          first = first && q >= p;
-        }
-      }
-      int slot = -1;
-      unsigned h = gram_hash(hw + p, n + 1) & a.mask;
-      for (unsigned probe = 0; probe <= a.mask; ++probe) {
-        const int v = a.rep[h];
-        if (v == -1) break;
-        if (gram_is(a.words, v, hw + p, n + 1)) {
-          slot = (int)h;
-          break;
-        }
-        h = (h + 1) & a.mask;
-      }
+      bool first;
+      const int tf = gram_count(hw, L, p, n + 1, &first);
+      const int slot = gram_find(a.rep, a.mask, a.words, hw + p, n + 1);
       const int df = slot >= 0 ? a.df[slot] : 0;
       const float w = (float)tf * (log_k - logf((float)(df > 1 ? df : 1)));
       hslot[n][p] = slot;
       hwt[n][p] = first ? w : 0.f;
       if (first) sq += w * w;
     }
-    norm_h[n] = sqrtf(block_sum(sq, red));
+    norm_h[n] = sqrtf(block_sum256(sq, red));
   }
   __syncthreads();
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -283,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void cider_hyp_kernel(CiderArgs a) {
               break;
             }
         }
-      float val = block_sum(c, red);
+      float val = block_sum256(c, red);
       const float nr = ok ? a.refnorm[s * 4 + n] : NAN;
       // (the cosine of a clipped vector: at most 1 in exact arithmetic, so rounding may not carry it above)
       if (norm_h[n] != 0.f && nr != 0.f) val = fminf(val / (norm_h[n] * nr), 1.0f);
@@ -310,8 +194,6 @@ __global__ __launch_bounds__(kThreads) void cider_scatter_kernel(CiderArgs a) {
   if (a.reward) a.reward[n] = s01[0] - s01[1];
 }
 
-inline long align256(long b) { return (b + 255) & ~255L; }
-
 struct Layout {
   long slots, rep, df, bad, occ, refw, refnorm, key_score, total;
 };
@@ -319,8 +201,7 @@ struct Layout {
 // ref_words <= 2^26 is checked by the callers
 inline Layout layout(long ref_words, long sentences, long keys, long sets) {
   Layout l;
-  l.slots = 64;
-  while (l.slots < 8 * ref_words) l.slots *= 2;   // at most 4 n-grams per word: at most half full
+  l.slots = gram_slots(ref_words);
   long at = 0;
   l.rep = at; at += align256(4 * l.slots);
   l.occ = at; at += align256(16 * (ref_words > 0 ? ref_words : 1));   // (set to -1 together with rep)
@@ -333,12 +214,10 @@ inline Layout layout(long ref_words, long sentences, long keys, long sets) {
   return l;
 }
 
-constexpr long kMaxRefWordsTotal = 1L << 26;
-
 }  // namespace
 
 extern "C" long ac_cider_workspace_bytes(long ref_words, int sentences, int keys, int sets) {
-  if (ref_words < 0 || ref_words > kMaxRefWordsTotal || sentences <= 0 || keys <= 0 || keys > sentences || sets <= 0 ||
+  if (ref_words < 0 || ref_words > kMaxGramWords || sentences <= 0 || keys <= 0 || keys > sentences || sets <= 0 ||
       sets > AC_CIDER_MAX_SETS)
     return AC_ERR_ARG;
   return layout(ref_words, sentences, keys, sets).total;
@@ -349,24 +228,17 @@ extern "C" int ac_cider_scores(const int* const* hyp, int sets, long hyp_ld, int
                                const int* sent_off, int sentences, int max_ref_words, const int* key_off, int keys,
                                const int* row_key, const int* first_row, int order, float sigma, void* workspace,
                                long workspace_bytes, float* scores, float* reward, void* stream) {
-  if (!hyp || sets <= 0 || sets > AC_CIDER_MAX_SETS || N <= 0 || T <= 0 || T > AC_CIDER_MAX_HYP_WORDS || hyp_ld < T ||
-      !canon || vocab_size <= 0 || n_words < vocab_size || !ref_words || total_words < 0 ||
-      total_words > kMaxRefWordsTotal || !sent_off || sentences <= 0 || max_ref_words < 0 ||
-      max_ref_words > AC_CIDER_MAX_REF_WORDS || !key_off || keys <= 0 || keys > sentences || !row_key || !first_row ||
-      order < 1 || order > 4 || !(sigma > 0.f) || !isfinite(sigma) || !workspace || !scores || (reward && sets < 2) ||
-      ((uintptr_t)workspace & 255))
+  CiderArgs a = {};
+  const int rc = fill_views(&a, &a, hyp, sets, hyp_ld, N, T, start_idx, end_idx, canon, vocab_size, ref_words, total_words,
+                            sent_off, sentences, max_ref_words, key_off, keys, row_key, first_row);
+  if (rc != AC_OK) return rc;
+  if (n_words < vocab_size || order < 1 || order > 4 || !(sigma > 0.f) || !isfinite(sigma) || !workspace || !scores ||
+      (reward && sets < 2) || ((uintptr_t)workspace & 255))
     return AC_ERR_ARG;
-  for (int s = 0; s < sets; ++s)
-    if (!hyp[s]) return AC_ERR_ARG;
   const Layout l = layout(total_words, sentences, keys, sets);
   if (workspace_bytes < l.total) return AC_ERR_ARG;
   char* ws = (char*)workspace;
-  CiderArgs a = {};
-  for (int s = 0; s < sets; ++s) a.hyp[s] = hyp[s];
-  a.hyp_ld = hyp_ld; a.sets = sets; a.N = N; a.T = T; a.start_idx = start_idx; a.end_idx = end_idx;
-  a.canon = canon; a.vocab_size = vocab_size; a.n_words = n_words;
-  a.words = ref_words; a.W = (int)total_words; a.sent_off = sent_off; a.M = sentences; a.key_off = key_off; a.K = keys;
-  a.row_key = row_key; a.first_row = first_row; a.order = order; a.inv_2sigma2 = 1.0f / (2.0f * sigma * sigma);
+  a.n_words = n_words; a.order = order; a.inv_2sigma2 = 1.0f / (2.0f * sigma * sigma);
   a.rep = (int*)(ws + l.rep); a.df = (int*)(ws + l.df); a.mask = (unsigned)(l.slots - 1); a.bad = (int*)(ws + l.bad);
   a.occ = (int*)(ws + l.occ); a.refw = (float*)(ws + l.refw); a.refnorm = (float*)(ws + l.refnorm);
   a.key_score = (float*)(ws + l.key_score); a.scores = scores; a.reward = reward;

@@ -897,21 +897,6 @@ __global__ __launch_bounds__(256) void search_finalize_kernel(float* logit, floa
 // ---------------------------------------------------------------------------------------------
 // beam search, device half (base.py:282-289)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_max256(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float block_sum256(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // lp[r][:] = log_softmax(log_softmax(logit[r]) / temp) + cum[r]
 __global__ __launch_bounds__(256) void beam_logprob_kernel(const float* logit, const float* cum, float temp,
                                                            float* lp, int V) {

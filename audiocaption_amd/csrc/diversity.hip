@@ -4,9 +4,9 @@
 // eval/old_diversity.py.  Self-BLEU by its definition is quadratic in the corpus; one table of the corpus' distinct
 // n-grams with four integers per entry makes it linear and yields the other numbers on the way.
 //
-// A distinct n-gram (n = 1 .. 4) is identified by the slot it holds in one open-addressing table, as in csrc/cider.hip:
-// a slot stores the position of one occurrence in the packed words (position * 4 + n - 1), a probe compares the WORDS
-// there with its own, so two n-grams share a slot only if they are equal, whatever the hash does.  Per slot:
+// A distinct n-gram (n = 1 .. 4) is identified by the slot it holds in one table over the packed words (ac_ngram.h, as
+// are the sentence rule and the count of a slot at its first occurrence); this file owns what is kept per slot and the
+// scores made of it.  Per slot:
 //   max1  the largest count of the n-gram in one sentence       ties  the sentences that hold max1
 //   max2  the largest count among the sentences below max1      docs  the sentences that contain it
 // so that for sentence i with count tf the largest count among the OTHER sentences is max1 when tf < max1 or ties >= 2,
@@ -27,8 +27,7 @@
 // sums of fixed order (a thread's strided items, then the threads in order), so a call is bitwise repeatable - which
 // occurrence represents an n-gram in the table depends on timing, and nothing downstream depends on it.  A word is
 // range-checked before it indexes `canon`; nothing else is indexed by a word.
-#include "ac_common.h"
-#include "../../include/audiocaption_hip.h"
+#include "ac_ngram.h"
 
 #include <math.h>
 
@@ -40,7 +39,6 @@ constexpr int kMaxWords = AC_CIDER_MAX_HYP_WORDS;
 constexpr int kHist = 1280;        // lengths 0 .. kMaxWords, padded
 constexpr int kCounters = 64;      // distinct[4], total words, bad (a word outside the vocabulary), full (no slot found)
 constexpr int kTotalWords = 4, kBad = 5, kFull = 6;
-constexpr long kMaxWordsTotal = 1L << 26;   // as kMaxRefWordsTotal of the other scorers: positions * 4 + n stay in int32
 
 struct DivArgs {
   const int* hyp;
@@ -68,52 +66,14 @@ struct DivArgs {
   double* summary;     // [6]
 };
 
-__device__ __forceinline__ unsigned gram_hash(const int* w, int len) {
-  unsigned h = 0x811C9DC5u ^ (unsigned)len;
-  for (int i = 0; i < len; ++i) h = (h ^ (unsigned)w[i]) * 0x01000193u;
-  h ^= h >> 15;
-  h *= 0x2C1B3C6Du;
-  return h ^ (h >> 12);
-}
-
-// does the slot's representative (an occurrence in the packed words) spell the `len` words at w?
-__device__ __forceinline__ bool gram_is(const int* words, int rep, const int* w, int len) {
-  if ((rep & 3) != len - 1) return false;
-  const int* r = words + (rep >> 2);
-  for (int i = 0; i < len; ++i)
-    if (r[i] != w[i]) return false;
-  return true;
-}
-
 __global__ __launch_bounds__(kThreads) void div_pack_kernel(DivArgs a) {
   __shared__ int raw[kMaxWords];
   __shared__ int can[kMaxWords];   // -1: not a vocabulary id
   __shared__ int hw[kMaxWords];
   __shared__ int sh_len;
   const int row = blockIdx.x;
-  for (int t = threadIdx.x; t < a.T; t += kThreads) {
-    const int w = a.hyp[(long)row * a.hyp_ld + t];
-    raw[t] = w;
-    can[t] = w >= 0 && w < a.vocab_size ? a.canon[w] : -1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int L = 0;
-    bool bad = false;
-    for (int t = 0; t < a.T; ++t) {
-      const int w = raw[t];
-      if (w == a.end_idx) break;
-      if (w == a.start_idx) continue;
-      if (w < 0 || w >= a.vocab_size) {
-        bad = true;
-        break;
-      }
-      hw[L++] = can[t];
-    }
-    sh_len = bad ? -1 : L;
-  }
-  __syncthreads();
-  const int L = sh_len;
+  const int L = load_sentence(a.hyp + (long)row * a.hyp_ld, a.T, a.start_idx, a.end_idx, a.canon, a.vocab_size, hw, raw,
+                              can, &sh_len);
   for (int p = threadIdx.x; p < L; p += kThreads) a.words[(long)row * a.T + p] = hw[p];
   if (threadIdx.x == 0) {
     a.len[row] = L;
@@ -137,19 +97,8 @@ __global__ __launch_bounds__(kThreads) void div_insert_kernel(DivArgs a) {
   __syncthreads();
   for (int n = 0; n < kOrder; ++n) {
     for (int p = threadIdx.x; p + n < L; p += kThreads) {
-      const int id = (int)(base + p) * 4 + n;
-      int slot = -1;
-      bool fresh = false;
-      unsigned h = gram_hash(hw + p, n + 1) & a.mask;
-      for (unsigned probe = 0; probe <= a.mask; ++probe) {   // (the table is at most half full)
-        const int v = atomicCAS(&a.rep[h], -1, id);
-        if (v == -1 || gram_is(a.words, v, hw + p, n + 1)) {
-          slot = (int)h;
-          fresh = v == -1;
-          break;
-        }
-        h = (h + 1) & a.mask;
-      }
+      bool fresh;
+      const int slot = gram_claim(a.rep, a.mask, a.words, hw + p, n + 1, (int)(base + p) * 4 + n, &fresh);
       if (fresh) atomicAdd(&a.counters[n], 1);
       if (slot < 0) a.counters[kFull] = 1;   // (cannot happen below half full; read by the later launches only)
       sl[p] = slot;
@@ -157,13 +106,8 @@ __global__ __launch_bounds__(kThreads) void div_insert_kernel(DivArgs a) {
     __syncthreads();
     for (int p = threadIdx.x; p + n < L; p += kThreads) {
       const int slot = sl[p];
-      int tf = 0;
-      bool first = true;
-      for (int q = 0; q + n < L; ++q)
-        if (sl[q] == slot) {
-          ++tf;
-          first = first && q >= p;
-        }
+      bool first;
+      const int tf = slot_count(sl, L - n, p, &first);
       a.occ[(long)n * a.W + base + p] = slot;
       a.tfirst[(long)n * a.W + base + p] = first ? tf : 0;
       if (first && slot >= 0) {
@@ -304,8 +248,6 @@ __global__ __launch_bounds__(kThreads) void div_finish_kernel(DivArgs a) {
   }
 }
 
-inline long align256(long b) { return (b + 255) & ~255L; }
-
 struct Layout {
   long slots, rep, cnt, len_hist, counters, words, len, occ, tfirst, rich, total;
 };
@@ -314,8 +256,7 @@ struct Layout {
 inline Layout layout(long N, long T) {
   const long W = N * T;
   Layout l;
-  l.slots = 64;
-  while (l.slots < 8 * W) l.slots *= 2;   // at most 4 n-grams per word: at most half full
+  l.slots = gram_slots(W);
   long at = 0;
   l.rep = at; at += align256(4 * l.slots);
   l.cnt = at; at += align256(16 * l.slots);
@@ -331,7 +272,7 @@ inline Layout layout(long N, long T) {
 }
 
 inline bool sizes_ok(int N, int T) {
-  return N >= 2 && T >= 1 && T <= kMaxWords && (long)N * T <= kMaxWordsTotal;
+  return N >= 2 && T >= 1 && T <= kMaxWords && (long)N * T <= kMaxGramWords;
 }
 
 }  // namespace

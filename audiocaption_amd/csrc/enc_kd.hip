@@ -34,39 +34,11 @@ constexpr float EK_EPS = 1e-12f;
 constexpr int EK_TILE = 16;
 constexpr int EK_KC = 64;     // columns of a staged tile; rows are padded by one word against bank conflicts
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // L_ij, rounded once: every kernel must see the SAME float for a logit.  This file is built with -ffp-contract=off
 // (build.py EXTRA_FLAGS): fused into the subtraction of the maximum the product would be rounded in one place and not in
 // another, and one clip's contrastive loss would be the product's rounding error (5.7e-8) instead of exactly 0.  The
 // long sums below ask for their FMAs by name.
 __device__ __forceinline__ float ek_logit(float scale, float cos) { return scale * cos; }
-
-template <int K>
-__device__ __forceinline__ void ek_block_sum(double (&v)[K], double (*red)[4]) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum_d(v[k]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k][threadIdx.x >> 6] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
-
-__device__ __forceinline__ float ek_block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
 
 // workspace (floats): ns [B][D] | nt [B][D] | cos [B][B] | nrm_s [B] | nrm_t [B] | mse_row [B] | rstat [B][4] | cstat [B][4]
 // nrm = max(||x||, eps), stored NEGATED where the clamp holds; stat = (max, sum exp(L - max), CE term, sum_j softmax_j cos_j)
@@ -99,7 +71,7 @@ __global__ __launch_bounds__(256) void enc_kd_norm_kernel(const float* __restric
     acc[0] += a * a;
     acc[1] += b * b;
   }
-  ek_block_sum<2>(acc, red);
+  block_sums256(acc, red);
   const double ls = sqrt(acc[0]), lt = sqrt(acc[1]);
   const double ds_ = fmax(ls, (double)EK_EPS), dt_ = fmax(lt, (double)EK_EPS);
   if (tid == 0) {
@@ -116,7 +88,7 @@ __global__ __launch_bounds__(256) void enc_kd_norm_kernel(const float* __restric
     const double d = l2 ? ya - yb : a - b;
     m[0] += d * d;
   }
-  ek_block_sum<1>(m, red);
+  block_sums256(m, red);
   if (tid == 0) w.mse_row[i] = (float)m[0];
 }
 
@@ -163,7 +135,7 @@ __global__ __launch_bounds__(256) void enc_kd_stats_kernel(int B, int D, const f
     l[e] = j < B ? ek_logit(scale, c[e]) : -INFINITY;
     mx = fmaxf(mx, l[e]);
   }
-  mx = ek_block_max(mx, redf);
+  mx = block_max256(mx, redf);
   double acc[2] = {0.0, 0.0};
 #pragma unroll
   for (int e = 0; e < EK_MAXB / 256; ++e) {
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(256) void enc_kd_stats_kernel(int B, int D, const f
     acc[0] += (double)p;
     acc[1] += (double)p * (double)c[e];
   }
-  ek_block_sum<2>(acc, red);
+  block_sums256(acc, red);
   if (tid == 0) {
     float* st = (col ? w.cstat : w.rstat) + 4 * r;
     const float diag = ek_logit(scale, w.cos[(long)r * B + r]);
@@ -210,7 +182,7 @@ __global__ __launch_bounds__(256) void enc_kd_grad_kernel(const float* __restric
       }
       if (mse) a[3] += (double)w.mse_row[i];
     }
-    ek_block_sum<4>(a, red);
+    block_sums256(a, red);
     if (tid == 0) {
       const float lc = contra ? (float)(0.5 * (a[0] + a[1]) / (double)B) : 0.f;
       const float lm = mse ? (float)(a[3] / ((double)B * (double)D)) : 0.f;
@@ -274,7 +246,7 @@ __global__ __launch_bounds__(256) void enc_kd_grad_kernel(const float* __restric
       const int k = e * 256 + tid;
       if (k < D) dot[0] += g[e] * (double)yp[k];
     }
-    ek_block_sum<1>(dot, red);
+    block_sums256(dot, red);
   }
   const float* xs = s + (long)r * ld_s;
   const float* xt = t + (long)r * ld_t;

@@ -92,11 +92,11 @@ __global__ __launch_bounds__(256) void ens_beam_row_kernel(EnsPlanes ens, const 
   float m2 = -INFINITY;
 #pragma unroll
   for (int i = 0; i < NPT; ++i) m2 = fmaxf(m2, x[i] * inv_t);
-  m2 = ens_block_max(m2, sh);
+  m2 = block_max256(m2, sh);
   float s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < NPT; ++i) s2 += expf(x[i] * inv_t - m2);   // exp(-inf) = 0 beyond V
-  const float lse2 = m2 + logf(ens_block_sum(s2, sh));
+  const float lse2 = m2 + logf(block_sum256(s2, sh));
   const float cr = cum[r];
 #pragma unroll
   for (int i = 0; i < NPT; ++i) x[i] = ens_col<NPT, true>(tid, i) < V ? cr + (x[i] * inv_t - lse2) : -INFINITY;

@@ -23,20 +23,6 @@ namespace {
 
 constexpr int KD_MAXV = 16384;   // ac_scst_loss' limit: two rows of 64 words per thread
 
-template <int K>
-__device__ __forceinline__ void kd_block_sum(float (&v)[K], float (*red)[4]) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k][threadIdx.x >> 6] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
-
 template <bool VEC>
 __device__ __forceinline__ float4 kd_load4(const float* p) {
   if (VEC) return *reinterpret_cast<const float4*>(p);
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void kd_loss_kernel(const float* __restrict__ 
     }
   }
   if (edge >= 0) term(zs_e, zt_e, edge);
-  kd_block_sum<8>(acc, red);
+  block_sums256(acc, red);
   const float cnt = acc[6], cnt_t = acc[7];
   const float se1 = cnt + acc[0], seT = cnt + acc[1], stT = cnt_t + acc[2];
   const float lse1 = logf(cnt) + log1pf(acc[0] / cnt), lseT = logf(cnt) + log1pf(acc[1] / cnt);
@@ -211,7 +197,7 @@ __global__ __launch_bounds__(256) void kd_sum_kernel(const float* row_sup, const
     a[0] += row_sup[i];
     a[1] += row_kd[i];
   }
-  kd_block_sum<2>(a, red);
+  block_sums256(a, red);
   if (threadIdx.x == 0) {
     const float sup = a[0] * scale, kd = a[1] * scale;
     loss[1] = sup;

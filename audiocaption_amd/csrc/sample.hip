@@ -56,20 +56,6 @@ __device__ __forceinline__ T block_scan(T v, T* sh, T& excl, T& total, Up up) {
   return v + add;
 }
 
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 // (min of a, max of b) over the block
 __device__ __forceinline__ void block_min_max(int& a, int& b, int* sh) {
 #pragma unroll
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   float m = -INFINITY;
 #pragma unroll
   for (int i = 0; i < NPT; ++i) m = fmaxf(m, x[i]);
-  m = block_max(m, sh_f);
+  m = block_max256(m, sh_f);
 
   const bool topk = p.method == AC_SAMPLE_TOPK, topp = p.method == AC_SAMPLE_TOPP;
   // lp / temp for plain and top-k; top-p draws from softmax(logit) and Gumbel-max from softmax(lp): temp has no effect
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
 #pragma unroll
     for (int i = 0; i < NPT; ++i)
       if (c0 + i < p.V) s += expf(x[i] - m);
-    lse = logf(block_sum(s, sh_f));
+    lse = logf(block_sum256(s, sh_f));
   }
 
   // ---- the kept set: key >> shift > prefix, or == prefix and among the first n_tie of those in index order ----

@@ -15,21 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ float scst_block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float scst_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // Bookkeeping of one rollout pass: the drawn (or forced) word of clip n -> seq[n][t] under the finished-row rule.  With
 // forced words the stored log-probability is recomputed here for the forced word (the sampler stored the drawn word's).
 __global__ __launch_bounds__(256) void scst_book_kernel(const float* logit, long ld, int V, float temp, int t, int end_idx,
@@ -42,10 +27,10 @@ __global__ __launch_bounds__(256) void scst_book_kernel(const float* logit, long
     const float* z = logit + n * ld;
     float m = -INFINITY;
     for (int v = threadIdx.x; v < V; v += 256) m = fmaxf(m, z[v]);
-    m = scst_block_max(m, red);
+    m = block_max256(m, red);
     float se = 0.f;
     for (int v = threadIdx.x; v < V; v += 256) se += expf(z[v] - m);
-    se = scst_block_sum(se, red);
+    se = block_sum256(se, red);
     // (a forced word outside the vocabulary: NaN instead of a read beyond the row)
     if (threadIdx.x == 0) logprob[n * lp_ld + t] = word >= 0 && word < V ? ((z[word] - m) - logf(se)) / temp : NAN;
   }
@@ -73,10 +58,10 @@ __global__ __launch_bounds__(256) void scst_loss_kernel(const float* logit, cons
   const int w = seq[n * seq_ld + t];
   float m = -INFINITY;
   for (int v = threadIdx.x; v < V; v += 256) m = fmaxf(m, z[v]);
-  m = scst_block_max(m, red);
+  m = block_max256(m, red);
   float se = 0.f;
   for (int v = threadIdx.x; v < V; v += 256) se += expf(z[v] - m);
-  se = scst_block_sum(se, red);
+  se = block_sum256(se, red);
   const float r = reward[n];
   // (a word outside the vocabulary: NaN instead of a read beyond the row)
   if (threadIdx.x == 0) row_loss[row] = w >= 0 && w < V ? -(((z[w] - m) - logf(se)) / temp) * r : NAN;
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(256) void scst_sum_kernel(const float* x, long n, f
   __shared__ float red[4];
   float a = 0.f;
   for (long i = threadIdx.x; i < n; i += 256) a += x[i];
-  a = scst_block_sum(a, red);
+  a = block_sum256(a, red);
   if (threadIdx.x == 0) out[0] = a * scale;
 }
 

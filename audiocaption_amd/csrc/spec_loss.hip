@@ -14,14 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();   // red may still be read by a previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __device__ __forceinline__ bool row_valid(const int* tgt_len, int n, int t) { return t < tgt_len[n] - 1; }
 
 __global__ __launch_bounds__(256) void spec_row_kernel(const float* logit, const float* ws, const int* tgt_len, int T, int V,
@@ -45,8 +37,8 @@ __global__ __launch_bounds__(256) void spec_row_kernel(const float* logit, const
     se += e;
     sw = fmaf(e, ws[v], sw);
   }
-  se = block_sum(se, red);
-  sw = block_sum(sw, red);
+  se = block_sum256(se, red);
+  sw = block_sum256(sw, red);
   if (threadIdx.x == 0) {
     row_s[row] = sw / se;
     row_lse[row] = m + logf(se);
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(256) void spec_clip_kernel(const float* row_s, cons
     diff[n] = e;
     sq = fmaf(e, e, sq);
   }
-  sq = block_sum(sq, red);
+  sq = block_sum256(sq, red);
   if (threadIdx.x == 0) loss[0] = sq / (float)N;
 }
 

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
-from .cider import MAX_HYP_WORDS, PackedScorer, canonical_ids
+from .cider import MAX_HYP_WORDS, PackedScorer
 
 MAX_TOTAL_WORDS = 1 << 26     # N * T, the bound of ac_diversity_scores
 
@@ -105,9 +105,7 @@ class Diversity(PackedScorer):
     # ---- word ids ------------------------------------------------------------------------------------------------
     def score_ids(self, vocabulary, vocab_size, words, start_idx, end_idx):
         vocab_size = int(vocab_size)
-        if self._vocab is None or self._vocab[0] is not vocabulary or self._vocab[1] != vocab_size:
-            self.clear_cache()
-            self._vocab = (vocabulary, vocab_size) + canonical_ids(vocabulary, vocab_size) + ({},)
+        self._canon(vocabulary, vocab_size)   # (a vocabulary that cannot be used is refused first)
         planes = [torch.as_tensor(w) for w in (words if isinstance(words, (list, tuple)) else [words])]
         if not planes or any(w.dim() != 2 for w in planes):
             raise ValueError(f"Diversity: words must be (N, T) tensors of word ids, got "
@@ -115,15 +113,9 @@ class Diversity(PackedScorer):
         T = max(w.shape[1] for w in planes)
         self._check_sizes(sum(w.shape[0] for w in planes), T)
         for w in planes:
-            if not w.is_cuda:      # a host copy can be checked; on the device the kernel answers a bad id with NaN
-                ok = ((w >= 0) & (w < vocab_size)) | (w == start_idx) | (w == end_idx)
-                if not bool(ok.all()):
-                    raise ValueError(f"Diversity: a word id outside [0, {vocab_size})")
-        on_dev = [w.device for w in planes if w.is_cuda]
-        dev = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
-        canon_dev = self._vocab[4].get(dev)
-        if canon_dev is None:
-            canon_dev = self._vocab[4][dev] = torch.from_numpy(self._vocab[3]).to(dev)
+            self._refuse_foreign_ids(w, vocab_size, start_idx, end_idx)
+        dev = self._device_of(planes)
+        canon_dev = self._canon(vocabulary, vocab_size, dev)
         planes = [w.to(device=dev, dtype=torch.int32) for w in planes]
         # rows of a shorter plane end where they end: filled up with end_idx
         planes = [w if w.shape[1] == T else torch.nn.functional.pad(w, (0, T - w.shape[1]), value=int(end_idx))

@@ -179,6 +179,30 @@ def random_case(vocab_size, n_keys, n_rows, T, seed, max_refs=5, max_ref_words=2
 RANDOM_CASES = {"small": (12, 7, 7, 20, 101), "repeated-keys": (30, 33, 40, 20, 202), "long": (40, 4, 5, 300, 304, 3, 400)}
 
 
+def limit_case(max_hyp_words, max_ref_words, seed=405):
+    """4 rows over 3 keys (``full`` twice) with T = max_hyp_words, vocabulary of 40 ids (n-grams repeat).  Key ``full`` has
+    one reference of exactly max_ref_words words and an ordinary one; ``plain0`` and ``plain1`` have ordinary references.
+    Rows of exactly T words (no <start>, no <end>: the row is the sentence): for ``full`` the long reference with three
+    words in ten replaced (set 0) and random words (set 1), for ``plain0`` random words (set 0), for ``plain1`` its first
+    reference over and over (set 1: counts far beyond the reference's).  The other rows are ordinary; the second row of
+    ``full`` differs from the first and must not count."""
+    V = 40
+    rng = np.random.default_rng(seed)
+    word = lambda: int(rng.integers(FIRST_WORD, V))
+    some = lambda n: [word() for _ in range(n)]
+    long_ref = some(max_ref_words)
+    id_refs = {"plain0": [some(9), some(12), some(8)], "full": [long_ref, some(12)], "plain1": [some(11), some(10)]}
+    keys = ["plain0", "full", "plain1", "full"]
+    T = max_hyp_words
+    near_long = [word() if rng.random() < 0.3 else long_ref[i % max_ref_words] for i in range(T)]
+    tiled = [id_refs["plain1"][0][i % 11] for i in range(T)]
+    sets = [[some(T), near_long, _row(id_refs["plain1"][1][:7] + some(2), T, rng, V), some(T)],
+            [_row(id_refs["plain0"][1][2:], T, rng, V, start=True), some(T), tiled, _row(some(5), T, rng, V)]]
+    key2refs = {k: [" ".join(f"w{w}" for w in r) for r in refs] for k, refs in id_refs.items()}
+    return {"vocab_size": V, "vocabulary": ListVocabulary(word_list(V)), "keys": keys, "key2refs": key2refs,
+            "words": [np.asarray(rows, dtype=np.int32) for rows in sets]}
+
+
 def edge_case():
     """5 rows over 4 keys (``a`` twice), T = 8, vocabulary of 12 ids in which id 9 spells the same word as id 4.
     Hypothesis lengths 0 (<end> first), 1, 3 and 8 without <end>; a <start> in the middle of a row; repeated words on both

@@ -71,6 +71,28 @@ def test_scores_and_reward_vs_float64(lib, name):
         assert mean == float(per_key.mean())
 
 
+def test_sentences_at_the_length_limit(lib):
+    """Hypotheses of exactly MAX_HYP_WORDS words (every LDS array of cider_hyp_kernel full, the staging of the row
+    included) and a reference of exactly MAX_REF_WORDS words, among ordinary keys."""
+    from audiocaption_amd.cider import Cider, MAX_HYP_WORDS, MAX_REF_WORDS
+    case = R.limit_case(MAX_HYP_WORDS, MAX_REF_WORDS)
+    assert all(w.shape == (4, MAX_HYP_WORDS) for w in case["words"])
+    assert [len(r.split()) for r in case["key2refs"]["full"]] == [MAX_REF_WORDS, 12]
+    assert all(len(R.row_sentence(case["words"][s][row], case["vocabulary"].idx2word).split()) == MAX_HYP_WORDS
+               for s, row in ((0, 0), (0, 1), (1, 1), (1, 2)))
+    out = _score_ids(Cider(), case)
+    got = out["scores"].cpu().numpy().astype(np.float64)
+    want = np.stack([R.host_scores(case, which)[0] for which in range(2)])
+    err = np.abs(got - want).max()
+    err_r = np.abs(out["reward"].cpu().numpy().astype(np.float64) - (want[0] - want[1])).max()
+    print(f"[limit] max |score - float64| {err:.3e}, reward {err_r:.3e}; scores {want.tolist()}")
+    assert want[0, 1] > 1.0 and want[0, 2] > 1.0                 # worth comparing: the long pair and an ordinary one
+    assert not np.isnan(got).any()
+    assert err <= GATE and err_r <= GATE
+    assert got.min() >= 0.0 and got.max() <= 10.0
+    assert np.array_equal(got[:, 3], got[:, 1])                  # the second row of the key: the score of its first
+
+
 def test_closed_form_answers_on_the_device(lib):
     from audiocaption_amd.cider import Cider
     refs = {"a": ["w1 w2 w3 w4 w5"], "b": ["w6 w7"], "c": ["w8 w9 w10 w11"]}
