@@ -1,12 +1,12 @@
 """MI355X-native audio-captioning forward/decode path (Cnn14Rnn-Trm), behind the plugin API of
 wsntxxn/AudioCaption.  See DESIGN.md / INTEGRATION.md."""
 from .cnn_encoder import Cnn14Encoder
-from .config import cnn14rnn_trm_config, effb2_trm_config, init_model_from_config
+from .config import cnn14rnn_keyword_trm_config, cnn14rnn_trm_config, effb2_trm_config, init_model_from_config
 from .effnet_encoder import EfficientNetB2
 from .crnn_trm_encoder import Cnn14RnnEncoder, CrnnEncoder
 from .rnn_encoder import RnnEncoder
-from .transformer_decoder import TransformerDecoder
-from .transformer_model import CaptionModel, TransformerModel
+from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder
+from .transformer_model import CaptionModel, KeywordCondTransformerModel, TransformerModel
 from .rnn_decoder import (BahAttnCatFcDecoder, ConditionalBahAttnDecoder, RnnDecoder, Seq2SeqAttention,
                           SpecificityBahAttnDecoder, TemporalBahAttnDecoder)
 from .attn_model import ConditionalSeq2SeqAttnModel, Seq2SeqAttnModel, TemporalSeq2SeqAttnModel
@@ -24,4 +24,5 @@ __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "Tran
            "CaptionModel", "TransformerModel", "RnnDecoder", "Seq2SeqAttention", "BahAttnCatFcDecoder", "TemporalBahAttnDecoder",
            "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "ConditionalBahAttnDecoder", "SpecificityBahAttnDecoder",
            "ConditionalSeq2SeqAttnModel", "SpecificityLossWrapper", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
-           "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config"]
+           "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config",
+           "KeywordProbTransformerDecoder", "KeywordCondTransformerModel", "cnn14rnn_keyword_trm_config"]

@@ -32,6 +32,11 @@ class AcTrmWeights(ctypes.Structure):
         ("layer", AcTrmLayer * AC_MAX_LAYERS)]
 
 
+class AcTrmKeyword(ctypes.Structure):
+    """ac_trm_keyword: the keyword operands of a KeywordProbTransformerDecoder step."""
+    _fields_ = [("kwp", ctypes.c_void_p), ("ln_w", ctypes.c_void_p), ("ln_b", ctypes.c_void_p), ("row_div", ctypes.c_int32)]
+
+
 class AcBahWeights(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "emb_dim", "d_model", "attn_size", "attn_emb_dim", "fc_emb_dim", "vocab", "n_tags", "variant")] + [
@@ -102,6 +107,12 @@ SIGNATURES = {
     "ac_trm_beam_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ac_trm_beam_reorder": (_I, [_WP, _I, _I, _I, _P, _P, _P]),
     "ac_trm_beam_update_all": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # keyword-conditioned decoder (csrc/decoder.hip PRO_EMBED_KW); the second argument is ctypes.byref(AcTrmKeyword)
+    "ac_trm_kw_greedy_segments": (_I, [_WP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_trm_kw_sample": (_I, [_WP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
+    "ac_trm_kw_forward_tokens": (_I, [_WP, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "ac_trm_kw_beam_step": (_I, [_WP, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "ac_trm_kw_embed_qkv": (_I, [_WP, _P, _I, _I, _I, _P, _L, _P, _P, _P]),
     # ensemble decoding (csrc/ensemble.hip)
     "ac_trm_step_logits": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P, _L, _P, _P]),
     "ac_ens_greedy_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
@@ -142,6 +153,8 @@ SIGNATURES = {
     "ac_build_prefix": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _L, _I, _I, _P]),
     "ac_embed_fwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _F, _U64, _F, _U64, _P, _P]),
     "ac_embed_bwd": (_I, [_P, _P, _P, _L, _I, _F, _U64, _F, _U64, _P, _P]),
+    "ac_kw_embed_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _F, _U64, _F, _U64, _P, _F, _P]),
+    "ac_kw_embed_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _U64, _F, _U64, _P, _F, _P]),
     "ac_dropadd_ln_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _U64, _P, _F, _P]),
     "ac_dropadd_ln_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _L, _I, _F, _U64, _P, _F, _P]),
     "ac_attn_seq_fwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,

@@ -18,6 +18,10 @@ ALIASES = {
     "captioning.models.crnn_trm_encoder.Cnn14RnnEncoder": "audiocaption_amd.crnn_trm_encoder.Cnn14RnnEncoder",
     "captioning.models.transformer_decoder.TransformerDecoder": "audiocaption_amd.transformer_decoder.TransformerDecoder",
     "captioning.models.transformer_model.TransformerModel": "audiocaption_amd.transformer_model.TransformerModel",
+    "captioning.models.transformer_decoder.KeywordProbTransformerDecoder":
+        "audiocaption_amd.transformer_decoder.KeywordProbTransformerDecoder",
+    "captioning.models.transformer_model.KeywordCondTransformerModel":
+        "audiocaption_amd.transformer_model.KeywordCondTransformerModel",
     "captioning.models.cnn_encoder.EfficientNetB2": "audiocaption_amd.effnet_encoder.EfficientNetB2",
     "captioning.models.transformer_encoder.TransformerEncoder": "audiocaption_amd.transformer_encoder.TransformerEncoder",
     "captioning.models.crnn_trm_encoder.Cnn14TransformerEncoder": "audiocaption_amd.crnn_trm_encoder.Cnn14TransformerEncoder",
@@ -98,6 +102,17 @@ def cnn14rnn_trm_config(vocab_size=4368, encoder_name="CrnnEncoder"):
         "type": "captioning.models.transformer_model.TransformerModel",
         "args": {},
     }
+
+
+def cnn14rnn_keyword_trm_config(vocab_size=4368, keyword_classes_num=300):
+    """``cnn14rnn_trm_config`` with the reference's keyword-conditioned pair: ``KeywordCondTransformerModel`` over a
+    ``KeywordProbTransformerDecoder`` (transformer_model.py:223-264, transformer_decoder.py:177-214); ``input_dict["keyword"]``
+    is (batch, keyword_classes_num)."""
+    config = cnn14rnn_trm_config(vocab_size)
+    config["decoder"]["type"] = "captioning.models.transformer_decoder.KeywordProbTransformerDecoder"
+    config["decoder"]["args"]["keyword_classes_num"] = int(keyword_classes_num)
+    config["type"] = "captioning.models.transformer_model.KeywordCondTransformerModel"
+    return config
 
 
 def cnn14trm_trm_config(vocab_size=4368):

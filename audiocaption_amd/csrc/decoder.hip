@@ -566,17 +566,20 @@ __global__ void transpose_sq_kernel(const float* W, long ldw, int d, float* WT) 
 //   PRO_PLAIN : A = X                                   (rows of a previous kernel's output)
 //   PRO_EMBED : A = E[tok[r][t]] * sqrt(d) + pe[t]       (transformer_decoder.py:89-91)
 //   PRO_ADDLN : A = LayerNorm(X + Y2) * g + b            (the post-LN residual join of the previous sub-layer)
+//   PRO_EMBED_KW : A = LayerNorm(E[tok[r][t]] * sqrt(d) + kwp[r / kw_div]) * g + b + pe[t]
+//                  (KeywordProbTransformerDecoder, transformer_decoder.py:196-202; kwp = keyword_proj(keyword), once per batch)
 // For the fused producers the 32-row A tile is built once per block in LDS (K = d_model) and the blocks of
 // column tile 0 also write it out (xout): it is the residual stream for the next join / the `embed` output.
 // Tile 32 x 32, the four waves split K and reduce through LDS: the step is latency-, not throughput-bound.
 // ---------------------------------------------------------------------------------------------
-enum { PRO_PLAIN = 0, PRO_EMBED = 1, PRO_ADDLN = 2 };
+enum { PRO_PLAIN = 0, PRO_EMBED = 1, PRO_ADDLN = 2, PRO_EMBED_KW = 3 };
 constexpr int DEC_MAX_D = 512;
 
 struct DecGemmParams {
-  const float* X; long ldx;          // PLAIN: A rows; ADDLN: residual input
+  const float* X; long ldx;          // PLAIN: A rows; ADDLN: residual input; EMBED_KW: the projected keyword rows kwp
   const float* Y2; long ldy2;        // ADDLN: sub-layer output to add
-  const float* ln_w; const float* ln_b;
+  const float* ln_w; const float* ln_b;   // ADDLN: the join's norm; EMBED_KW: word_keyword_norm
+  int kw_div;                        // EMBED_KW: decoder row r reads kwp row r / kw_div (beam search: B * beam rows over B clips)
   const int* tok; long tok_stride; int t;  // EMBED
   const float* emb; const float* pe; float emb_scale;
   float* xout; long ldxo;            // where column-tile-0 blocks store the produced A rows (may be null)
@@ -667,13 +670,26 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
       for (int i = 0; i < NF; ++i)
         v[i] = (ok && i < nf) ? e4[sub + 16 * i] * p.emb_scale + p4[sub + 16 * i] : zero4;
     } else {
-      const f32x4* x4 = (const f32x4*)(p.X + (size_t)(ok ? r : 0) * p.ldx);
-      const f32x4* y4 = (const f32x4*)(p.Y2 + (size_t)(ok ? r : 0) * p.ldy2);
+      if (PRO == PRO_EMBED_KW) {
+        // the embedding with the clip's keyword row added, then normalised like a join; pe[t] is added after the norm
+        const int w = ok ? p.tok[(size_t)r * p.tok_stride + p.t] : 0;
+        const f32x4* e4 = (const f32x4*)(p.emb + (size_t)w * p.K);
+        const f32x4* k4 = (const f32x4*)(p.X + (size_t)(ok ? r / p.kw_div : 0) * p.ldx);
 #pragma unroll
-      for (int i = 0; i < NF; ++i) {
-        gw[i] = i < nf ? ((const f32x4*)p.ln_w)[sub + 16 * i] : zero4;
-        gb[i] = i < nf ? ((const f32x4*)p.ln_b)[sub + 16 * i] : zero4;
-        v[i] = (ok && i < nf) ? x4[sub + 16 * i] + y4[sub + 16 * i] : zero4;
+        for (int i = 0; i < NF; ++i) {
+          gw[i] = i < nf ? ((const f32x4*)p.ln_w)[sub + 16 * i] : zero4;
+          gb[i] = i < nf ? ((const f32x4*)p.ln_b)[sub + 16 * i] : zero4;
+          v[i] = (ok && i < nf) ? e4[sub + 16 * i] * p.emb_scale + k4[sub + 16 * i] : zero4;
+        }
+      } else {
+        const f32x4* x4 = (const f32x4*)(p.X + (size_t)(ok ? r : 0) * p.ldx);
+        const f32x4* y4 = (const f32x4*)(p.Y2 + (size_t)(ok ? r : 0) * p.ldy2);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+          gw[i] = i < nf ? ((const f32x4*)p.ln_w)[sub + 16 * i] : zero4;
+          gb[i] = i < nf ? ((const f32x4*)p.ln_b)[sub + 16 * i] : zero4;
+          v[i] = (ok && i < nf) ? x4[sub + 16 * i] + y4[sub + 16 * i] : zero4;
+        }
       }
       DEC_STAMP(1);
       float sm = 0.f;
@@ -690,6 +706,12 @@ __global__ __launch_bounds__(64 * DEC_WAVES) DEC_CAP void dec_gemm_kernel(DecGem
       const float rstd = rsqrtf(row16_sum(q) / (float)p.K + 1e-5f);
 #pragma unroll
       for (int i = 0; i < NF; ++i) v[i] = (v[i] - mean) * rstd * gw[i] + gb[i];
+      if (PRO == PRO_EMBED_KW) {
+        const f32x4* p4 = (const f32x4*)(p.pe + (size_t)p.t * p.K);
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+          if (i < nf) v[i] = v[i] + p4[sub + 16 * i];
+      }
     }
 #pragma unroll
     for (int i = 0; i < NF; ++i)
@@ -1284,7 +1306,7 @@ struct Route {
   int cls_ntb = 4, wide_cls_ntb = 2;       // column tiles per block of the classifier projection / of its wide twin
 };
 
-Route resolve_route(const ac_trm_weights* w, int R, int Tm, int t) {
+Route resolve_route(const ac_trm_weights* w, int R, int Tm, int t, bool keyword = false) {
   auto is = [](const char* v, const char* want) { return v && !strcmp(v, want); };
   Route rt;
   // AUDIOCAPTION_DEC_WIDE_MIN=n (default 0 = never): a step over n rows or more takes the wide route.  Opt-in, because it does
@@ -1295,13 +1317,14 @@ Route resolve_route(const ac_trm_weights* w, int R, int Tm, int t) {
   // (EXPERIMENTS.md, round 6).
   const char* e = getenv("AUDIOCAPTION_DEC_WIDE_MIN");
   const int wide_min = e ? atoi(e) : 0;
-  rt.wide = wide_min > 0 && R >= wide_min && wide_shape_ok(w) && w->d_model / w->nhead <= 64 && w->d_model % w->nhead == 0;
+  // (a keyword decoder stays on the general / rows routes: the wide kernels have no keyword producer)
+  rt.wide = !keyword && wide_min > 0 && R >= wide_min && wide_shape_ok(w) && w->d_model / w->nhead <= 64 && w->d_model % w->nhead == 0;
   // AUDIOCAPTION_DEC_HYBRID=1 (default off): from 512 rows on (a beam search over grouped batches) the QKV projection with the
   // residual join in its prologue and the classifier take their wide twins (csrc/decoder_wide.hip).  Stand-alone those are the
   // two launches of the narrow route furthest from their arithmetic (20 and 30 + 5 us at 768 rows against 11 and 27); inside the
   // EffB2-Trm pipeline the wide classifier's one-workgroup-per-CU blocks take 43 us beside the encoder and the step does not move
   // (20.41 vs 20.41 k clips/s, 30 s / beam 4: 7.70 vs 7.70 k): opt-in, kept for the record.
-  rt.hybrid = !rt.wide && is(getenv("AUDIOCAPTION_DEC_HYBRID"), "1") && R >= 512 && wide_shape_ok(w);
+  rt.hybrid = !keyword && !rt.wide && is(getenv("AUDIOCAPTION_DEC_HYBRID"), "1") && R >= 512 && wide_shape_ok(w);
   // the reference's decoder shape (d_model 256 = 4 heads of 64) takes the fused per-row sub-layer kernel: 4 launches per
   // layer instead of 8; any other shape the general 8-launch sequence
   // AUDIOCAPTION_DEC_ROW=gemm: the general 18-launch sequence (attn_step_kernel + dec_gemm_kernel) instead of the per-row
@@ -1402,6 +1425,19 @@ DecGemmParams produced_proj(DecGemmParams g, const Join& j, int d, float* xout, 
   return g;
 }
 
+// A produced_proj launch with no join pending, for a keyword decoder: the embedding's descriptor plus the keyword operands
+DecGemmParams keyword_embed(DecGemmParams p, const ac_trm_keyword* kw, int d) {
+  p.X = kw->kwp; p.ldx = d; p.ln_w = kw->ln_w; p.ln_b = kw->ln_b; p.kw_div = kw->row_div;
+  return p;
+}
+
+// Null or misaligned keyword operands (the producer reads them with 16-byte loads), or a row_div other than the search's
+int check_keyword(const ac_trm_keyword* kw, int row_div) {
+  if (!kw || !kw->kwp || !kw->ln_w || !kw->ln_b || kw->row_div != row_div) return AC_ERR_ARG;
+  if (((uintptr_t)kw->kwp | (uintptr_t)kw->ln_w | (uintptr_t)kw->ln_b) & 15) return AC_ERR_ARG;
+  return AC_OK;
+}
+
 // The wide twin of a produced_proj launch (csrc/decoder_wide.hip) over the same descriptor: producer 2 = the join, 1 = the
 // embedding.  ntb: 64-column groups per workgroup; split_out: Y leaves as a fragment pack
 int wide_produced(const DecGemmParams& p, int producer, int ntb, int split_out, hipStream_t s) {
@@ -1430,13 +1466,15 @@ RowParams row_params(const AttnParams& a, const Join& j, const float* WoT, const
 //   rows     self attention .. norm2 one row per workgroup in ONE launch (rows_split: one per attention); the feed forward
 //            reads the materialised x2: 4 launches per layer (5)
 //   hybrid   general or rows with the joined QKV projection (layer 1 on; the embedding one stays narrow) on its wide twin
+// kw (may be null): the keyword operands of a KeywordProbTransformerDecoder, checked by the caller (check_keyword) - the first
+// projection then embeds through PRO_EMBED_KW with kwp row r / row_div; nothing else of the step changes.
 int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
                  int max_len, int t, const int* tok, const unsigned char* mask, long tok_stride, float* cache,
-                 const Ws& ws, StepOut* fin, hipStream_t s, const Live& live) {
+                 const Ws& ws, StepOut* fin, hipStream_t s, const Live& live, const ac_trm_keyword* kw = nullptr) {
   if (t >= w->max_pos || !w->step_pk) return AC_ERR_ARG;
   const int d = w->d_model, ff = w->dim_ff;
   const float* pk = w->step_pk;
-  const Route rt = resolve_route(w, R, Tm, t);
+  const Route rt = resolve_route(w, R, Tm, t, kw != nullptr);
   const PackOffsets po = pack_layout(w);
   Step c{};
   c.w = w; c.ws = &ws; c.memkv = memkv; c.mem_len = mem_len; c.cache = cache; c.mask = mask;
@@ -1460,7 +1498,8 @@ int decoder_step(const ac_trm_weights* w, const float* memkv, const int* mem_len
     const DecGemmParams p = produced_proj(wide_twin && !rt.wide ? rows_only : g, j, d, xout, d, pk + wp, bias, Y,
                                           pack_out ? 0 : N, N, out & RELU);
     if (wide_twin) return wide_produced(p, j.x ? 2 : 1, 1, pack_out, s);
-    return j.x ? launch_dec_gemm<PRO_ADDLN>(p, s) : launch_dec_gemm<PRO_EMBED>(p, s);
+    if (j.x) return launch_dec_gemm<PRO_ADDLN>(p, s);
+    return kw ? launch_dec_gemm<PRO_EMBED_KW>(keyword_embed(p, kw, d), s) : launch_dec_gemm<PRO_EMBED>(p, s);
   };
   auto attention = [&](const AttnParams& a) {
     hipLaunchKernelGGL(attn_step_kernel, dim3(R, w->nhead), dim3(64), 0, s, a);
@@ -1618,7 +1657,8 @@ extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int m
 // segments returns before its first load (struct Live), and a last launch clears the columns of the steps not run.
 static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments, int Tm,
                       int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
-                      float* embed, int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream) {
+                      float* embed, int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream,
+                      const ac_trm_keyword* kw = nullptr) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !seq || !logit || !logprob || !embed || !unfinished_cnt || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || Tm <= 0 || Tm > MAX_KEYS || max_len <= 0 || max_len > w->max_pos) return AC_ERR_ARG;
@@ -1638,7 +1678,7 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
     StepOut fin;
     live.t = t;
     AC_TRY(decoder_step(w, memkv, mem_len, B, 1, Tm, max_len, t, ws.tok, ws.mask, max_len + 1, ws.cache[0], ws,
-                        &fin, s, live));
+                        &fin, s, live, kw));
     AC_TRY(classifier_step(w, fin, B, embed + (size_t)t * d, (long)max_len * d, logit + (size_t)t * V,
                            (long)max_len * V, s, live));
     if (sp) {
@@ -1690,9 +1730,9 @@ extern "C" int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const 
                     unfinished_cnt, ws_base, &sp, stream);
 }
 
-extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv, const int* mem_len, int N,
-                                     int Tm, const int* tokens, const unsigned char* key_mask, int T,
-                                     float* embed, float* logit, float* ws_base, void* stream) {
+static int forward_tokens(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int N,
+                          int Tm, const int* tokens, const unsigned char* key_mask, int T, float* embed, float* logit,
+                          float* ws_base, void* stream) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !tokens || !embed || !logit || !ws_base) return AC_ERR_ARG;
   if (N <= 0 || Tm <= 0 || Tm > MAX_KEYS || T <= 0 || T > w->max_pos) return AC_ERR_ARG;
@@ -1701,10 +1741,16 @@ extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv
   const int d = w->d_model, V = w->vocab;
   for (int t = 0; t < T; ++t) {
     StepOut fin;
-    AC_TRY(decoder_step(w, memkv, mem_len, N, 1, Tm, T, t, tokens, key_mask, T, ws.cache[0], ws, &fin, s, Live()));
+    AC_TRY(decoder_step(w, memkv, mem_len, N, 1, Tm, T, t, tokens, key_mask, T, ws.cache[0], ws, &fin, s, Live(), kw));
     AC_TRY(classifier_step(w, fin, N, embed + (size_t)t * d, (long)T * d, logit + (size_t)t * V, (long)T * V, s, Live()));
   }
   return AC_OK;
+}
+
+extern "C" int ac_trm_forward_tokens(const ac_trm_weights* w, const float* memkv, const int* mem_len, int N,
+                                     int Tm, const int* tokens, const unsigned char* key_mask, int T,
+                                     float* embed, float* logit, float* ws_base, void* stream) {
+  return forward_tokens(w, nullptr, memkv, mem_len, N, Tm, tokens, key_mask, T, embed, logit, ws_base, stream);
 }
 
 extern "C" int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div,
@@ -1724,10 +1770,9 @@ extern "C" int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, c
   return classifier_step(w, fin, R, embed, ld_embed, logit, ldl, s, Live(), ws.att);   // ws.att: dead once the last layer has consumed it
 }
 
-extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam,
-                                int Tm, int max_len, int t, float temp, const int* tokens,
-                                const unsigned char* key_mask, const float* cum_logprob, float* top_val,
-                                int* top_idx, float* ws_base, void* stream) {
+static int beam_step(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int B,
+                     int beam, int Tm, int max_len, int t, float temp, const int* tokens, const unsigned char* key_mask,
+                     const float* cum_logprob, float* top_val, int* top_idx, float* ws_base, void* stream) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !tokens || !cum_logprob || !top_val || !top_idx || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || beam <= 0 || beam > 64 || Tm <= 0 || Tm > MAX_KEYS || t < 0 || t >= max_len) return AC_ERR_ARG;
@@ -1737,7 +1782,7 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
   const Ws ws = carve(w, R, max_len, ws_base);
   StepOut fin;
   AC_TRY(decoder_step(w, memkv, mem_len, R, beam, Tm, max_len, t, tokens, key_mask, max_len + 1,
-                      ws.cache[t & 1], ws, &fin, s, Live()));
+                      ws.cache[t & 1], ws, &fin, s, Live(), kw));
   AC_TRY(classifier_step(w, fin, R, nullptr, 0, ws.lg, V, s, Live(), ws.att));   // ws.att: dead once the last layer has consumed it
   static const bool two_kernels = getenv("AUDIOCAPTION_BEAM_TOPK") && !strcmp(getenv("AUDIOCAPTION_BEAM_TOPK"), "scan");
   if (beam <= 8 && V <= 8192 && !two_kernels) {
@@ -1757,6 +1802,72 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
   hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(256), 0, s, lp, beam, t == 0 ? 1 : beam, V, top_val,
                      top_idx);
   return ac_check_launch();
+}
+
+extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam,
+                                int Tm, int max_len, int t, float temp, const int* tokens,
+                                const unsigned char* key_mask, const float* cum_logprob, float* top_val,
+                                int* top_idx, float* ws_base, void* stream) {
+  return beam_step(w, nullptr, memkv, mem_len, B, beam, Tm, max_len, t, temp, tokens, key_mask, cum_logprob, top_val, top_idx,
+                   ws_base, stream);
+}
+
+// ---- keyword-conditioned decoder (KeywordProbTransformerDecoder): the same searches with the keyword operands --------------
+extern "C" int ac_trm_kw_greedy_segments(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv,
+                                         const int* mem_len, int B, int segments, int Tm, int max_len, int start_idx,
+                                         int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob, float* embed,
+                                         int* unfinished_cnt, float* ws_base, void* stream) {
+  AC_TRY(check_keyword(kw, 1));
+  return trm_search(w, memkv, mem_len, B, segments, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, nullptr, stream, kw);
+}
+
+extern "C" int ac_trm_kw_sample(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len,
+                                int B, int Tm, int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq,
+                                float* logit, float* logprob, float* embed, int* unfinished_cnt, float* ws_base, int method,
+                                int k, float top_p, float temp, const uint64_t* seed_dev, void* stream) {
+  AC_TRY(check_keyword(kw, 1));
+  SampleParams sp = {};
+  sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
+  return trm_search(w, memkv, mem_len, B, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, &sp, stream, kw);
+}
+
+extern "C" int ac_trm_kw_forward_tokens(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv,
+                                        const int* mem_len, int N, int Tm, const int* tokens,
+                                        const unsigned char* key_mask, int T, float* embed, float* logit, float* ws_base,
+                                        void* stream) {
+  AC_TRY(check_keyword(kw, 1));
+  return forward_tokens(w, kw, memkv, mem_len, N, Tm, tokens, key_mask, T, embed, logit, ws_base, stream);
+}
+
+extern "C" int ac_trm_kw_beam_step(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len,
+                                   int B, int beam, int Tm, int max_len, int t, float temp, const int* tokens,
+                                   const unsigned char* key_mask, const float* cum_logprob, float* top_val, int* top_idx,
+                                   float* ws_base, void* stream) {
+  AC_TRY(check_keyword(kw, beam));
+  return beam_step(w, kw, memkv, mem_len, B, beam, Tm, max_len, t, temp, tokens, key_mask, cum_logprob, top_val, top_idx,
+                   ws_base, stream);
+}
+
+// The first launch of a keyword decoder's step alone: xout [R][d] = the produced embedding rows, qkv [R][3 d] = layer 0's
+// self-attention in-projection of them (what decoder_step writes to its workspace before anything overwrites it)
+extern "C" int ac_trm_kw_embed_qkv(const ac_trm_weights* w, const ac_trm_keyword* kw, int R, int row_div, int t,
+                                   const int* tokens, long tok_stride, float* xout, float* qkv, void* stream) {
+  AC_TRY(check_weights(w));
+  if (row_div <= 0) return AC_ERR_ARG;
+  AC_TRY(check_keyword(kw, row_div));
+  if (!tokens || !xout || !qkv || !w->step_pk || R <= 0 || R % row_div || t < 0 || t >= w->max_pos || tok_stride <= t)
+    return AC_ERR_ARG;
+  if (((uintptr_t)xout | (uintptr_t)qkv) & 15) return AC_ERR_ARG;
+  const int d = w->d_model;
+  DecGemmParams g{};
+  g.tok = tokens; g.tok_stride = tok_stride; g.t = t; g.emb = w->emb; g.pe = w->pe; g.emb_scale = sqrtf((float)d);
+  g.M = R; g.ntb = 1;
+  const ac_trm_layer& L = w->layer[0];
+  const DecGemmParams p = produced_proj(g, Join{}, d, xout, d, w->step_pk + pack_layout(w).layer[0].n.sa_in, L.sa_in_b, qkv,
+                                        3 * d, 3 * d, 0);
+  return launch_dec_gemm<PRO_EMBED_KW>(keyword_embed(p, kw, d), (hipStream_t)stream);
 }
 
 static int beam_update(const float* top_val, const int* top_idx, const int* tokens_in, int* tokens_out,

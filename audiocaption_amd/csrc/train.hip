@@ -650,6 +650,80 @@ __global__ __launch_bounds__(256) void dropadd_ln_bwd_kernel(const float* dy, co
   atomicAdd(dbeta + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
 }
 
+// ---- keyword-conditioned embedding (transformer_decoder.py:196-202 KeywordProbTransformerDecoder) -----------------
+// x[row] = dropB( LayerNorm( dropA(E[word[row]]) * sqrt(d) + kwp[clip[row]] ) * gamma + beta + pe[pos[row]] ), 256 columns,
+// one wave per row; the dropout sites and their element index (row * d + column) are embed_fwd_kernel's.  `pre` (the
+// LayerNorm's input) is kept for the backward, which recomputes mean and rstd from it like dropadd_ln_bwd_kernel.
+__global__ __launch_bounds__(256) void kw_embed_fwd_kernel(const float* emb, const float* pe, const int* word, const int* pos,
+                                                           const int* clip, const float* kwp, const float* gamma,
+                                                           const float* beta, float* pre, float* x, long row0, long rows,
+                                                           float sqrt_d, Drop da, Drop db, float eps) {
+  const int lane = threadIdx.x & 63;
+  const long r = row0 + blockIdx.x * 4L + (threadIdx.x >> 6);
+  if (r >= row0 + rows) return;
+  const f32x4 e = *(const f32x4*)(emb + (long)word[r] * DM + lane * 4);
+  const f32x4 kw = *(const f32x4*)(kwp + (long)clip[r] * DM + lane * 4);
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = e[j] * da.mask((uint64_t)r * DM + lane * 4 + j) * sqrt_d + kw[j];
+  *(f32x4*)(pre + r * DM + lane * 4) = v;
+  const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / DM);
+  const f32x4 c = v - mean;
+  const float var = wave_sum(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3]) * (1.0f / DM);
+  const float rstd = rsqrtf(var + eps);
+  const f32x4 g = *(const f32x4*)(gamma + lane * 4), b = *(const f32x4*)(beta + lane * 4);
+  const f32x4 p4 = *(const f32x4*)(pe + (long)pos[r] * DM + lane * 4);
+  f32x4 y = c * rstd * g + b + p4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) y[j] *= db.mask((uint64_t)r * DM + lane * 4 + j);
+  *(f32x4*)(x + r * DM + lane * 4) = y;
+}
+
+// dx -> through dropB and the LayerNorm to dpre; dgamma / dbeta with one atomic per column per block (LN_ROWS rows per
+// block, as dropadd_ln_bwd_kernel); dkwp[clip[row]] += dpre (the sum over the clip's rows; the caller zeroes dkwp);
+// demb[word[row]] += dpre * sqrt(d) * maskA (embed_bwd_kernel's scatter).
+__global__ __launch_bounds__(256) void kw_embed_bwd_kernel(const float* dx, const int* word, const int* clip, const float* pre,
+                                                           const float* gamma, float* dgamma, float* dbeta, float* dkwp,
+                                                           float* demb, long rows, float sqrt_d, Drop da, Drop db, float eps) {
+  __shared__ float sg[4][DM], sb[4][DM];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const f32x4 g = *(const f32x4*)(gamma + lane * 4);
+  f32x4 ag = {0.f, 0.f, 0.f, 0.f}, ab = {0.f, 0.f, 0.f, 0.f};
+  for (int i = wave; i < LN_ROWS; i += 4) {
+    const long r = blockIdx.x * (long)LN_ROWS + i;
+    if (r >= rows) break;
+    const f32x4 v = *(const f32x4*)(pre + r * DM + lane * 4);
+    f32x4 dyv = *(const f32x4*)(dx + r * DM + lane * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dyv[j] *= db.mask((uint64_t)r * DM + lane * 4 + j);
+    const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / DM);
+    const f32x4 c = v - mean;
+    const float var = wave_sum(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3]) * (1.0f / DM);
+    const float rstd = rsqrtf(var + eps);
+    const f32x4 xh = c * rstd;
+    const f32x4 dxh = dyv * g;
+    const float m1 = wave_sum(dxh[0] + dxh[1] + dxh[2] + dxh[3]) * (1.0f / DM);
+    const float m2 = wave_sum(dxh[0] * xh[0] + dxh[1] * xh[1] + dxh[2] * xh[2] + dxh[3] * xh[3]) * (1.0f / DM);
+    const f32x4 dp = (dxh - m1 - xh * m2) * rstd;
+    ag += dyv * xh;
+    ab += dyv;
+    float* kw_row = dkwp + (long)clip[r] * DM + lane * 4;
+    float* emb_row = demb + (long)word[r] * DM + lane * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      atomicAdd(kw_row + j, dp[j]);
+      const float ge = dp[j] * sqrt_d * da.mask((uint64_t)r * DM + lane * 4 + j);
+      if (ge != 0.f) atomicAdd(emb_row + j, ge);
+    }
+  }
+  *(f32x4*)(&sg[wave][lane * 4]) = ag;
+  *(f32x4*)(&sb[wave][lane * 4]) = ab;
+  __syncthreads();
+  const int c = threadIdx.x;
+  atomicAdd(dgamma + c, (sg[0][c] + sg[1][c]) + (sg[2][c] + sg[3][c]));
+  atomicAdd(dbeta + c, (sb[0][c] + sb[1][c]) + (sb[2][c] + sb[3][c]));
+}
+
 // =========================================================================================================
 // Multi-head attention over short sequences, one workgroup per (sequence, head); head_dim 64.
 // Sequence s has L[s] queries at rows qrow0[s].. and Tk keys at rows krow0[s]..;  self-attention: key j is
@@ -1538,6 +1612,31 @@ int ac_dropadd_ln_bwd(const float* dy, const float* pre, const float* gamma, flo
   if (!dy || !pre || !gamma || !dgamma || !dbeta || rows <= 0 || d != DM || relu_mod < 0) return AC_ERR_ARG;
   hipLaunchKernelGGL(dropadd_ln_bwd_kernel, dim3((rows + LN_ROWS - 1) / LN_ROWS), dim3(256), 0, (hipStream_t)stream, dy, pre,
                      gamma, dx, dres, accumulate, relu_src, relu_mod, dgamma, dbeta, rows, make_drop(p, seed, seed_dev), eps);
+  return ac_check_launch();
+}
+
+int ac_kw_embed_fwd(const float* emb, const float* pe, const int* word, const int* pos, const int* clip, const float* kwp,
+                    const float* gamma, const float* beta, float* pre, float* x, long row0, long rows, int d, float pa,
+                    unsigned long long seed_a, float pb, unsigned long long seed_b, const unsigned long long* seed_dev,
+                    float eps, void* stream) {
+  if (!emb || !pe || !word || !pos || !clip || !kwp || !gamma || !beta || !pre || !x || rows <= 0 || row0 < 0 || d != DM)
+    return AC_ERR_ARG;
+  if (((uintptr_t)emb | (uintptr_t)pe | (uintptr_t)kwp | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pre | (uintptr_t)x) & 15)
+    return AC_ERR_ARG;
+  hipLaunchKernelGGL(kw_embed_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, emb, pe, word, pos, clip,
+                     kwp, gamma, beta, pre, x, row0, rows, sqrtf((float)d), make_drop(pa, seed_a, seed_dev),
+                     make_drop(pb, seed_b, seed_dev), eps);
+  return ac_check_launch();
+}
+
+int ac_kw_embed_bwd(const float* dx, const int* word, const int* clip, const float* pre, const float* gamma, float* dgamma,
+                    float* dbeta, float* dkwp, float* demb, long rows, int d, float pa, unsigned long long seed_a, float pb,
+                    unsigned long long seed_b, const unsigned long long* seed_dev, float eps, void* stream) {
+  if (!dx || !word || !clip || !pre || !gamma || !dgamma || !dbeta || !dkwp || !demb || rows <= 0 || d != DM) return AC_ERR_ARG;
+  if (((uintptr_t)dx | (uintptr_t)pre | (uintptr_t)gamma) & 15) return AC_ERR_ARG;
+  hipLaunchKernelGGL(kw_embed_bwd_kernel, dim3((rows + LN_ROWS - 1) / LN_ROWS), dim3(256), 0, (hipStream_t)stream, dx, word,
+                     clip, pre, gamma, dgamma, dbeta, dkwp, demb, rows, sqrtf((float)d), make_drop(pa, seed_a, seed_dev),
+                     make_drop(pb, seed_b, seed_dev), eps);
   return ac_check_launch();
 }
 

@@ -34,7 +34,7 @@ import torch.nn as nn
 from . import _lib
 from . import kernels as K
 from ._lib import check, ptr, stream
-from .transformer_decoder import TransformerDecoder
+from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder
 from .transformer_model import CaptionModel, _device_flags
 
 
@@ -64,6 +64,9 @@ class EnsembleModel(nn.Module):
             if not isinstance(getattr(m, "decoder", None), TransformerDecoder):
                 raise NotImplementedError(f"EnsembleModel: the step kernels cover TransformerDecoder members only "
                                           f"(got {type(getattr(m, 'decoder', m)).__name__})")
+            if isinstance(m.decoder, KeywordProbTransformerDecoder):
+                raise NotImplementedError("EnsembleModel: keyword conditioning is not built for ensemble decoding (a "
+                                          "KeywordProbTransformerDecoder member needs its keyword batch at every step)")
         first = models[0]
         for m in models[1:]:
             if m.vocab_size != first.vocab_size:

@@ -55,6 +55,10 @@ class _EncoderKdWrapper(nn.Module, CaptionMetaMixin):
         if not use_tchr_proj:
             raise NotImplementedError(f"{type(self).__name__}: use_tchr_proj=False (the student's projection applied to "
                                       "attn_emb as well and fed to the decoder, kd_wrapper.py:91-96) is not built")
+        from .transformer_model import KeywordCondTransformerModel
+        if isinstance(model, KeywordCondTransformerModel):
+            raise NotImplementedError(f"{type(self).__name__}: encoder knowledge distillation is not built for "
+                                      "KeywordCondTransformerModel (keyword conditioning)")
         self.model = model
         self.use_tchr_proj = use_tchr_proj
         self.tchr_dim = tchr_dim

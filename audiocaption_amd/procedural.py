@@ -145,6 +145,29 @@ def decoder_state(prefix="", vocab_size=4368, d_model=256, attn_emb_dim=512, nla
     return out
 
 
+def keyword_decoder_state(prefix="", vocab_size=4368, keyword_classes_num=300, d_model=256, attn_emb_dim=512, nlayers=2,
+                          dim_ff=1024, seed=BASE_SEED):
+    """KeywordProbTransformerDecoder tensors (reference transformer_decoder.py:177-184): ``decoder_state`` plus
+    ``keyword_proj`` and ``word_keyword_norm``, in the reference's key order.  keyword_proj is drawn at O(1) per active
+    keyword, the order of the scaled token embedding, so that the keywords move the logits."""
+    out = decoder_state(prefix, vocab_size, d_model, attn_emb_dim, nlayers, dim_ff, seed)
+    k = prefix + "keyword_proj.weight"
+    out[k] = _normal(k, (d_model, keyword_classes_num), 1.0, seed)
+    out[prefix + "keyword_proj.bias"] = _uniform(prefix + "keyword_proj.bias", (d_model,), -0.1, 0.1, seed)
+    out[prefix + "word_keyword_norm.weight"] = _uniform(prefix + "word_keyword_norm.weight", (d_model,), 0.9, 1.1, seed)
+    out[prefix + "word_keyword_norm.bias"] = _uniform(prefix + "word_keyword_norm.bias", (d_model,), -0.1, 0.1, seed)
+    return out
+
+
+def cnn14rnn_keyword_trm_state(vocab_size=4368, keyword_classes_num=300, seed=BASE_SEED):
+    """Full state dict of ``config.cnn14rnn_keyword_trm_config``: the Cnn14Rnn-Trm captioner with the keyword decoder."""
+    out = {}
+    out.update(cnn14_state("encoder.cnn.", seed))
+    out.update(gru_state("encoder.rnn.", 2048, 256, 3, seed))
+    out.update(keyword_decoder_state("decoder.", vocab_size, keyword_classes_num, 256, 512, 2, 1024, seed))
+    return out
+
+
 # A second, HIGH-ENTROPY decoder draw for the decode fixtures g4b / g5b (tests/golden/make_golden.py): larger token
 # embeddings and positional encodings make the next token depend on the whole prefix (few repeated tokens, clips and beams
 # that differ), a larger <end> logit makes beams finish early while others continue (the -1000 path of base.py:317), and

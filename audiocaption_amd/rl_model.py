@@ -34,7 +34,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, ptr, stream
 from .cider import Cider
-from .transformer_model import CaptionMetaMixin, TransformerModel
+from .transformer_model import CaptionMetaMixin, KeywordCondTransformerModel, TransformerModel
 
 
 def compute_batch_score(decode_res, key2refs, keys, start_idx, end_idx, vocabulary, scorer):
@@ -111,6 +111,9 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
         if isinstance(model, ConditionalSeq2SeqAttnModel):
             raise NotImplementedError("ScstWrapper: self-critical training is not built for ConditionalSeq2SeqAttnModel (the "
                                       "condition-controlled decoders have no sampled rollout)")
+        if isinstance(model, KeywordCondTransformerModel):
+            raise NotImplementedError("ScstWrapper: self-critical training is not built for KeywordCondTransformerModel (the "
+                                      "keyword-conditioned decoder has no sampled rollout)")
         self._attn_gru = isinstance(model, Seq2SeqAttnModel) and isinstance(model.encoder, CrnnEncoder)
         if not (isinstance(model, TransformerModel) or self._attn_gru):
             over = f" over {model.encoder.__class__.__name__}" if isinstance(model, Seq2SeqAttnModel) else ""

@@ -35,6 +35,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .cnn_encoder import cnn14_feat_len
+from .transformer_decoder import KeywordProbTransformerDecoder, check_keyword
 
 # dropout site codes (low 16 bits of the seed; oracle/train_path.py restates them)
 OP_CNN_BLOCK = 1
@@ -312,6 +313,8 @@ class TrainEngine:
                 "TrainEngine: built for the reference's training recipe, CrnnEncoder or Cnn14TransformerEncoder with "
                 "freeze_cnn=True, freeze_cnn_bn=True (cnn14rnn_trm.yaml:9-13); the backward through the Cnn14 is not built")
         self.enc_width = self._check_widths(model)
+        # a KeywordProbTransformerDecoder: the keyword form of the embedding (ac_kw_embed_fwd / _bwd), autograd route only
+        self.keyword = isinstance(model.decoder, KeywordProbTransformerDecoder)
         self.model = model
         self.lib = _lib.load()
         self.flat = None
@@ -537,11 +540,13 @@ class TrainEngine:
         R = sum(N * L for L, _ in passes)
         S = len(passes) * N
         pos = torch.empty(R, dtype=torch.int32)
+        clip = torch.empty(R, dtype=torch.int32)      # the clip a row belongs to (keyword conditioning: its row of kwp)
         qrow0 = torch.empty(S, dtype=torch.int32)
         qlen = torch.empty(S, dtype=torch.int32)
         cls_rows = torch.empty(N * T, dtype=torch.int32)
         for t, (L, off) in enumerate(passes):
             pos[off:off + N * L] = torch.arange(L, dtype=torch.int32).repeat(N)
+            clip[off:off + N * L] = torch.arange(N, dtype=torch.int32).repeat_interleave(L)
             qrow0[t * N:(t + 1) * N] = off + torch.arange(N, dtype=torch.int32) * L
             qlen[t * N:(t + 1) * N] = L
             if teacher_forcing:
@@ -549,7 +554,7 @@ class TrainEngine:
             else:
                 cls_rows[t::T] = off + torch.arange(N, dtype=torch.int32) * L + t
         lay = {"passes": passes, "R": R, "S": S, "ones": torch.ones(max(T, 1), dtype=torch.int32, device=device)}
-        for k, v in (("pos", pos), ("qrow0", qrow0), ("qlen", qlen), ("cls_rows", cls_rows),
+        for k, v in (("pos", pos), ("clip", clip), ("qrow0", qrow0), ("qlen", qlen), ("cls_rows", cls_rows),
                      ("mrow0", torch.arange(S, dtype=torch.int32) * Tm), ("mklen", torch.full((S,), Tm, dtype=torch.int32))):
             lay[k] = v.to(device)
         return lay
@@ -598,6 +603,11 @@ class TrainEngine:
         Tm = Tq + 1 if trm else Tq      # decoder memory rows per clip (the Transformer encoder prepends cls_token)
         key = (dev, N, Tc, tuple(wav.shape) if hook is None else ("hook", Tq), teacher_forcing, p_dec, p_rnn, p_cnn,
                model.start_idx, model.pad_idx, specaug and hook is None)
+        keyword = None
+        if self.keyword:
+            # the keyword batch of a KeywordCondTransformerModel: checked on the host, staged like `cap`
+            keyword = check_keyword(input_dict.get("keyword"), N, dec.keyword_classes_num)
+            key += ("keyword", tuple(keyword.shape))
         if rollout:
             key += ("rollout",)     # the SCST rollout's states never collide with the cross-entropy step's of the same shape
         if evalm:
@@ -614,6 +624,7 @@ class TrainEngine:
                   "wav": torch.empty_like(wav, dtype=torch.float32) if hook is None else None,
                   "cnn_attn_in": torch.empty(N, Tq, 2048, device=dev) if hook is not None else None,
                   "cap": torch.empty(N, Tc, device=dev, dtype=torch.int64),
+                  "keyword": torch.empty(keyword.shape, device=dev, dtype=torch.float32) if keyword is not None else None,
                   "specaug": torch.zeros(N, 4, 2, device=dev, dtype=torch.int32) if (specaug and hook is None) else None,
                   "specaug_pinned": [],
                   # one pinned staging block -> one device block (int32 words):
@@ -667,6 +678,8 @@ class TrainEngine:
         else:
             st["cnn_attn_in"].copy_(hook, non_blocking=True)
         st["cap"].copy_(cap, non_blocking=True)
+        if keyword is not None:
+            st["keyword"].copy_(keyword, non_blocking=True)
         st["lens_host"] = mlens
         return st
 
@@ -720,6 +733,13 @@ class TrainEngine:
             self._lin(s, mem, fp.p(lp + "multihead_attn.in_proj_weight") + 4 * D * D,
                       fp.p(lp + "multihead_attn.in_proj_bias") + 4 * D, kvb, Rm, 2 * D, D)
             kv.append(kvb)
+
+        # ---- keyword conditioning: kwp = keyword_proj(keyword), once per batch -------------------------
+        if self.keyword:
+            C = dec.keyword_classes_num
+            st["kwp"], st["emb_pre"] = ws.f("kwp", N, D), ws.f("emb_pre", R, D)
+            self._gemm(s, st["keyword"].data_ptr(), C, 1, fp.p(dp + "keyword_proj.weight"), 1, C, st["kwp"], D, N, D, C,
+                       fp.p(dp + "keyword_proj.bias"))
 
         # ---- the passes ------------------------------------------------------------------------------
         word = ws.i("word", R)
@@ -897,8 +917,13 @@ class TrainEngine:
             L, off_t = passes[t]
             check(lib.ac_build_prefix(cap_p, Tc, c["seq"], T, ucap_ptr, 0 if teacher_forcing else t, model.start_idx, word,
                                       off_t, N, L, s), "ac_build_prefix")
-        check(lib.ac_embed_fwd(c["emb"], c["pe"], word, c["pos"], acts[0]["x_in"], off, nr, D, p_dec, OP_EMB_A, p_dec,
-                               OP_EMB_B, self._seed_ptr, s), "ac_embed_fwd")
+        if self.keyword:
+            check(lib.ac_kw_embed_fwd(c["emb"], c["pe"], word, c["pos"], lay["clip"].data_ptr(), st["kwp"],
+                                      *fp.wb(dp + "word_keyword_norm."), st["emb_pre"], acts[0]["x_in"], off, nr, D, p_dec,
+                                      OP_EMB_A, p_dec, OP_EMB_B, self._seed_ptr, 1e-5, s), "ac_kw_embed_fwd")
+        else:
+            check(lib.ac_embed_fwd(c["emb"], c["pe"], word, c["pos"], acts[0]["x_in"], off, nr, D, p_dec, OP_EMB_A, p_dec,
+                                   OP_EMB_B, self._seed_ptr, s), "ac_embed_fwd")
         qrow0, qlen, mrow0, mklen, mvalid = c["qrow0"], c["qlen"], c["mrow0"], c["mklen"], c["mvalid"]
         for l, a in enumerate(acts):
             lp = f"{dp}model.layers.{l}."
@@ -993,6 +1018,9 @@ class TrainEngine:
         Returns ``logit`` (N, T, V), ``seq`` (int64) and ``seq_i32`` (N, T), ``sampled_logprob`` (N, T), all on the device."""
         import math
         model = self.model
+        if self.keyword:
+            raise NotImplementedError("TrainEngine.rollout: the SCST rollout is not built for keyword conditioning "
+                                      "(KeywordCondTransformerModel)")
         T = int(input_dict.get("max_length", model.max_length))
         temp = float(input_dict.get("temp", 1.0))
         if T < 1:
@@ -1143,8 +1171,20 @@ class TrainEngine:
                 "ac_attn_seq_bwd", (a["P"], T, T), (qrow0, qlen, qrow0, qlen, 0, S, nh, 64, T, T, p_dec, op + 0), ()),
                 p_dec, op + 1, 1e-5)
         side.join()   # the embedding's gradient may be the classifier's (tied weights): no two writers at once
-        check(lib.ac_embed_bwd(dx, sv["word"], fp.g(dp + "word_embedding.weight"), R, D, p_dec, OP_EMB_A, p_dec, OP_EMB_B,
-                               self._seed_ptr, s), "ac_embed_bwd")
+        if self.keyword:
+            # through word_keyword_norm: its gradients, the embedding's scatter and dkwp (summed over each clip's rows), from
+            # which keyword_proj's gradients follow; `keyword` itself receives none
+            C = dec.keyword_classes_num
+            dkwp = ws.f("dkwp", N, D)
+            ws.tensor("dkwp")[:N * D].zero_()
+            w_ln, g_ln_w, g_ln_b = fp.wgb(dp + "word_keyword_norm.")
+            check(lib.ac_kw_embed_bwd(dx, sv["word"], lay["clip"].data_ptr(), sv["emb_pre"], w_ln, g_ln_w, g_ln_b, dkwp,
+                                      fp.g(dp + "word_embedding.weight"), R, D, p_dec, OP_EMB_A, p_dec, OP_EMB_B,
+                                      self._seed_ptr, 1e-5, s), "ac_kw_embed_bwd")
+            self._lin_bwd(s, side, dkwp, sv["keyword"].data_ptr(), *fp.wgb(dp + "keyword_proj."), N, D, C)
+        else:
+            check(lib.ac_embed_bwd(dx, sv["word"], fp.g(dp + "word_embedding.weight"), R, D, p_dec, OP_EMB_A, p_dec, OP_EMB_B,
+                                   self._seed_ptr, s), "ac_embed_bwd")
 
         # ---- audio memory -> attn_proj -> GRU output ---------------------------------------------------
         da_rep = ws.f("da_rep", Rm, D)
@@ -1349,6 +1389,10 @@ class TrainEngine:
         carries ``sup_loss`` and ``kd_loss`` beside ``loss`` (the total)."""
         import math
         from .optim import FusedAdam, clip_grad_norm_
+        if self.keyword:
+            raise NotImplementedError("TrainEngine.step: the fused step (device-side loss, clip, Adam, graph capture; also "
+                                      "with kd=) is not built for keyword conditioning (KeywordCondTransformerModel); train "
+                                      "through model(input_dict) with mode='train' and a torch optimizer")
         if "cap_len" not in input_dict:
             raise KeyError("cap_len")
         if not self.model.training:

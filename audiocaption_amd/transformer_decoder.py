@@ -250,13 +250,33 @@ class TransformerDecoder(BaseDecoder):
               "ac_trm_forward_tokens")
         return {"embed": embed, "logit": logit}
 
+    # ---- what a conditioned decoder adds to a search (KeywordProbTransformerDecoder overrides these four) -------------------
+    def _extra_key(self, extra):
+        """The part of a search state's cache key that names the extra per-clip inputs (none here)."""
+        if extra is not None:
+            raise TypeError(f"{self.__class__.__name__} takes no conditioning input")
+        return ()
+
+    def _extra_buffers(self, dev, B, row_div=1):
+        """Static buffers of those inputs inside a search state over B clips (``row_div`` decoder rows per clip)."""
+        return {}
+
+    def _stage_extra(self, st, extra):
+        """Copy the inputs of this call into the state's static buffers (before a launch or a replay)."""
+
+    def _memory_launch(self, st):
+        """The once-per-batch part of a search's launch sequence over its static buffers, on the current stream (capturable):
+        the audio memory and the cross-attention K / V of every layer."""
+        B, Tm, _ = st["attn_emb"].shape
+        check(_lib.load().ac_trm_memory(ctypes.byref(self.weights()), ptr(st["attn_emb"]), B, Tm, ptr(st["memkv"]),
+                                        ptr(st["tmp"]), stream()), "ac_trm_memory")
+
     def _greedy_launch(self, st, max_length, start_idx, end_idx, pad_idx):
         """Memory preparation + the whole on-device greedy loop on the current stream (capturable)."""
         lib = _lib.load()
         B, Tm, _ = st["attn_emb"].shape
         w = ctypes.byref(self.weights())
-        check(lib.ac_trm_memory(w, ptr(st["attn_emb"]), B, Tm, ptr(st["memkv"]), ptr(st["tmp"]), stream()),
-              "ac_trm_memory")
+        self._memory_launch(st)
         if st.get("cluster_ws") is not None:
             check(lib.ac_trm_greedy_cluster(w, ptr(st["cluster_pk"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length,
                                             start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]),
@@ -274,6 +294,7 @@ class TransformerDecoder(BaseDecoder):
         f32 = dict(device=dev, dtype=torch.float32)
         ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), B, max_length)
         return {
+            **self._extra_buffers(dev, B),
             "key": key, "graph": None, "uses": 0, "segments": segments,
             "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
             "memkv": torch.empty(self.nlayers, B * Tm, 2 * self.d_model, **f32),
@@ -286,7 +307,7 @@ class TransformerDecoder(BaseDecoder):
                                           dtype=torch.int32),
         }
 
-    def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None):
+    def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None, extra=None):
         """On-device greedy search.  Returns device tensors seq (int64), logit, logprob, embed, cnt.  ``attn_emb`` /
         ``attn_emb_len``: one batch, or lists of batches of the same (frames, width) decoded as one chain.  Batches of one
         row count are the chain's segments: each stops when ITS rows have all emitted <end>, as the reference's loop over
@@ -327,7 +348,8 @@ class TransformerDecoder(BaseDecoder):
         # AUDIOCAPTION_CLUSTER_EARLY_STOP=0: the one-launch form runs all max_length steps like the launch chain (benchmarks that
         # compare the two at equal work; the outputs are the same either way)
         early = os.environ.get("AUDIOCAPTION_CLUSTER_EARLY_STOP", "1") != "0"
-        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, cluster, early, self._weights_key(), segments)
+        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, cluster, early, self._weights_key(), segments) + \
+            self._extra_key(extra)
         if self._greedy_state is None:
             self._greedy_state = {}
         states = self._greedy_state
@@ -350,6 +372,7 @@ class TransformerDecoder(BaseDecoder):
         if isinstance(attn_emb_len, (list, tuple)):
             attn_emb_len = torch.cat([torch.as_tensor(l_).cpu().reshape(-1) for l_ in attn_emb_len])   # host side
         st["mem_len"].copy_(K.upload(attn_emb_len, dev, torch.int32))
+        self._stage_extra(st, extra)
         if not use_graph or st["uses"] < 2:
             # first batch of this shape: plain launches (also the warm-up a capture needs); a shape that never comes
             # back is never captured
@@ -373,14 +396,13 @@ class TransformerDecoder(BaseDecoder):
         B, Tm, _ = st["attn_emb"].shape
         w = ctypes.byref(self.weights())
         method, k, top_p, temp = params
-        check(lib.ac_trm_memory(w, ptr(st["attn_emb"]), B, Tm, ptr(st["memkv"]), ptr(st["tmp"]), stream()),
-              "ac_trm_memory")
+        self._memory_launch(st)
         check(lib.ac_trm_sample(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx, pad_idx,
                                 ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
                                 ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp),
                                 ptr(st["seed"]), stream()), "ac_trm_sample")
 
-    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed):
+    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed, extra=None):
         """On-device sampled search (base.py:152-170 with a sampling ``sample_method``; csrc/sample.hip).  ``method``, ``k``,
         ``top_p``, ``temp``: ``sampling.parse_sample_method``; ``seed``: 64-bit Philox key - row b of step t draws from
         counter (t, b), so a caption depends on (seed, row, step) only.  Returns what ``greedy`` returns.
@@ -394,7 +416,7 @@ class TransformerDecoder(BaseDecoder):
         B, Tm, A = attn_emb.shape
         use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
         params = (int(method), int(k), float(top_p), float(temp))
-        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key())
+        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key()) + self._extra_key(extra)
         if getattr(self, "_sample_state", None) is None:
             self._sample_state = {}
         states = self._sample_state
@@ -409,6 +431,7 @@ class TransformerDecoder(BaseDecoder):
         st["attn_emb"].copy_(attn_emb)
         st["mem_len"].copy_(K.upload(attn_emb_len, dev, torch.int32))
         st["seed"].fill_(seed_word(seed))
+        self._stage_extra(st, extra)
         if not use_graph or st["uses"] < 2:
             self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params)
         else:
@@ -431,7 +454,180 @@ class TransformerDecoder(BaseDecoder):
                                    ptr(ws), stream()), "ac_trm_beam_step")
         return top_val, top_idx
 
+    def _beam_step_launch(self, st, B, beam, Tm, max_length, t, temp, tokens):
+        """Step t of a beam search over the static buffers of its state (``TransformerModel._beam_begin``; capturable)."""
+        check(_lib.load().ac_trm_beam_step(ctypes.byref(self.weights()), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm,
+                                           max_length, t, float(temp), ptr(tokens), ptr(st["mask"]), ptr(st["cum"]),
+                                           ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]), stream()), "ac_trm_beam_step")
+
     def beam_reorder(self, R, max_length, t, src_row, ws):
         lib = _lib.load()
         check(lib.ac_trm_beam_reorder(ctypes.byref(self.weights()), R, max_length, t, ptr(src_row), ptr(ws),
                                       stream()), "ac_trm_beam_reorder")
+
+
+def check_keyword(keyword, rows, classes):
+    """``input_dict["keyword"]`` of a keyword-conditioned captioner: (rows, classes) multi-hot or probabilities, a CPU or
+    device tensor (or array) of any float dtype.  KeyError when it is missing, ValueError for another shape - both before
+    anything is launched.  Returns it as a float32 tensor (device unchanged)."""
+    if keyword is None:
+        raise KeyError("keyword: a KeywordProbTransformerDecoder needs input_dict['keyword'] of shape "
+                       f"(batch, {classes})")
+    keyword = torch.as_tensor(keyword)
+    if keyword.dim() != 2 or keyword.shape[0] != rows or keyword.shape[1] != classes:
+        raise ValueError(f"keyword must be ({rows}, {classes}) = (batch, keyword_classes_num), got {tuple(keyword.shape)}")
+    if keyword.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f"keyword must be a float tensor (multi-hot or probabilities), got {keyword.dtype}")
+    return keyword.detach().to(torch.float32)
+
+
+class KeywordProbTransformerDecoder(TransformerDecoder):
+    """The reference's ``KeywordProbTransformerDecoder`` (transformer_decoder.py:177-214): a ``TransformerDecoder`` whose
+    input rows are ``word_keyword_norm(embedding * sqrt(d) + keyword_proj(keyword)) + pe`` - a per-clip keyword vector
+    (multi-hot or probabilities over ``keyword_classes_num`` classes) steers every decoding position.  Same constructor,
+    parameters in the reference's order (``keyword_proj``, ``word_keyword_norm`` are created after the base class has run
+    its xavier initialisation, so they keep torch's default initialisation as in the reference).
+
+    ``keyword_proj(keyword)`` runs once per batch (``ac_gemm``, inside the captured launch sequence, right after the audio
+    memory); the decode step embeds through the PRO_EMBED_KW producer of csrc/decoder.hip.  Always the launch chain on the
+    general / per-row routes: the one-launch cluster search and the wide routes are not built for it."""
+
+    def __init__(self, emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, keyword_classes_num, **kwargs):
+        super().__init__(emb_dim, vocab_size, fc_emb_dim, attn_emb_dim, dropout, **kwargs)
+        self.keyword_classes_num = int(keyword_classes_num)
+        self.keyword_proj = nn.Linear(self.keyword_classes_num, self.d_model)
+        self.word_keyword_norm = nn.LayerNorm(self.d_model)
+        self._kw_keep = self._kw_key = None
+
+    def check_supported(self):
+        super().check_supported()
+        if self.keyword_classes_num < 1:
+            raise _lib.HipLibraryError(f"KeywordProbTransformerDecoder (HIP path): keyword_classes_num "
+                                       f"{self.keyword_classes_num} is below 1")
+
+    def cluster_covers(self, rows, Tm, max_length, device=None):
+        return False      # csrc/decoder_cluster.hip embeds without keywords
+
+    def _keyword_weights(self):
+        """(keyword_proj.weight, keyword_proj.bias, word_keyword_norm.weight, word_keyword_norm.bias) as contiguous f32
+        device tensors on 16-byte boundaries (the producer reads the norm with 16-byte loads), cached with ``weights()``."""
+        self.weights()
+        if self._kw_key != self._w_key:
+            def P(t):
+                t = f32c(t.detach())
+                return t if t.data_ptr() % 16 == 0 else t.clone()
+            self._kw_keep = tuple(P(t) for t in (self.keyword_proj.weight, self.keyword_proj.bias,
+                                                 self.word_keyword_norm.weight, self.word_keyword_norm.bias))
+            self._kw_key = self._w_key
+        return self._kw_keep
+
+    # ---- the keyword batch inside a search state --------------------------------------------------------------------------
+    def _extra_key(self, extra):
+        if extra is None:
+            raise KeyError("keyword: a KeywordProbTransformerDecoder needs the keyword batch")
+        return ("keyword", tuple(extra.shape))
+
+    def _extra_buffers(self, dev, B, row_div=1):
+        f32 = dict(device=dev, dtype=torch.float32)
+        _, _, ln_w, ln_b = self._keyword_weights()
+        kwp = torch.empty(B, self.d_model, **f32)
+        kw = _lib.AcTrmKeyword(kwp.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), int(row_div))
+        return {"keyword": torch.empty(B, self.keyword_classes_num, **f32), "kwp": kwp, "kw": kw, "kw_hold": (ln_w, ln_b)}
+
+    def _stage_extra(self, st, extra):
+        st["keyword"].copy_(check_keyword(extra, *st["keyword"].shape))
+
+    def _keyword_proj_launch(self, keyword, kwp):
+        """kwp (B, d) = keyword (B, classes) keyword_proj.weight^T + bias on the current stream (any class count)."""
+        W, b, _, _ = self._keyword_weights()
+        B, C = keyword.shape
+        check(_lib.load().ac_gemm(ptr(keyword), C, 1, ptr(W), 1, C, ptr(kwp), self.d_model, B, self.d_model, C, ptr(b), 0, 0.0,
+                                  1, 0.0, 0, None, 0, None, 0, stream()), "ac_gemm(keyword_proj)")
+
+    def _memory_launch(self, st):
+        super()._memory_launch(st)
+        self._keyword_proj_launch(st["keyword"], st["kwp"])
+
+    def _greedy_launch(self, st, max_length, start_idx, end_idx, pad_idx):
+        B, Tm, _ = st["attn_emb"].shape
+        self._memory_launch(st)
+        check(_lib.load().ac_trm_kw_greedy_segments(
+            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm,
+            max_length, start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
+            ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()), "ac_trm_kw_greedy_segments")
+
+    def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params):
+        B, Tm, _ = st["attn_emb"].shape
+        method, k, top_p, temp = params
+        self._memory_launch(st)
+        check(_lib.load().ac_trm_kw_sample(
+            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length,
+            start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
+            ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st["seed"]),
+            stream()), "ac_trm_kw_sample")
+
+    def _beam_step_launch(self, st, B, beam, Tm, max_length, t, temp, tokens):
+        check(_lib.load().ac_trm_kw_beam_step(
+            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length,
+            t, float(temp), ptr(tokens), ptr(st["mask"]), ptr(st["cum"]), ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]),
+            stream()), "ac_trm_kw_beam_step")
+
+    def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, keyword=None, alone=False, mode=None):
+        """``TransformerDecoder.greedy`` with the keyword batch (B, keyword_classes_num); one batch per call.  ``mode``
+        "cluster" (or AUDIOCAPTION_GREEDY=cluster) raises HipLibraryError: the one-launch search has no keyword producer."""
+        if isinstance(attn_emb, (list, tuple)):
+            raise NotImplementedError("KeywordProbTransformerDecoder: one batch per greedy chain (shared chains are not built "
+                                      "for keyword conditioning)")
+        keyword = check_keyword(keyword, attn_emb.shape[0], self.keyword_classes_num)
+        return super().greedy(attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=alone, mode=mode,
+                              extra=keyword)
+
+    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed,
+               keyword=None):
+        keyword = check_keyword(keyword, attn_emb.shape[0], self.keyword_classes_num)
+        return super().sample(attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed,
+                              extra=keyword)
+
+    def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws, kwp=None):
+        """``TransformerDecoder.beam_step`` with ``kwp`` (B, d) = ``keyword_proj`` of the clips' keywords."""
+        if kwp is None:
+            raise KeyError("keyword: KeywordProbTransformerDecoder.beam_step needs kwp, the projected keyword batch")
+        dev = memkv.device
+        _, _, ln_w, ln_b = self._keyword_weights()
+        kw = _lib.AcTrmKeyword(kwp.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), int(beam))
+        top_val = torch.empty(B, beam, device=dev, dtype=torch.float32)
+        top_idx = torch.empty(B, beam, device=dev, dtype=torch.int32)
+        check(_lib.load().ac_trm_kw_beam_step(ctypes.byref(self.weights()), ctypes.byref(kw), ptr(memkv), ptr(mem_len), B, beam,
+                                              Tm, max_length, t, float(temp), ptr(tokens), ptr(mask), ptr(cum), ptr(top_val),
+                                              ptr(top_idx), ptr(ws), stream()), "ac_trm_kw_beam_step")
+        return top_val, top_idx
+
+    def forward(self, input_dict):
+        """The eval-mode full-sequence call: {"word", "attn_emb", "attn_emb_len", "cap_padding_mask", "keyword"} ->
+        {"embed", "logit"} (transformer_decoder.py:186-214)."""
+        if self.training:
+            raise NotImplementedError(
+                "KeywordProbTransformerDecoder (HIP path): in train mode the decoder only runs inside the whole-model training "
+                "step (KeywordCondTransformerModel.forward with mode='train')")
+        lib = _lib.load()
+        self.weights()       # first: an unsupported shape is refused before any buffer exists
+        attn_emb = input_dict["attn_emb"]
+        dev = attn_emb.device
+        word = input_dict["word"].to(dev)
+        N, T = word.shape
+        keyword = check_keyword(input_dict.get("keyword"), N, self.keyword_classes_num).to(dev).contiguous()
+        Tm = attn_emb.shape[1]
+        mem_len = K.upload(input_dict["attn_emb_len"], dev, torch.int32)
+        mask = input_dict.get("cap_padding_mask")
+        mask_u8 = None if mask is None else mask.to(dev).to(torch.uint8).contiguous()
+        memkv = self.memory(attn_emb)
+        st = self._extra_buffers(dev, N)
+        self._keyword_proj_launch(keyword, st["kwp"])
+        tokens = word.to(torch.int32).contiguous()
+        embed = torch.empty(N, T, self.d_model, device=dev, dtype=torch.float32)
+        logit = torch.empty(N, T, self.vocab_size, device=dev, dtype=torch.float32)
+        ws = self.workspace(N, T, dev)
+        check(lib.ac_trm_kw_forward_tokens(ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(memkv), ptr(mem_len), N,
+                                           Tm, ptr(tokens), ptr(mask_u8), T, ptr(embed), ptr(logit), ptr(ws), stream()),
+              "ac_trm_kw_forward_tokens")
+        return {"embed": embed, "logit": logit}

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import _lib
 from . import kernels as K
 from ._lib import check, ptr, stream
-from .transformer_decoder import TransformerDecoder
+from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder, check_keyword
 
 
 class CaptionMetaMixin:
@@ -125,7 +125,7 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
         forward_dict = {"mode": "inference"}
         default_args = {"sample_method": "greedy", "max_length": self.max_length, "temp": 1.0}
         for key in self.inference_forward_keys:
-            forward_dict[key] = input_dict.get(key, default_args[key])
+            forward_dict[key] = input_dict[key] if key in input_dict else default_args[key]
         if forward_dict["sample_method"] == "beam":
             forward_dict["beam_size"] = input_dict.get("beam_size", 3)
             forward_dict["n_best"] = input_dict.get("n_best", False)
@@ -251,6 +251,12 @@ class TransformerModel(CaptionModel):
 
     def __init__(self, encoder, decoder, **kwargs):
         super().__init__(encoder, decoder, **kwargs)
+        # a keyword decoder IS a TransformerDecoder by inheritance, but only the model that feeds it `keyword` may hold it
+        names = [c.__name__ for c in self.compatible_decoders]
+        assert (not isinstance(decoder, KeywordProbTransformerDecoder)
+                or any(issubclass(c, KeywordProbTransformerDecoder) for c in self.compatible_decoders)), \
+            f"{decoder.__class__.__name__} is incompatible with {self.__class__.__name__}, " \
+            f"please use decoder in {names} "
         self._streams = None
         self._pinned = {}
         self._held = None   # forward_async: submitted batches whose decode waits for partner batches (a list)
@@ -535,6 +541,14 @@ class TransformerModel(CaptionModel):
                           (lambda pool=pool, a=host_seq, b=host_lp, c=host_flag, d=host_cnt: pool.append((a, b, c, d))), host_flag,
                           host_cnt if shared else None)
 
+    def _decoder_extra(self, input_dict):
+        """The per-clip conditioning input a search hands to the decoder beside the audio memory (none here)."""
+        return None
+
+    def _search_kwargs(self, input_dict):
+        """Keyword arguments of ``decoder.greedy`` / ``decoder.sample`` that carry that input."""
+        return {}
+
     # ---- greedy (base.py:152-218) -----------------------------------------------------------------
     def greedy_search(self, input_dict):
         if input_dict.get("temp", 1.0) != 1.0:
@@ -542,12 +556,13 @@ class TransformerModel(CaptionModel):
         args = (input_dict["attn_emb"], input_dict["attn_emb_len"], int(input_dict["max_length"]), self.start_idx, self.end_idx,
                 self.pad_idx)
         # the blocking call: nothing else runs on the GPU while this batch decodes -> the one-launch form where it applies
-        res = self.decoder.greedy(*args, alone=True)
+        kw = self._search_kwargs(input_dict)
+        res = self.decoder.greedy(*args, alone=True, **kw)
         if "cluster_error" in res and int(res["cluster_error"].item() & 0xffffffff) != 0:
             import warnings
             warnings.warn("one-launch greedy search: a workgroup's partners never started (another process on the GPU?); "
                           "decoding this batch with the launch chain")
-            res = self.decoder.greedy(*args, mode="chain")
+            res = self.decoder.greedy(*args, mode="chain", **kw)
         out = {
             "seq": res["seq"].cpu(),                          # the reference keeps seq on the CPU (base.py:122)
             "logit": res["logit"],
@@ -572,7 +587,8 @@ class TransformerModel(CaptionModel):
         seed = input_dict.get("seed")
         seed = draw_seed() if seed is None else int(seed)
         res = self.decoder.sample(input_dict["attn_emb"], input_dict["attn_emb_len"], int(input_dict["max_length"]),
-                                  self.start_idx, self.end_idx, self.pad_idx, method, k, top_p, temp, seed)
+                                  self.start_idx, self.end_idx, self.pad_idx, method, k, top_p, temp, seed,
+                                  **self._search_kwargs(input_dict))
         return {
             "seq": res["seq"].cpu(),                          # CPU as in base.py:122
             "logit": res["logit"],
@@ -615,7 +631,9 @@ class TransformerModel(CaptionModel):
         ld = max_length + 1
         cap = beam * max_length                    # upper bound of finished beams per clip
         use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
-        key = (dev, B, Tm, A, beam, max_length, temp, self.start_idx, self.end_idx, self.pad_idx, dec._weights_key(), slot)
+        extra = self._decoder_extra(input_dict)    # a conditioned decoder's per-clip inputs (None for the plain one)
+        key = (dev, B, Tm, A, beam, max_length, temp, self.start_idx, self.end_idx, self.pad_idx, dec._weights_key(), slot) + \
+            dec._extra_key(extra)
         if getattr(self, "_beam_state", None) is None:
             self._beam_state = {}
         states = self._beam_state
@@ -629,7 +647,7 @@ class TransformerModel(CaptionModel):
             if self.start_idx == self.pad_idx or self.end_idx == self.pad_idx:
                 mask0 = (tok0 == self.pad_idx).to(torch.uint8)
             ws_n = lib.ac_trm_workspace_floats(ctypes.byref(dec.weights()), R, max_length)
-            st = {"uses": 0, "graphs": {},
+            st = {**dec._extra_buffers(dev, B, beam), "uses": 0, "graphs": {},
                   "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, **i32),
                   "memkv": torch.empty(dec.nlayers, B * Tm, 2 * dec.d_model, **f32),
                   "tmp": torch.empty(B * Tm, dec.d_model, **f32), "ws": torch.empty(ws_n, **f32),
@@ -646,6 +664,7 @@ class TransformerModel(CaptionModel):
         st["uses"] += 1
         st["attn_emb"].copy_(K.f32c(attn_emb))
         st["mem_len"].copy_(K.upload(input_dict["attn_emb_len"], dev, torch.int32))
+        dec._stage_extra(st, extra)
         tok, mask, cum, active = st["tok"], st["mask"], st["cum"], st["active"]
         done_cnt, done_seq, done_score = st["done_cnt"], st["done_seq"], st["done_score"]
         src_row, n_active, ws = st["src_row"], st["n_active"], st["ws"]
@@ -661,12 +680,9 @@ class TransformerModel(CaptionModel):
                 active.fill_(1)
                 done_cnt.zero_()
                 n_active.fill_(B)
-                check(lib.ac_trm_memory(w, ptr(st["attn_emb"]), B, Tm, ptr(st["memkv"]), ptr(st["tmp"]), stream()),
-                      "ac_trm_memory")
+                dec._memory_launch(st)
             for t in range(t0, t1):
-                check(lib.ac_trm_beam_step(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length, t, float(temp),
-                                           ptr(tok[t & 1]), ptr(mask), ptr(cum), ptr(st["top_val"]), ptr(st["top_idx"]),
-                                           ptr(ws), stream()), "ac_trm_beam_step")
+                dec._beam_step_launch(st, B, beam, Tm, max_length, t, temp, tok[t & 1])
                 check(lib.ac_trm_beam_update(ptr(st["top_val"]), ptr(st["top_idx"]), ptr(tok[t & 1]), ptr(tok[(t + 1) & 1]),
                                              ptr(mask), ptr(cum), ptr(active), ptr(done_cnt), ptr(done_seq),
                                              ptr(done_score), ptr(src_row), ptr(n_active), B, beam, V, max_length, t,
@@ -738,3 +754,38 @@ class TransformerModel(CaptionModel):
             "sampled_logprob": torch.zeros(B, max_length),
             "embed": torch.empty(B, max_length, dec.d_model, device=dev),
         }
+
+
+class KeywordCondTransformerModel(TransformerModel):
+    """The reference's ``KeywordCondTransformerModel`` (transformer_model.py:223-264) over a
+    ``KeywordProbTransformerDecoder``: ``input_dict["keyword"]`` - (batch, keyword_classes_num), multi-hot or probabilities, a
+    CPU or device tensor of any float dtype - conditions every decoding step and the training forward.  A missing keyword
+    is a KeyError, another shape a ValueError, both before anything is launched.
+
+    Inference through the blocking ``model(input_dict)``: greedy, beam (with ``n_best`` / ``n_best_size``) and every sampling
+    method of ``sampling.parse_sample_method``; ``mode="train"`` through ``train.train_forward`` (the autograd bridge).
+    Not built (NotImplementedError): ``forward_async``, membership in an ``EnsembleModel``, ``ScstWrapper`` /
+    ``TrainEngine.rollout``, the fused ``TrainEngine.step`` (also with ``kd=``), the encoder-KD wrappers, and ``dbs``."""
+
+    compatible_decoders = (KeywordProbTransformerDecoder,)
+
+    def __init__(self, encoder, decoder, **kwargs):
+        super().__init__(encoder, decoder, **kwargs)
+        self.train_forward_keys += ["keyword"]
+        self.inference_forward_keys += ["keyword"]
+
+    def forward(self, input_dict):
+        # refused on the host, before the encoder runs: the launches of a request do not depend on whether the key is there
+        rows = len(input_dict["wav"]) if "wav" in input_dict else input_dict["attn_emb"].shape[0]
+        check_keyword(input_dict.get("keyword"), rows, self.decoder.keyword_classes_num)
+        return super().forward(input_dict)
+
+    def forward_async(self, input_dict, pair=None):
+        raise NotImplementedError("KeywordCondTransformerModel: forward_async (shared greedy chains, deferred beam searches) is "
+                                  "not built for keyword conditioning; use model(input_dict)")
+
+    def _decoder_extra(self, input_dict):
+        return check_keyword(input_dict.get("keyword"), input_dict["attn_emb"].shape[0], self.decoder.keyword_classes_num)
+
+    def _search_kwargs(self, input_dict):
+        return {"keyword": self._decoder_extra(input_dict)}

@@ -427,6 +427,41 @@ int ac_trm_beam_update_all(const float* top_val, const int* top_idx, const int* 
                            float* done_score, int* src_row, int* n_active, int B, int beam, int V, int max_len, int t,
                            int end_idx, int pad_idx, int done_capacity, void* stream);
 
+/* ---- keyword-conditioned decoder (transformer_decoder.py:177-214 KeywordProbTransformerDecoder) -------------
+ * A decoder input row becomes LayerNorm(emb[tok] * sqrt(d) + kwp[clip]) * ln_w + ln_b + pe[t] (eps 1e-5) instead of
+ * emb[tok] * sqrt(d) + pe[t]; everything after it is the plain decoder's.  kwp [clips][d_model] = keyword_proj(keyword), which
+ * the caller computes once per batch (ac_gemm, any keyword width); ln_w / ln_b = word_keyword_norm.  row_div: decoder row r
+ * reads kwp row r / row_div - 1 for the greedy, sampled and teacher-forced calls, `beam` for ac_trm_kw_beam_step.  The three
+ * pointers are device pointers, 16-byte aligned.  The operands travel as arguments of the launches: stream-ordered, and a
+ * captured graph keeps the addresses it was captured with.
+ * ac_trm_kw_greedy_segments / _sample / _forward_tokens / _beam_step: their namesakes without `kw_` (same arguments after `kw`,
+ * same outputs), always on the launch chain's general / per-row routes.  AC_ERR_ARG before any launch: kw or one of its
+ * pointers NULL or misaligned, row_div not the call's.
+ * ac_trm_kw_embed_qkv: the first launch of such a step alone, R rows at position t of tokens [R][tok_stride] -
+ * xout [R][d_model] the rows as above, qkv [R][3 * d_model] layer 0's self-attention in-projection of them (16-byte aligned). */
+typedef struct {
+  const float* kwp;
+  const float* ln_w;
+  const float* ln_b;
+  int32_t row_div;
+} ac_trm_keyword;
+int ac_trm_kw_greedy_segments(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len,
+                              int B, int segments, int Tm, int max_len, int start_idx, int end_idx, int pad_idx,
+                              int64_t* seq, float* logit, float* logprob, float* embed, int* unfinished_cnt, float* ws,
+                              void* stream);
+int ac_trm_kw_sample(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int B, int Tm,
+                     int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                     float* embed, int* unfinished_cnt, float* ws, int method, int k, float top_p, float temp,
+                     const uint64_t* seed_dev, void* stream);
+int ac_trm_kw_forward_tokens(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int N,
+                             int Tm, const int* tokens, const unsigned char* key_mask, int T, float* embed, float* logit,
+                             float* ws, void* stream);
+int ac_trm_kw_beam_step(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int B,
+                        int beam, int Tm, int max_len, int t, float temp, const int* tokens, const unsigned char* key_mask,
+                        const float* cum_logprob, float* top_val, int* top_idx, float* ws, void* stream);
+int ac_trm_kw_embed_qkv(const ac_trm_weights* w, const ac_trm_keyword* kw, int R, int row_div, int t, const int* tokens,
+                        long tok_stride, float* xout, float* qkv, void* stream);
+
 /* ---- ensemble decoding (ensemble.py:94-151 stepwise_forward, :154-276 beam_search) -------------
  * Several captioners decode one batch together: at every step each member's decoder runs on the shared prefix, the word
  * is chosen from m = mean_n log_softmax(logit_n) (f32, NOT renormalised) and is appended for all of them.  The members
@@ -711,6 +746,20 @@ int ac_embed_fwd(const float* emb, const float* pe, const int* word, const int* 
                  const unsigned long long* seed_dev, void* stream);
 int ac_embed_bwd(const float* dx, const int* word, float* demb, long rows, int d, float pa, unsigned long long seed_a,
                  float pb, unsigned long long seed_b, const unsigned long long* seed_dev, void* stream);
+/* The same for a KeywordProbTransformerDecoder (transformer_decoder.py:196-202), d = 256:
+ *   x[row] = dropB( LayerNorm( dropA(E[word[row]]) * sqrt(d) + kwp[clip[row]] ) * gamma + beta + pe[pos[row]] ),
+ * clip [all rows] int32: the clip (row of kwp = keyword_proj(keyword), [clips][d]) a row belongs to; gamma / beta =
+ * word_keyword_norm; the dropout sites and their element index are ac_embed_fwd's.  pre [all rows][d] receives the LayerNorm's
+ * input.  The backward (all rows at once) takes dx = d(loss)/dx and ADDS d gamma, d beta, dkwp [clips][d] (the sum over each
+ * clip's rows) and the embedding table's gradient (atomic adds); d keyword_proj follows from dkwp by ac_gemm.  emb, pe, kwp,
+ * gamma, beta, pre, x, dx: 16-byte aligned. */
+int ac_kw_embed_fwd(const float* emb, const float* pe, const int* word, const int* pos, const int* clip, const float* kwp,
+                    const float* gamma, const float* beta, float* pre, float* x, long row0, long rows, int d, float pa,
+                    unsigned long long seed_a, float pb, unsigned long long seed_b, const unsigned long long* seed_dev,
+                    float eps, void* stream);
+int ac_kw_embed_bwd(const float* dx, const int* word, const int* clip, const float* pre, const float* gamma, float* dgamma,
+                    float* dbeta, float* dkwp, float* demb, long rows, int d, float pa, unsigned long long seed_a, float pb,
+                    unsigned long long seed_b, const unsigned long long* seed_dev, float eps, void* stream);
 /* pre = res + dropout(x); y = LayerNorm(pre) over d = 256 columns (post-LN residual blocks of
  * nn.TransformerDecoderLayer; attn_proj's Dropout -> LayerNorm with res = NULL, transformer_decoder.py:38-43).
  * xmod > 0: x has only xmod rows and row r reads x[r % xmod] (the projected audio memory is shared by all passes, only
