@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import search_state
 from ._lib import check, ptr, stream
 from .rnn_decoder import (BahAttnCatFcDecoder, ConditionalBahAttnDecoder, SpecificityBahAttnDecoder, TemporalBahAttnDecoder,
                           check_condition, check_temporal_tag)
@@ -146,16 +147,12 @@ class Seq2SeqAttnModel(CaptionModel):
         mem = dec.memory(attn_emb, self._side(input_dict), input_dict["attn_emb_len"], beam, L)
         if tags is not None:
             tags = K.upload(tags, dev, torch.int32)
-        i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+        f32 = dict(device=dev, dtype=torch.float32)
         Vp = (V + 3) // 4 * 4
-        tok = [torch.full((R, ld), self.end_idx, **i32) for _ in range(2)]
-        tok[0][:, 0] = self.start_idx
-        mask = torch.zeros(R, ld, device=dev, dtype=torch.uint8)
-        cum, active, done_cnt = torch.zeros(R, **f32), torch.ones(B, **i32), torch.zeros(B, **i32)
-        active_before = torch.empty(B, **i32)
-        done_seq, done_score = torch.empty(B, cap, L, **i32), torch.empty(B, cap, **f32)
-        src_row, n_active = torch.empty(R, **i32), torch.full((1,), B, **i32)
-        top_val, top_idx = torch.empty(B, beam, **f32), torch.empty(B, beam, **i32)
+        st = search_state.beam_buffers(dev, B, beam, L, self.start_idx, self.end_idx, self.pad_idx)
+        search_state.beam_reset(st, B)
+        tok, cum, active, n_active, top_val, top_idx = (st[k] for k in ("tok", "cum", "active", "n_active", "top_val", "top_idx"))
+        active_before = torch.empty_like(active)
         scratch = torch.empty(2 * R * beam, **f32)
         logit, step_w = torch.empty(R, Vp, **f32), torch.empty(R, Tm, **f32)
         state, state_new = torch.zeros(R, d, **f32), torch.empty(R, d, **f32)
@@ -165,29 +162,18 @@ class Seq2SeqAttnModel(CaptionModel):
             # the host asks now and then whether any clip is still searching (TransformerModel.beam_search's schedule)
             if t in (8, 12, 16) and int(n_active.item()) == 0:
                 break
-            cur, nxt = tok[t & 1], tok[(t + 1) & 1]
+            cur = tok[t & 1]
             dec.step(mem, state, state_new, words=cur[:, t:], word_stride=ld, tags=tags if t == 0 else None, logit=logit,
                      ldl=Vp, attn_weight=step_w, attn_strides=(Tm, 1))
             active_before.copy_(active)
             check(lib.ac_ens_beam_step_select(planes, 1, Vp, B, beam, V, t, temp, ptr(cum), ptr(top_val), ptr(top_idx),
                                               ptr(scratch), stream()), "ac_ens_beam_step_select")
-            check(lib.ac_trm_beam_update(ptr(top_val), ptr(top_idx), ptr(cur), ptr(nxt), ptr(mask), ptr(cum), ptr(active),
-                                         ptr(done_cnt), ptr(done_seq), ptr(done_score), ptr(src_row), ptr(n_active), B, beam,
-                                         V, L, t, self.end_idx, self.pad_idx, cap, stream()), "ac_trm_beam_update")
-            check(lib.ac_bah_beam_gather(ptr(src_row), ptr(active_before), ptr(state_new), ptr(state), ptr(step_w),
+            search_state.beam_update(st, t, B, beam, V, L, self.end_idx, self.pad_idx, cap)
+            check(lib.ac_bah_beam_gather(ptr(st["src_row"]), ptr(active_before), ptr(state_new), ptr(state), ptr(step_w),
                                          ptr(hist[t & 1]), ptr(hist[(t + 1) & 1]), B, beam, d, Tm, L, t, stream()),
                   "ac_bah_beam_gather")
             last = hist[(t + 1) & 1]
-        counts, seqs, scores = done_cnt.cpu().numpy(), done_seq.cpu().numpy(), done_score.cpu().numpy()
-        seq = torch.full((B, n_best_size, L) if n_best else (B, L), self.end_idx, dtype=torch.long)
-        for i in range(B):
-            n = min(int(counts[i]), cap)
-            order = sorted(range(n), key=lambda j: -scores[i, j])   # stable: ties keep the append order
-            if n_best:
-                for j, o in enumerate(order[:n_best_size]):
-                    seq[i, j] = torch.from_numpy(seqs[i, o].astype(np.int64))
-            else:
-                seq[i] = torch.from_numpy(seqs[i, order[0]].astype(np.int64))
+        seq, _ = search_state.beam_rank(st, B, cap, L, self.end_idx, n_best, n_best_size)
         # logit / embed / sampled_logprob are not filled by the reference's beam search either (base.py:124-127)
         return {"seq": seq, "logit": torch.empty(B, L, V, device=dev), "sampled_logprob": torch.zeros(B, L),
                 "embed": torch.empty(B, L, d, device=dev),

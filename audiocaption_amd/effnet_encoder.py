@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import search_state
 from ._lib import check, ptr, stream
 from .cnn_encoder import cnn14_feat_len
 from .mel import MelSpectrogramBuffers, MelTables
@@ -331,13 +332,8 @@ class EfficientNetB2(nn.Module):
         input buffer and replayed; weights repacked by a checkpoint load or an in-place update start a new graph."""
         self._pack()
         key = (wav.device, tuple(wav.shape), self._packed_key)
-        st = self._graphs.pop(key, None)
-        if st is None:
-            st = {"uses": 0, "graph": None}
-            while len(self._graphs) >= 4:       # a handful of shapes (fixed-length batches); ragged streams stay eager
-                self._graphs.pop(next(iter(self._graphs)))
-        self._graphs[key] = st
-        st["uses"] += 1
+        # a handful of shapes (fixed-length batches); ragged streams stay eager
+        st = search_state.lookup(self._graphs, key, lambda: {"graph": None}, 4)
         if st["uses"] < 2:
             return self._encode(wav)
         if st["graph"] is not None and st["buf_gen"] != self._buf_gen:

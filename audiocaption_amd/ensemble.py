@@ -25,7 +25,6 @@ csrc/ensemble.hip over all members' logit planes; the whole search is a fixed la
 per shape into a HIP graph on its second use and replayed (AUDIOCAPTION_DECODE_GRAPH=0: always launch eagerly).
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -33,6 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import search_state
 from ._lib import check, ptr, stream
 from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder
 from .transformer_model import CaptionModel, _device_flags
@@ -154,31 +154,11 @@ class EnsembleModel(nn.Module):
         dev = encs[0]["attn_emb"].device
         key = (kind, dev, params, tuple(tuple(e["attn_emb"].shape) for e in encs),
                tuple(m.decoder._weights_key() for m in self.models), self.start_idx, self.end_idx, self.pad_idx)
-        st = self._state.pop(key, None)
-        if st is None:
-            st = build(dev)
-            st.update(graph=None, uses=0)
-        self._state[key] = st                  # most recently used last
-        while len(self._state) > 6:
-            self._state.pop(next(iter(self._state)))
-        st["uses"] += 1
+        st = search_state.lookup(self._state, key, lambda: dict(build(dev), graph=None), 6)
         for b, e in zip(st["members"], encs):
             b["attn_emb"].copy_(K.f32c(e["attn_emb"]))
             b["mem_len"].copy_(K.upload(e["attn_emb_len"], dev, torch.int32))
         return st, dev
-
-    def _run(self, st, dev, launch):
-        """The fixed launch sequence of a search: eager on the first use of a shape, a captured graph from the second."""
-        if os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") == "0" or st["uses"] < 2:
-            launch()
-            return
-        if st["graph"] is None:
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                launch()
-            st["graph"] = graph
-        st["graph"].replay()
 
     def _memory(self, st):
         lib = _lib.load()
@@ -247,7 +227,7 @@ class EnsembleModel(nn.Module):
                                                  ptr(st["logprob"]), ptr(st["tok"]), ptr(st["mask"]), ptr(st["unfinished"]),
                                                  ptr(st["cnt"]), None, stream()), "ac_ens_sample_pick")
 
-        self._run(st, dev, launch)
+        search_state.run(st, dev, launch)
         return {"seq": st["seq"].cpu(), "sampled_logprob": st["logprob"].cpu()}
 
     # ---- beam search (ensemble.py:154-276), all clips batched ---------------------------------------------
@@ -257,64 +237,32 @@ class EnsembleModel(nn.Module):
             raise ValueError(f"ensemble beam search covers beam sizes 1..8 (got {beam})")
         if not (temp > 0 and np.isfinite(temp)):
             raise ValueError(f"beam search needs a finite temp > 0 (got {temp})")
-        R, ld, cap = B * beam, max_length + 1, beam * max_length   # cap: every beam of every step may finish
+        R, cap = B * beam, beam * max_length   # cap: every beam of every step may finish
 
         def build(dev):
-            i32 = dict(device=dev, dtype=torch.int32)
-            f32 = dict(device=dev, dtype=torch.float32)
             members, planes, ldl = self._member_buffers(encs, R, beam, max_length, dev)
-            tok0 = torch.full((R, ld), self.end_idx, **i32)
-            tok0[:, 0] = self.start_idx
-            return {"members": members, "planes": planes, "ldl": ldl, "tok0": tok0,
-                    "mask0": (tok0 == self.pad_idx).to(torch.uint8), "tok": [torch.empty_like(tok0) for _ in range(2)],
-                    "mask": torch.empty(R, ld, device=dev, dtype=torch.uint8), "cum": torch.empty(R, **f32),
-                    "active": torch.empty(B, **i32), "done_cnt": torch.empty(B, **i32),
-                    "done_seq": torch.empty(B, cap, max_length, **i32), "done_score": torch.empty(B, cap, **f32),
-                    "src_row": torch.empty(R, **i32), "n_active": torch.empty(1, **i32),
-                    "top_val": torch.empty(B, beam, **f32), "top_idx": torch.empty(B, beam, **i32),
-                    "scratch": torch.empty(2 * R * beam, **f32)}
+            return {"members": members, "planes": planes, "ldl": ldl,
+                    **search_state.beam_buffers(dev, B, beam, max_length, self.start_idx, self.end_idx, self.pad_idx),
+                    "scratch": torch.empty(2 * R * beam, device=dev, dtype=torch.float32)}
 
         st, dev = self._state_for("beam", encs, (B, beam, max_length, temp), build)
         lib = _lib.load()
         tok = st["tok"]
 
         def launch():
-            tok[0].copy_(st["tok0"])
-            tok[1].fill_(self.end_idx)
-            st["mask"].copy_(st["mask0"])
-            st["cum"].zero_()
-            st["active"].fill_(1)
-            st["done_cnt"].zero_()
-            st["n_active"].fill_(B)
+            search_state.beam_reset(st, B)
             self._memory(st)
             for t in range(max_length):
                 self._steps(st, R, max_length, t, tok[t & 1], st["mask"], t & 1)
                 check(lib.ac_ens_beam_step_select(st["planes"], M, st["ldl"], B, beam, V, t, temp, ptr(st["cum"]),
                                                   ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["scratch"]), stream()),
                       "ac_ens_beam_step_select")
-                check(lib.ac_trm_beam_update_all(ptr(st["top_val"]), ptr(st["top_idx"]), ptr(tok[t & 1]), ptr(tok[(t + 1) & 1]),
-                                                 ptr(st["mask"]), ptr(st["cum"]), ptr(st["active"]), ptr(st["done_cnt"]),
-                                                 ptr(st["done_seq"]), ptr(st["done_score"]), ptr(st["src_row"]),
-                                                 ptr(st["n_active"]), B, beam, V, max_length, t, self.end_idx, self.pad_idx, cap,
-                                                 stream()), "ac_trm_beam_update_all")
+                search_state.beam_update(st, t, B, beam, V, max_length, self.end_idx, self.pad_idx, cap, all_rows=True)
                 if t + 1 < max_length:
                     for m, b in zip(self.models, st["members"]):   # every member re-gathers its own KV cache
                         check(lib.ac_trm_beam_reorder(ctypes.byref(m.decoder.weights()), R, max_length, t, ptr(st["src_row"]),
                                                       ptr(b["ws"]), stream()), "ac_trm_beam_reorder")
 
-        self._run(st, dev, launch)
-        counts = st["done_cnt"].cpu().numpy()
-        seqs = st["done_seq"].cpu().numpy()
-        scores = st["done_score"].cpu().numpy()
-        width = n_best_size if n_best else 1
-        seq = torch.full((B, width, max_length), self.end_idx, dtype=torch.long)
-        score = torch.full((B, width), float("-inf"))
-        for i in range(B):
-            n = min(int(counts[i]), cap)
-            order = sorted(range(n), key=lambda j: -scores[i, j])   # stable: ties keep the order the beams finished in
-            for j, o in enumerate(order[:width]):
-                seq[i, j] = torch.from_numpy(seqs[i, o].astype(np.int64))
-                score[i, j] = float(scores[i, o])
-        if not n_best:
-            seq, score = seq[:, 0], score[:, 0]
+        search_state.run(st, dev, launch)
+        seq, score = search_state.beam_rank(st, B, cap, max_length, self.end_idx, n_best, n_best_size)
         return {"seq": seq, "sampled_logprob": torch.zeros(B, max_length), "score": score}

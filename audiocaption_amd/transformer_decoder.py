@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import search_state
 from ._lib import check, f32c, ptr, stream
 
 
@@ -226,31 +227,55 @@ class TransformerDecoder(BaseDecoder):
         return memkv
 
     def forward(self, input_dict):
+        """The eval-mode full-sequence call: {"word", "attn_emb", "attn_emb_len", "cap_padding_mask"} (and what a conditioned
+        decoder takes beside them) -> {"embed", "logit"}."""
         if self.training:
             raise NotImplementedError(
-                "TransformerDecoder (HIP path): in train mode the decoder only runs inside the whole-model training "
-                "step (audiocaption_amd.train.TrainEngine / TransformerModel.forward with mode='train')")
-        lib = _lib.load()
+                f"{type(self).__name__} (HIP path): in train mode the decoder only runs inside the whole-model training "
+                "step (audiocaption_amd.train.TrainEngine / the model's forward with mode='train')")
         self.weights()       # first: an unsupported shape is refused before any buffer exists
         attn_emb = input_dict["attn_emb"]
         dev = attn_emb.device
         word = input_dict["word"].to(dev)
         N, T = word.shape
         Tm = attn_emb.shape[1]
+        extra = self._forward_extra(input_dict, dev, N)
         mem_len = K.upload(input_dict["attn_emb_len"], dev, torch.int32)
         mask = input_dict.get("cap_padding_mask")
         mask_u8 = None if mask is None else mask.to(dev).to(torch.uint8).contiguous()
-        memkv = self.memory(attn_emb)
+        st = {**extra, "attn_emb": f32c(attn_emb),
+              "memkv": torch.empty(self.nlayers, N * Tm, 2 * self.d_model, device=dev, dtype=torch.float32),
+              "tmp": torch.empty(N * Tm, self.d_model, device=dev, dtype=torch.float32)}
+        self._memory_launch(st)
         tokens = word.to(torch.int32).contiguous()
         embed = torch.empty(N, T, self.d_model, device=dev, dtype=torch.float32)
         logit = torch.empty(N, T, self.vocab_size, device=dev, dtype=torch.float32)
         ws = self.workspace(N, T, dev)
-        check(lib.ac_trm_forward_tokens(ctypes.byref(self.weights()), ptr(memkv), ptr(mem_len), N, Tm, ptr(tokens),
-                                        ptr(mask_u8), T, ptr(embed), ptr(logit), ptr(ws), stream()),
-              "ac_trm_forward_tokens")
+        self._trm("forward_tokens", st.get("kw"), ptr(st["memkv"]), ptr(mem_len), N, Tm, ptr(tokens), ptr(mask_u8), T, ptr(embed),
+                  ptr(logit), ptr(ws))
         return {"embed": embed, "logit": logit}
 
-    # ---- what a conditioned decoder adds to a search (KeywordProbTransformerDecoder overrides these four) -------------------
+    def _trm(self, name, kw, *args):
+        """``ac_trm_<name>(weights, *args, stream)`` - with the keyword struct ``kw`` of a conditioned decoder,
+        ``ac_trm_kw_<name>(weights, &kw, *args, stream)``: the one place that chooses between the two entry points."""
+        lib, w = _lib.load(), ctypes.byref(self.weights())
+        if kw is None:
+            check(getattr(lib, "ac_trm_" + name)(w, *args, stream()), "ac_trm_" + name)
+        else:
+            check(getattr(lib, "ac_trm_kw_" + name)(w, ctypes.byref(kw), *args, stream()), "ac_trm_kw_" + name)
+
+    # ---- what a conditioned decoder adds to a search (KeywordProbTransformerDecoder overrides these) -------------------------
+    def _keyword_struct(self, kwp, row_div):
+        """The keyword struct over projected keywords ``kwp``, ``row_div`` decoder rows per clip (None: the plain entry
+        points)."""
+        if kwp is not None:
+            raise TypeError(f"{self.__class__.__name__} takes no conditioning input")
+        return None
+
+    def _forward_extra(self, input_dict, dev, N):
+        """``_extra_buffers`` of a ``forward`` over N rows with this call's inputs in them, checked before any launch."""
+        return {}
+
     def _extra_key(self, extra):
         """The part of a search state's cache key that names the extra per-clip inputs (none here)."""
         if extra is not None:
@@ -273,20 +298,16 @@ class TransformerDecoder(BaseDecoder):
 
     def _greedy_launch(self, st, max_length, start_idx, end_idx, pad_idx):
         """Memory preparation + the whole on-device greedy loop on the current stream (capturable)."""
-        lib = _lib.load()
         B, Tm, _ = st["attn_emb"].shape
-        w = ctypes.byref(self.weights())
         self._memory_launch(st)
         if st.get("cluster_ws") is not None:
-            check(lib.ac_trm_greedy_cluster(w, ptr(st["cluster_pk"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length,
-                                            start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]),
-                                            ptr(st["sampled_logprob"]), ptr(st["embed"]), ptr(st["unfinished_cnt"]),
-                                            ptr(st["cluster_ws"]), int(st["early_stop"]), stream()), "ac_trm_greedy_cluster")
+            self._trm("greedy_cluster", None, ptr(st["cluster_pk"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length,
+                      start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
+                      ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["cluster_ws"]), int(st["early_stop"]))
             return
-        check(lib.ac_trm_greedy_segments(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm, max_length, start_idx,
-                                         end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
-                                         ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()),
-              "ac_trm_greedy_segments")
+        self._trm("greedy_segments", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm, max_length,
+                  start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
+                  ptr(st["unfinished_cnt"]), ptr(st["ws"]))
 
     def _search_buffers(self, key, dev, B, Tm, A, max_length, segments=1):
         """Static buffers of an on-device search (greedy or sampled) over B rows: inputs, workspace, outputs.  ``segments``
@@ -332,9 +353,8 @@ class TransformerDecoder(BaseDecoder):
         reference returns).  Set AUDIOCAPTION_DECODE_GRAPH=0 to launch eagerly."""
         parts = list(attn_emb) if isinstance(attn_emb, (list, tuple)) else [attn_emb]   # several batches, one chain: each is
         dev = parts[0].device                                                           # copied into its rows of the static buffer
-        B, (Tm, A) = sum(p_.shape[0] for p_ in parts), parts[0].shape[1:]
+        B, Tm = sum(p_.shape[0] for p_ in parts), parts[0].shape[1]
         segments = len(parts) if len({p_.shape[0] for p_ in parts}) == 1 else 1
-        use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
         mode = mode or os.environ.get("AUDIOCAPTION_GREEDY", "auto")
         if mode not in ("auto", "chain", "cluster"):
             raise ValueError(f"AUDIOCAPTION_GREEDY={mode!r}: 'auto', 'chain' or 'cluster'")
@@ -352,55 +372,50 @@ class TransformerDecoder(BaseDecoder):
             self._extra_key(extra)
         if self._greedy_state is None:
             self._greedy_state = {}
-        states = self._greedy_state
-        st = states.pop(key, None)
-        if st is None:
-            st = self._search_buffers(key, dev, B, Tm, A, max_length, segments)
-            if cluster:
-                nb = _lib.load().ac_trm_cluster_workspace_bytes(B)
-                st["cluster_ws"] = torch.zeros((nb + 7) // 8, device=dev, dtype=torch.int64)   # (the error word is reset by every call)
-                st["cluster_pk"] = self.cluster_pack()
-                st["early_stop"] = early
-        states[key] = st                       # most recently used last; batches of changing length keep 8 shapes
-        while len(states) > 8:
-            states.pop(next(iter(states)))
-        st["uses"] += 1
+
+        def more():
+            if not cluster:
+                return {}
+            nb = _lib.load().ac_trm_cluster_workspace_bytes(B)
+            return {"cluster_ws": torch.zeros((nb + 7) // 8, device=dev, dtype=torch.int64),   # (the error word is reset by every call)
+                    "cluster_pk": self.cluster_pack(), "early_stop": early}
+        if isinstance(attn_emb_len, (list, tuple)):
+            attn_emb_len = torch.cat([torch.as_tensor(l_).cpu().reshape(-1) for l_ in attn_emb_len])   # host side
+        return self._search(self._greedy_state, key, parts, attn_emb_len, max_length, segments, more, extra,
+                            lambda st: self._greedy_launch(st, max_length, start_idx, end_idx, pad_idx))
+
+    def _search(self, states, key, parts, attn_emb_len, max_length, segments, more, extra, launch, seed=None):
+        """The body of ``greedy`` and ``sample``: the state of ``key`` (``_search_buffers`` and what ``more()`` adds; batches of
+        changing length keep 8 shapes), every batch of ``parts`` copied into its rows of the static input, ``launch(st)`` run or
+        replayed (``search_state.run``), the outputs cloned out."""
+        dev = parts[0].device
+
+        def build():
+            B, (Tm, A) = sum(p_.shape[0] for p_ in parts), parts[0].shape[1:]
+            return {**self._search_buffers(key, dev, B, Tm, A, max_length, segments), **more()}
+        st = search_state.lookup(states, key, build, 8)
         r0 = 0
         for p_ in parts:
             st["attn_emb"][r0:r0 + p_.shape[0]].copy_(p_)
             r0 += p_.shape[0]
-        if isinstance(attn_emb_len, (list, tuple)):
-            attn_emb_len = torch.cat([torch.as_tensor(l_).cpu().reshape(-1) for l_ in attn_emb_len])   # host side
         st["mem_len"].copy_(K.upload(attn_emb_len, dev, torch.int32))
+        if seed is not None:
+            st["seed"].fill_(seed)
         self._stage_extra(st, extra)
-        if not use_graph or st["uses"] < 2:
-            # first batch of this shape: plain launches (also the warm-up a capture needs); a shape that never comes
-            # back is never captured
-            self._greedy_launch(st, max_length, start_idx, end_idx, pad_idx)
-        else:
-            if st["graph"] is None:
-                torch.cuda.synchronize(dev)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._greedy_launch(st, max_length, start_idx, end_idx, pad_idx)
-                st["graph"] = graph
-            st["graph"].replay()
+        search_state.run(st, dev, lambda: launch(st))
         out = {k: st[k].clone() for k in ("seq", "logit", "sampled_logprob", "embed", "unfinished_cnt")}
-        if cluster:
+        if st.get("cluster_ws") is not None:
             out["cluster_error"] = st["cluster_ws"][:1].clone()
         return out
 
     def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params):
         """Memory preparation + the whole sampled search on the current stream (capturable; the seed is read on the device)."""
-        lib = _lib.load()
         B, Tm, _ = st["attn_emb"].shape
-        w = ctypes.byref(self.weights())
         method, k, top_p, temp = params
         self._memory_launch(st)
-        check(lib.ac_trm_sample(w, ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx, pad_idx,
-                                ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
-                                ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp),
-                                ptr(st["seed"]), stream()), "ac_trm_sample")
+        self._trm("sample", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx, pad_idx,
+                  ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]), ptr(st["unfinished_cnt"]),
+                  ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st["seed"]))
 
     def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed, extra=None):
         """On-device sampled search (base.py:152-170 with a sampling ``sample_method``; csrc/sample.hip).  ``method``, ``k``,
@@ -412,53 +427,31 @@ class TransformerDecoder(BaseDecoder):
         seed lives in a device word that is written before every launch or replay, so one graph serves every seed.
         AUDIOCAPTION_DECODE_GRAPH=0 launches eagerly."""
         from .sampling import seed_word
-        dev = attn_emb.device
-        B, Tm, A = attn_emb.shape
-        use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
+        dev, (B, Tm, _) = attn_emb.device, attn_emb.shape
         params = (int(method), int(k), float(top_p), float(temp))
         key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key()) + self._extra_key(extra)
         if getattr(self, "_sample_state", None) is None:
             self._sample_state = {}
-        states = self._sample_state
-        st = states.pop(key, None)
-        if st is None:
-            st = self._search_buffers(key, dev, B, Tm, A, max_length)
-            st["seed"] = torch.zeros(1, device=dev, dtype=torch.int64)
-        states[key] = st                       # most recently used last
-        while len(states) > 8:
-            states.pop(next(iter(states)))
-        st["uses"] += 1
-        st["attn_emb"].copy_(attn_emb)
-        st["mem_len"].copy_(K.upload(attn_emb_len, dev, torch.int32))
-        st["seed"].fill_(seed_word(seed))
-        self._stage_extra(st, extra)
-        if not use_graph or st["uses"] < 2:
-            self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params)
-        else:
-            if st["graph"] is None:
-                torch.cuda.synchronize(dev)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params)
-                st["graph"] = graph
-            st["graph"].replay()
-        return {k_: st[k_].clone() for k_ in ("seq", "logit", "sampled_logprob", "embed", "unfinished_cnt")}
+        return self._search(self._sample_state, key, [attn_emb], attn_emb_len, max_length, 1,
+                            lambda: {"seed": torch.zeros(1, device=dev, dtype=torch.int64)}, extra,
+                            lambda st: self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params),
+                            seed=seed_word(seed))
 
-    def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws):
-        lib = _lib.load()
+    def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws, kwp=None):
+        """One beam-search step outside a search state.  ``kwp`` (B, d): the clips' projected keywords, for a decoder that
+        takes them."""
+        kw = self._keyword_struct(kwp, beam)
         dev = memkv.device
         top_val = torch.empty(B, beam, device=dev, dtype=torch.float32)
         top_idx = torch.empty(B, beam, device=dev, dtype=torch.int32)
-        check(lib.ac_trm_beam_step(ctypes.byref(self.weights()), ptr(memkv), ptr(mem_len), B, beam, Tm, max_length,
-                                   t, float(temp), ptr(tokens), ptr(mask), ptr(cum), ptr(top_val), ptr(top_idx),
-                                   ptr(ws), stream()), "ac_trm_beam_step")
+        self._trm("beam_step", kw, ptr(memkv), ptr(mem_len), B, beam, Tm, max_length, t, float(temp), ptr(tokens), ptr(mask),
+                  ptr(cum), ptr(top_val), ptr(top_idx), ptr(ws))
         return top_val, top_idx
 
     def _beam_step_launch(self, st, B, beam, Tm, max_length, t, temp, tokens):
         """Step t of a beam search over the static buffers of its state (``TransformerModel._beam_begin``; capturable)."""
-        check(_lib.load().ac_trm_beam_step(ctypes.byref(self.weights()), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm,
-                                           max_length, t, float(temp), ptr(tokens), ptr(st["mask"]), ptr(st["cum"]),
-                                           ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]), stream()), "ac_trm_beam_step")
+        self._trm("beam_step", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length, t, float(temp),
+                  ptr(tokens), ptr(st["mask"]), ptr(st["cum"]), ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]))
 
     def beam_reorder(self, R, max_length, t, src_row, ws):
         lib = _lib.load()
@@ -527,15 +520,24 @@ class KeywordProbTransformerDecoder(TransformerDecoder):
             raise KeyError("keyword: a KeywordProbTransformerDecoder needs the keyword batch")
         return ("keyword", tuple(extra.shape))
 
+    def _keyword_struct(self, kwp, row_div):
+        if kwp is None:
+            raise KeyError("keyword: KeywordProbTransformerDecoder.beam_step needs kwp, the projected keyword batch")
+        _, _, ln_w, ln_b = self._keyword_weights()
+        return _lib.AcTrmKeyword(kwp.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), int(row_div))
+
     def _extra_buffers(self, dev, B, row_div=1):
         f32 = dict(device=dev, dtype=torch.float32)
-        _, _, ln_w, ln_b = self._keyword_weights()
         kwp = torch.empty(B, self.d_model, **f32)
-        kw = _lib.AcTrmKeyword(kwp.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), int(row_div))
-        return {"keyword": torch.empty(B, self.keyword_classes_num, **f32), "kwp": kwp, "kw": kw, "kw_hold": (ln_w, ln_b)}
+        return {"keyword": torch.empty(B, self.keyword_classes_num, **f32), "kwp": kwp,
+                "kw": self._keyword_struct(kwp, row_div), "kw_hold": self._keyword_weights()[2:]}
 
     def _stage_extra(self, st, extra):
         st["keyword"].copy_(check_keyword(extra, *st["keyword"].shape))
+
+    def _forward_extra(self, input_dict, dev, N):
+        keyword = check_keyword(input_dict.get("keyword"), N, self.keyword_classes_num).to(dev).contiguous()
+        return {**self._extra_buffers(dev, N), "keyword": keyword}   # projected where it lies: no copy into the buffer
 
     def _keyword_proj_launch(self, keyword, kwp):
         """kwp (B, d) = keyword (B, classes) keyword_proj.weight^T + bias on the current stream (any class count)."""
@@ -547,30 +549,6 @@ class KeywordProbTransformerDecoder(TransformerDecoder):
     def _memory_launch(self, st):
         super()._memory_launch(st)
         self._keyword_proj_launch(st["keyword"], st["kwp"])
-
-    def _greedy_launch(self, st, max_length, start_idx, end_idx, pad_idx):
-        B, Tm, _ = st["attn_emb"].shape
-        self._memory_launch(st)
-        check(_lib.load().ac_trm_kw_greedy_segments(
-            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm,
-            max_length, start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
-            ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), stream()), "ac_trm_kw_greedy_segments")
-
-    def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params):
-        B, Tm, _ = st["attn_emb"].shape
-        method, k, top_p, temp = params
-        self._memory_launch(st)
-        check(_lib.load().ac_trm_kw_sample(
-            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length,
-            start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
-            ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st["seed"]),
-            stream()), "ac_trm_kw_sample")
-
-    def _beam_step_launch(self, st, B, beam, Tm, max_length, t, temp, tokens):
-        check(_lib.load().ac_trm_kw_beam_step(
-            ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length,
-            t, float(temp), ptr(tokens), ptr(st["mask"]), ptr(st["cum"]), ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]),
-            stream()), "ac_trm_kw_beam_step")
 
     def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, keyword=None, alone=False, mode=None):
         """``TransformerDecoder.greedy`` with the keyword batch (B, keyword_classes_num); one batch per call.  ``mode``
@@ -587,47 +565,3 @@ class KeywordProbTransformerDecoder(TransformerDecoder):
         keyword = check_keyword(keyword, attn_emb.shape[0], self.keyword_classes_num)
         return super().sample(attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed,
                               extra=keyword)
-
-    def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws, kwp=None):
-        """``TransformerDecoder.beam_step`` with ``kwp`` (B, d) = ``keyword_proj`` of the clips' keywords."""
-        if kwp is None:
-            raise KeyError("keyword: KeywordProbTransformerDecoder.beam_step needs kwp, the projected keyword batch")
-        dev = memkv.device
-        _, _, ln_w, ln_b = self._keyword_weights()
-        kw = _lib.AcTrmKeyword(kwp.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), int(beam))
-        top_val = torch.empty(B, beam, device=dev, dtype=torch.float32)
-        top_idx = torch.empty(B, beam, device=dev, dtype=torch.int32)
-        check(_lib.load().ac_trm_kw_beam_step(ctypes.byref(self.weights()), ctypes.byref(kw), ptr(memkv), ptr(mem_len), B, beam,
-                                              Tm, max_length, t, float(temp), ptr(tokens), ptr(mask), ptr(cum), ptr(top_val),
-                                              ptr(top_idx), ptr(ws), stream()), "ac_trm_kw_beam_step")
-        return top_val, top_idx
-
-    def forward(self, input_dict):
-        """The eval-mode full-sequence call: {"word", "attn_emb", "attn_emb_len", "cap_padding_mask", "keyword"} ->
-        {"embed", "logit"} (transformer_decoder.py:186-214)."""
-        if self.training:
-            raise NotImplementedError(
-                "KeywordProbTransformerDecoder (HIP path): in train mode the decoder only runs inside the whole-model training "
-                "step (KeywordCondTransformerModel.forward with mode='train')")
-        lib = _lib.load()
-        self.weights()       # first: an unsupported shape is refused before any buffer exists
-        attn_emb = input_dict["attn_emb"]
-        dev = attn_emb.device
-        word = input_dict["word"].to(dev)
-        N, T = word.shape
-        keyword = check_keyword(input_dict.get("keyword"), N, self.keyword_classes_num).to(dev).contiguous()
-        Tm = attn_emb.shape[1]
-        mem_len = K.upload(input_dict["attn_emb_len"], dev, torch.int32)
-        mask = input_dict.get("cap_padding_mask")
-        mask_u8 = None if mask is None else mask.to(dev).to(torch.uint8).contiguous()
-        memkv = self.memory(attn_emb)
-        st = self._extra_buffers(dev, N)
-        self._keyword_proj_launch(keyword, st["kwp"])
-        tokens = word.to(torch.int32).contiguous()
-        embed = torch.empty(N, T, self.d_model, device=dev, dtype=torch.float32)
-        logit = torch.empty(N, T, self.vocab_size, device=dev, dtype=torch.float32)
-        ws = self.workspace(N, T, dev)
-        check(lib.ac_trm_kw_forward_tokens(ctypes.byref(self.weights()), ctypes.byref(st["kw"]), ptr(memkv), ptr(mem_len), N,
-                                           Tm, ptr(tokens), ptr(mask_u8), T, ptr(embed), ptr(logit), ptr(ws), stream()),
-              "ac_trm_kw_forward_tokens")
-        return {"embed": embed, "logit": logit}

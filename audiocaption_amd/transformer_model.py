@@ -15,8 +15,6 @@ call per step (the reference loops over clips, base.py:266) with the reference's
 device->host copy per step.
 """
 import ctypes
-
-import numpy as np
 import os
 import weakref
 
@@ -25,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import search_state
 from ._lib import check, ptr, stream
 from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder, check_keyword
 
@@ -541,12 +540,9 @@ class TransformerModel(CaptionModel):
                           (lambda pool=pool, a=host_seq, b=host_lp, c=host_flag, d=host_cnt: pool.append((a, b, c, d))), host_flag,
                           host_cnt if shared else None)
 
-    def _decoder_extra(self, input_dict):
-        """The per-clip conditioning input a search hands to the decoder beside the audio memory (none here)."""
-        return None
-
     def _search_kwargs(self, input_dict):
-        """Keyword arguments of ``decoder.greedy`` / ``decoder.sample`` that carry that input."""
+        """The per-clip conditioning input a search hands to the decoder beside the audio memory, as the keyword argument of
+        ``decoder.greedy`` / ``decoder.sample`` that carries it (none here)."""
         return {}
 
     # ---- greedy (base.py:152-218) -----------------------------------------------------------------
@@ -628,74 +624,45 @@ class TransformerModel(CaptionModel):
         # dependent kernels cannot keep up once it shares the device with the next batches' encoders.
         lib = _lib.load()
         dec.weights()                              # first: an unsupported decoder shape is refused before any buffer exists
-        ld = max_length + 1
         cap = beam * max_length                    # upper bound of finished beams per clip
-        use_graph = os.environ.get("AUDIOCAPTION_DECODE_GRAPH", "1") != "0"
-        extra = self._decoder_extra(input_dict)    # a conditioned decoder's per-clip inputs (None for the plain one)
+        extra = self._search_kwargs(input_dict).get("keyword")   # a conditioned decoder's per-clip input (None for the plain one)
         key = (dev, B, Tm, A, beam, max_length, temp, self.start_idx, self.end_idx, self.pad_idx, dec._weights_key(), slot) + \
             dec._extra_key(extra)
         if getattr(self, "_beam_state", None) is None:
             self._beam_state = {}
-        states = self._beam_state
-        st = states.pop(key, None)
-        if st is None:
-            i32 = dict(device=dev, dtype=torch.int32)
+
+        def build():
             f32 = dict(device=dev, dtype=torch.float32)
-            tok0 = torch.full((R, ld), self.end_idx, **i32)
-            tok0[:, 0] = self.start_idx
-            mask0 = torch.zeros(R, ld, device=dev, dtype=torch.uint8)
-            if self.start_idx == self.pad_idx or self.end_idx == self.pad_idx:
-                mask0 = (tok0 == self.pad_idx).to(torch.uint8)
             ws_n = lib.ac_trm_workspace_floats(ctypes.byref(dec.weights()), R, max_length)
-            st = {**dec._extra_buffers(dev, B, beam), "uses": 0, "graphs": {},
-                  "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, **i32),
-                  "memkv": torch.empty(dec.nlayers, B * Tm, 2 * dec.d_model, **f32),
-                  "tmp": torch.empty(B * Tm, dec.d_model, **f32), "ws": torch.empty(ws_n, **f32),
-                  "tok0": tok0, "tok1": torch.full((R, ld), self.end_idx, **i32), "mask0": mask0,
-                  "tok": [torch.empty(R, ld, **i32) for _ in range(2)],
-                  "mask": torch.empty(R, ld, device=dev, dtype=torch.uint8),
-                  "cum": torch.empty(R, **f32), "active": torch.empty(B, **i32), "done_cnt": torch.empty(B, **i32),
-                  "done_seq": torch.empty(B, cap, max_length, **i32), "done_score": torch.empty(B, cap, **f32),
-                  "src_row": torch.empty(R, **i32), "n_active": torch.empty(1, **i32),
-                  "top_val": torch.empty(B, beam, **f32), "top_idx": torch.empty(B, beam, **i32)}
-        states[key] = st                       # most recently used last
-        while len(states) > 6:
-            states.pop(next(iter(states)))
-        st["uses"] += 1
+            return {**dec._extra_buffers(dev, B, beam), "graphs": {},
+                    "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
+                    "memkv": torch.empty(dec.nlayers, B * Tm, 2 * dec.d_model, **f32),
+                    "tmp": torch.empty(B * Tm, dec.d_model, **f32), "ws": torch.empty(ws_n, **f32),
+                    **search_state.beam_buffers(dev, B, beam, max_length, self.start_idx, self.end_idx, self.pad_idx)}
+        st = search_state.lookup(self._beam_state, key, build, 6)
         st["attn_emb"].copy_(K.f32c(attn_emb))
         st["mem_len"].copy_(K.upload(input_dict["attn_emb_len"], dev, torch.int32))
         dec._stage_extra(st, extra)
-        tok, mask, cum, active = st["tok"], st["mask"], st["cum"], st["active"]
-        done_cnt, done_seq, done_score = st["done_cnt"], st["done_seq"], st["done_score"]
-        src_row, n_active, ws = st["src_row"], st["n_active"], st["ws"]
+        tok = st["tok"]
         w = ctypes.byref(dec.weights())
 
         def segment(t0, t1):
             """Steps t0 .. t1 - 1 on the current stream (capturable: fixed launches over the static buffers)."""
             if t0 == 0:
-                tok[0].copy_(st["tok0"])
-                tok[1].copy_(st["tok1"])
-                mask.copy_(st["mask0"])
-                cum.zero_()
-                active.fill_(1)
-                done_cnt.zero_()
-                n_active.fill_(B)
+                search_state.beam_reset(st, B)
                 dec._memory_launch(st)
             for t in range(t0, t1):
                 dec._beam_step_launch(st, B, beam, Tm, max_length, t, temp, tok[t & 1])
-                check(lib.ac_trm_beam_update(ptr(st["top_val"]), ptr(st["top_idx"]), ptr(tok[t & 1]), ptr(tok[(t + 1) & 1]),
-                                             ptr(mask), ptr(cum), ptr(active), ptr(done_cnt), ptr(done_seq),
-                                             ptr(done_score), ptr(src_row), ptr(n_active), B, beam, V, max_length, t,
-                                             self.end_idx, self.pad_idx, cap, stream()), "ac_trm_beam_update")
+                search_state.beam_update(st, t, B, beam, V, max_length, self.end_idx, self.pad_idx, cap)
                 if t + 1 < max_length:
-                    check(lib.ac_trm_beam_reorder(w, R, max_length, t, ptr(src_row), ptr(ws), stream()),
+                    check(lib.ac_trm_beam_reorder(w, R, max_length, t, ptr(st["src_row"]), ptr(st["ws"]), stream()),
                           "ac_trm_beam_reorder")
 
         # AUDIOCAPTION_BEAM_SEGMENTS="0,8,12,16" (default): the steps after which the host asks whether any clip is still searching
         # ("0": never - one launch sequence for the whole search, no host synchronisation inside it)
         seg = [int(v) for v in os.environ.get("AUDIOCAPTION_BEAM_SEGMENTS", "0,8,12,16").split(",") if v.strip() != ""]
         bounds = sorted({0} | {b for b in seg if 0 < b < max_length}) + [max_length]
-        return {"st": st, "segment": segment, "bounds": bounds, "next": 0, "use_graph": use_graph and st["uses"] >= 2,
+        return {"st": st, "segment": segment, "bounds": bounds, "next": 0, "use_graph": search_state.captures(st),
                 "dev": dev, "B": B, "beam": beam, "max_length": max_length, "cap": cap, "V": V, "n_best": n_best,
                 "n_best_size": n_best_size}
 
@@ -714,38 +681,14 @@ class TransformerModel(CaptionModel):
         else:
             # keyed by the step range: AUDIOCAPTION_BEAM_SEGMENTS is read per call, and a segment that starts at the same
             # step under another list ends at another step
-            graph = st["graphs"].get((t0, t1))
-            if graph is None:
-                torch.cuda.synchronize(run["dev"])
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    run["segment"](t0, t1)
-                st["graphs"][(t0, t1)] = graph
-            graph.replay()
+            search_state.replay(st["graphs"], (t0, t1), run["dev"], lambda: run["segment"](t0, t1))
         run["next"] = i + 1
         return True
 
     def _beam_finish(self, run):
         st, dec = run["st"], self.decoder
         B, max_length, cap, V, dev = run["B"], run["max_length"], run["cap"], run["V"], run["dev"]
-        n_best, n_best_size = run["n_best"], run["n_best_size"]
-        done_cnt, done_seq, done_score = st["done_cnt"], st["done_seq"], st["done_score"]
-        counts = done_cnt.cpu().numpy()
-        seqs = done_seq.cpu().numpy()
-        scores = done_score.cpu().numpy()
-
-        if n_best:
-            seq = torch.full((B, n_best_size, max_length), self.end_idx, dtype=torch.long)
-        else:
-            seq = torch.full((B, max_length), self.end_idx, dtype=torch.long)
-        for i in range(B):
-            n = min(int(counts[i]), cap)
-            order = sorted(range(n), key=lambda j: -scores[i, j])   # stable: ties keep the append order
-            if n_best:
-                for j, o in enumerate(order[:n_best_size]):
-                    seq[i, j] = torch.from_numpy(seqs[i, o].astype(np.int64))
-            else:
-                seq[i] = torch.from_numpy(seqs[i, order[0]].astype(np.int64))
+        seq, _ = search_state.beam_rank(st, B, cap, max_length, self.end_idx, run["n_best"], run["n_best_size"])
         # logit / embed / sampled_logprob are not filled by the reference's beam search either
         # (base.py:124-127 leaves them at torch.empty / zeros)
         return {
@@ -784,8 +727,6 @@ class KeywordCondTransformerModel(TransformerModel):
         raise NotImplementedError("KeywordCondTransformerModel: forward_async (shared greedy chains, deferred beam searches) is "
                                   "not built for keyword conditioning; use model(input_dict)")
 
-    def _decoder_extra(self, input_dict):
-        return check_keyword(input_dict.get("keyword"), input_dict["attn_emb"].shape[0], self.decoder.keyword_classes_num)
-
     def _search_kwargs(self, input_dict):
-        return {"keyword": self._decoder_extra(input_dict)}
+        return {"keyword": check_keyword(input_dict.get("keyword"), input_dict["attn_emb"].shape[0],
+                                         self.decoder.keyword_classes_num)}
