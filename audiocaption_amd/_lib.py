@@ -96,6 +96,7 @@ SIGNATURES = {
     "ac_trm_greedy_segments": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ac_sample_rows": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P]),
     "ac_trm_sample": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
+    "ac_trm_sample_multi": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P]),
     "ac_conv3x3_skinny_workspace_floats": (_L, [_I, _I, _I, _I, _I]),
     "ac_conv3x3_bn_relu_skinny": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _F, _U64, _P, _P]),
     "ac_trm_cluster_pack_floats": (_L, [_WP]),
@@ -193,6 +194,8 @@ SIGNATURES = {
     # Self-BLEU, distinct n-grams and richness on token ids (csrc/diversity.hip)
     "ac_diversity_workspace_bytes": (_L, [_I, _I]),
     "ac_diversity_scores": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "ac_diversity_group_workspace_bytes": (_L, [_I, _I, _I]),
+    "ac_diversity_group_scores": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_gru_layer_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_gru_layer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ac_swa_update": (_I, [_P, _P, _L, _I, _P]),

@@ -1655,14 +1655,16 @@ extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int m
 // loop ends when every row of THAT batch has emitted <end> (base.py:167, :206-211).  The launch sequence is fixed - it is
 // captured into a graph - so the end is data: from then on every workgroup of every launch that holds only rows of ended
 // segments returns before its first load (struct Live), and a last launch clears the columns of the steps not run.
+// row_div: rows per clip - row r reads the memory K / V and the length of clip r / row_div (memkv and mem_len hold
+// B / row_div clips), as the rows of a beam do; 1 = a clip per row.
 static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments, int Tm,
                       int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
                       float* embed, int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream,
-                      const ac_trm_keyword* kw = nullptr) {
+                      const ac_trm_keyword* kw = nullptr, int row_div = 1) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !seq || !logit || !logprob || !embed || !unfinished_cnt || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || Tm <= 0 || Tm > MAX_KEYS || max_len <= 0 || max_len > w->max_pos) return AC_ERR_ARG;
-  if (segments <= 0 || B % segments) return AC_ERR_ARG;
+  if (segments <= 0 || B % segments || row_div <= 0 || B % row_div) return AC_ERR_ARG;
   if (w->vocab > PICK_MAXV) return AC_ERR_ARG;
   if (sp && (ac_sample_check(w->vocab, sp->method, sp->k, sp->top_p, sp->temp) != AC_OK || !sp->seed)) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -1677,7 +1679,7 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
   for (int t = 0; t < max_len; ++t) {
     StepOut fin;
     live.t = t;
-    AC_TRY(decoder_step(w, memkv, mem_len, B, 1, Tm, max_len, t, ws.tok, ws.mask, max_len + 1, ws.cache[0], ws,
+    AC_TRY(decoder_step(w, memkv, mem_len, B, row_div, Tm, max_len, t, ws.tok, ws.mask, max_len + 1, ws.cache[0], ws,
                         &fin, s, live, kw));
     AC_TRY(classifier_step(w, fin, B, embed + (size_t)t * d, (long)max_len * d, logit + (size_t)t * V,
                            (long)max_len * V, s, live));
@@ -1728,6 +1730,20 @@ extern "C" int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const 
   sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
   return trm_search(w, memkv, mem_len, B, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
                     unfinished_cnt, ws_base, &sp, stream);
+}
+
+extern "C" int ac_trm_sample_multi(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B,
+                                   int samples_per_clip, int Tm, int max_len, int start_idx, int end_idx, int pad_idx,
+                                   int64_t* seq, float* logit, float* logprob, float* embed, int* unfinished_cnt,
+                                   float* ws_base, int method, int k, float top_p, float temp, const uint64_t* seed_dev,
+                                   void* stream) {
+  // the row indices of the search (tokens, masks, the initialisation) are ints
+  if (B <= 0 || samples_per_clip < 1 || max_len <= 0 || (long)B * samples_per_clip * ((long)max_len + 1) > 0x7fffffffL)
+    return AC_ERR_ARG;
+  SampleParams sp = {};
+  sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
+  return trm_search(w, memkv, mem_len, B * samples_per_clip, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob,
+                    embed, unfinished_cnt, ws_base, &sp, stream, nullptr, samples_per_clip);
 }
 
 static int forward_tokens(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int N,

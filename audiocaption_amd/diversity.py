@@ -16,7 +16,16 @@ in include/audiocaption_hip.h.  Distinct-2 divides by the number of WORDS, as di
 by a sentence's own unigrams and bigrams; where the reference divides by zero (a sentence without a bigram) they raise
 ValueError.  The sentence rule and the canonical-id table are those of cider.py.
 
-Not built: Self-BLEU within groups (the samples of one clip), mBLEU, clap_score.py and specificity.py.
+Within groups - the evaluation of SEVERAL captions per clip, each clip's captions scored against each other only:
+
+* ``score_groups(vocabulary, vocab_size, words, start_idx, end_idx, group_off=None)`` on word ids, ``(B, S, T)`` (the groups
+  are the clips: ``TransformerModel``'s ``seq_dev`` under ``n_samples``, taken where it lies) or ``(N, T)`` with explicit
+  row offsets ``group_off`` (ragged groups); the results stay on the device.
+* ``compute_group_score({key: [sentence, ...]})`` on strings: mBLEU-1..4 (nltk's ``sentence_bleu`` of a caption against its
+  clip's other captions with uniform weights over the orders 1..n, method1), Self-BLEU (= mBLEU-4) and div-1 / div-2
+  (distinct n-grams of a clip's captions / their words) as means over the clips, plus the per-key values.
+
+Not built: richness within groups, clap_score.py and specificity.py.
 """
 import numpy as np
 import torch
@@ -102,6 +111,83 @@ class Diversity(PackedScorer):
                                       ptr(out["summary"]), stream()), "ac_diversity_scores")
         return out
 
+    def score_group_rows(self, rows, group_off, start_idx, end_idx, canon, vocab_size):
+        """The dict of ``score_groups`` for one int32 plane ``rows`` (N, T) and int32 offsets ``group_off`` (G + 1,), both on
+        the device of ``canon`` (the offsets have been checked on the host: ``_group_offsets``)."""
+        lib = _lib.load()
+        dev = canon.device
+        N, T = rows.shape
+        G = group_off.numel() - 1
+        self._check_sizes(N, T)
+        if T == 0:
+            rows = rows.new_full((N, 1), int(end_idx))
+            T = 1
+        if rows.stride(1) != 1:
+            rows = rows.contiguous()
+        need = lib.ac_diversity_group_workspace_bytes(N, T, G)
+        if need < 0:
+            raise _lib.HipLibraryError(f"ac_diversity_group_workspace_bytes refused ({N} rows of {T} words in {G} groups)")
+        workspace = self._workspace_of(need, dev)
+        i32, f64 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float64)
+        out = {"self_bleu": torch.empty(N, **f64), "mbleu": torch.empty(N, 4, **f64),
+               "stats": torch.empty(N, 10, **i32), "sent_distinct": torch.empty(N, 4, **i32),
+               "group_totals": torch.empty(G, 5, **i32), "group_mean": torch.empty(G, 5, **f64),
+               "summary": torch.empty(5, **f64)}
+        check(lib.ac_diversity_group_scores(ptr(rows), rows.stride(0), N, T, int(start_idx), int(end_idx), ptr(canon),
+                                            int(vocab_size), ptr(group_off), G, ptr(workspace), workspace.numel(),
+                                            ptr(out["stats"]), ptr(out["sent_distinct"]), ptr(out["self_bleu"]),
+                                            ptr(out["mbleu"]), ptr(out["group_totals"]), ptr(out["group_mean"]),
+                                            ptr(out["summary"]), stream()), "ac_diversity_group_scores")
+        return out
+
+    @staticmethod
+    def _group_offsets(sizes):
+        """Row offsets (G + 1,) int32 on the host of groups of ``sizes`` rows.  ValueError for no group and for a group of
+        fewer than two rows: a caption alone in its group has no other caption to be scored against."""
+        sizes = [int(n) for n in sizes]
+        if not sizes:
+            raise ValueError("Diversity: no groups")
+        for g, n in enumerate(sizes):
+            if n < 2:
+                raise ValueError(f"Diversity: group {g} has {n} sentence(s): within a group a sentence is scored against "
+                                 f"the group's others, so every group needs two or more")
+        return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+    def score_groups(self, vocabulary, vocab_size, words, start_idx, end_idx, group_off=None):
+        """Diversity within groups: ``words`` (B, S, T) - B groups of S rows, e.g. the S sampled captions of each of B clips -
+        or (N, T) with ``group_off``, G + 1 ascending row offsets from 0 to N held on the host (a list, an array or a CPU
+        tensor; ragged groups).  A device tensor is scored where it lies; nothing is synchronised.  Returns device tensors
+        ``{"stats" (N, 10), "sent_distinct" (N, 4), "self_bleu" (N,), "mbleu" (N, 4), "group_totals" (G, 5) = words and
+        distinct n-grams of the group, "group_mean" (G, 5) = mean mBLEU-1..4 and mean Self-BLEU of the group, "summary" (5,)
+        = their means over the groups}`` with "the others" of a sentence being the other rows of its group.  ValueError
+        before any launch for a group of fewer than two rows and for the limits of ``score_ids``; a word id outside the
+        vocabulary on the device makes every float NaN and every integer -1."""
+        vocab_size = int(vocab_size)
+        self._canon(vocabulary, vocab_size)   # (a vocabulary that cannot be used is refused first)
+        w = torch.as_tensor(words)
+        if w.dim() == 3:
+            if group_off is not None:
+                raise ValueError("Diversity.score_groups: (B, S, T) words imply the groups; group_off goes with (N, T) words")
+            B, S, T = w.shape
+            offsets = self._group_offsets([S] * B)
+            w = w.reshape(B * S, T)
+        elif w.dim() == 2:
+            if group_off is None:
+                raise ValueError("Diversity.score_groups: (N, T) words need group_off, the G + 1 row offsets of the groups")
+            offsets = np.asarray(torch.as_tensor(group_off).cpu(), dtype=np.int64).reshape(-1)
+            if offsets.size < 2 or offsets[0] != 0 or offsets[-1] != w.shape[0]:
+                raise ValueError(f"Diversity.score_groups: group_off must run from 0 to {w.shape[0]} rows, got "
+                                 f"{offsets.tolist()[:8]}")
+            offsets = self._group_offsets(np.diff(offsets))
+        else:
+            raise ValueError(f"Diversity.score_groups: words must be (B, S, T) or (N, T) word ids, got {tuple(w.shape)}")
+        self._check_sizes(w.shape[0], w.shape[1])
+        self._refuse_foreign_ids(w, vocab_size, start_idx, end_idx)
+        dev = self._device_of([w])
+        canon_dev = self._canon(vocabulary, vocab_size, dev)
+        return self.score_group_rows(w.to(device=dev, dtype=torch.int32), torch.from_numpy(offsets).to(dev), start_idx,
+                                     end_idx, canon_dev, vocab_size)
+
     # ---- word ids ------------------------------------------------------------------------------------------------
     def score_ids(self, vocabulary, vocab_size, words, start_idx, end_idx):
         vocab_size = int(vocab_size)
@@ -174,4 +260,50 @@ class Diversity(PackedScorer):
             result["distinct_1_instance"], result["distinct_2_instance"] = d1, d2
         if train_captions is not None:
             result["novel"] = novel_share(sentences, train_captions)
+        return result
+
+    # ---- strings, within groups ------------------------------------------------------------------------------------
+    def _pack_groups(self, hypothesis):
+        """``{key: [sentence, ...]}`` as ``(keys, rows, group_off, start_idx, end_idx, vocab_size)``: the sentences of a key
+        are consecutive rows, the keys in the dict's order.  Every refusal of ``compute_group_score`` is raised here."""
+        if not isinstance(hypothesis, dict) or any(isinstance(g, str) for g in hypothesis.values()):
+            raise ValueError("Diversity.compute_group_score: {key: [sentence, ...]}")
+        keys = list(hypothesis)
+        groups = [list(hypothesis[k]) for k in keys]
+        for k, g in zip(keys, groups):
+            if len(g) < 2:
+                raise ValueError(f"Diversity.compute_group_score: key {k!r} has {len(g)} sentence(s): a caption is scored "
+                                 f"against the other captions of its key, so every key needs two or more")
+            if any(not isinstance(t, str) for t in g):
+                raise ValueError("Diversity.compute_group_score: sentences must be strings")
+        group_off = self._group_offsets([len(g) for g in groups])
+        rows, start_idx, end_idx, vocab_size = self._pack_sentences([t for g in groups for t in g])
+        return keys, rows, group_off, start_idx, end_idx, vocab_size
+
+    def compute_group_score(self, hypothesis):
+        """``{"mbleu_1" .. "mbleu_4", "self_bleu", "div_1", "div_2"}`` as means over the keys of ``hypothesis`` =
+        ``{key: [sentence, ...]}`` - each key's sentences scored against each other only - and ``"per_key"``: the same seven
+        numbers for every key.  div-n of a key: the distinct n-grams of its sentences over their words (NaN for a key
+        without a word).  ValueError for a key with fewer than two sentences, a sentence of more than ``MAX_HYP_WORDS``
+        words and the other limits of ``compute_score``."""
+        keys, rows, group_off, start_idx, end_idx, vocab_size = self._pack_groups(hypothesis)
+        canon = torch.arange(vocab_size, device="cuda", dtype=torch.int32)
+        out = self.score_group_rows(torch.from_numpy(rows).to(canon.device), torch.from_numpy(group_off).to(canon.device),
+                                    start_idx, end_idx, canon, vocab_size)
+        summary = out["summary"].cpu().tolist()
+        means = out["group_mean"].cpu().tolist()
+        totals = out["group_totals"].cpu().tolist()
+        names = ("mbleu_1", "mbleu_2", "mbleu_3", "mbleu_4", "self_bleu")
+        per_key = {}
+        for key, m, t in zip(keys, means, totals):
+            per_key[key] = dict(zip(names, m))
+            per_key[key]["div_1"] = t[1] / t[0] if t[0] else float("nan")
+            per_key[key]["div_2"] = t[2] / t[0] if t[0] else float("nan")
+        result = dict(zip(names, summary))
+        for name in ("div_1", "div_2"):
+            total = 0.0
+            for key in keys:          # added in the order of the keys
+                total += per_key[key][name]
+            result[name] = total / len(keys)
+        result["per_key"] = per_key
         return result

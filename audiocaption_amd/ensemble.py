@@ -86,6 +86,9 @@ class EnsembleModel(nn.Module):
     def forward(self, input_dict):
         if input_dict.get("mode") != "inference":
             raise NotImplementedError("EnsembleModel decodes only (mode='inference'); train the members one by one")
+        if input_dict.get("n_samples") is not None:
+            from .transformer_model import N_SAMPLES
+            raise NotImplementedError(f"EnsembleModel: {N_SAMPLES} is not built for ensembles")
         encs = [m.encoder(input_dict) for m in self.models]   # one after the other on the current stream
         args = {k: input_dict[k] for k in ("sample_method", "max_length", "temp", "beam_size", "n_best", "n_best_size", "seed")
                 if input_dict.get(k) is not None}

@@ -150,6 +150,9 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
     def scst(self, input_dict):
         from .train import _TrainBridge
         model = self.model
+        if input_dict.get("n_samples") is not None:
+            from .transformer_model import N_SAMPLES
+            raise NotImplementedError(f"ScstWrapper: {N_SAMPLES} is not built for the SCST rollout")
         for k in ("keys", "key2refs", "vocabulary", "scorer"):
             if input_dict.get(k) is None:
                 raise ValueError(f"ScstWrapper: input_dict[{k!r}] is required for mode 'train' (run.py:35-41)")

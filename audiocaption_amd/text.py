@@ -83,6 +83,8 @@ class DictTokenizer:
     # ---- ids -> text (what the model returns) --------------------------------------------------------------------------
     def decode(self, batch_token_ids):
         ids = np.asarray(batch_token_ids)
+        if ids.ndim == 3:        # (B, S, L), several captions per clip (``n_samples``, ``n_best``): a list of S strings per clip
+            return [self.decode(clip) for clip in ids]
         if ids.ndim == 1:
             ids = ids[None]
         ended = ids == self.eos
@@ -98,10 +100,14 @@ class DictTokenizer:
 
 
 def write_predictions(key2pred, path):
-    """The runners' prediction file: {"predictions": [{"filename": key, "tokens": caption}, ...]} (base.py:295-305)."""
+    """The runners' prediction file: {"predictions": [{"filename": key, "tokens": caption}, ...]} (base.py:295-305).  A clip
+    with several captions (a list of more than one string, what ``DictTokenizer.decode`` makes of a (B, S, L) array) keeps
+    them all: ``tokens`` is then the list that eval/diversity.py and diversity_instance.py read."""
     rows = []
     for key, pred in key2pred.items():
-        rows.append({"filename": key, "tokens": pred[0] if isinstance(pred, (list, tuple)) else pred})
+        if isinstance(pred, (list, tuple)):
+            pred = pred[0] if len(pred) == 1 else list(pred)
+        rows.append({"filename": key, "tokens": pred})
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump({"predictions": rows}, f, indent=4)

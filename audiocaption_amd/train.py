@@ -1018,6 +1018,9 @@ class TrainEngine:
         Returns ``logit`` (N, T, V), ``seq`` (int64) and ``seq_i32`` (N, T), ``sampled_logprob`` (N, T), all on the device."""
         import math
         model = self.model
+        if input_dict.get("n_samples") is not None:
+            from .transformer_model import N_SAMPLES
+            raise NotImplementedError(f"TrainEngine.rollout: {N_SAMPLES} is not built for the SCST rollout")
         if self.keyword:
             raise NotImplementedError("TrainEngine.rollout: the SCST rollout is not built for keyword conditioning "
                                       "(KeywordCondTransformerModel)")

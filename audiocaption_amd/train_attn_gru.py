@@ -174,6 +174,9 @@ class AttnGruTrainEngine(TrainEngine):
         Returns ``logit`` (N, T, V), ``seq`` (int64), ``seq_i32`` and ``sampled_logprob`` (N, T) on the device, and
         ``embed``, ``attn_weight``, ``state``, ``attn_emb_len`` as ``forward`` does; ``backward`` works as after ``forward``."""
         model = self.model
+        if input_dict.get("n_samples") is not None:
+            from .transformer_model import N_SAMPLES
+            raise NotImplementedError(f"AttnGruTrainEngine.rollout: {N_SAMPLES} is not built for the SCST rollout")
         T = int(input_dict.get("max_length", model.max_length))
         temp = float(input_dict.get("temp", 1.0))
         if T < 1:

@@ -309,21 +309,26 @@ class TransformerDecoder(BaseDecoder):
                   start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
                   ptr(st["unfinished_cnt"]), ptr(st["ws"]))
 
-    def _search_buffers(self, key, dev, B, Tm, A, max_length, segments=1):
-        """Static buffers of an on-device search (greedy or sampled) over B rows: inputs, workspace, outputs.  ``segments``
-        batches share the chain: one row of unfinished counts each (one segment: the plain ``(max_length,)`` vector)."""
+    def _search_buffers(self, key, dev, B, Tm, A, max_length, segments=1, samples_per_clip=1):
+        """Static buffers of an on-device search (greedy or sampled) over B clips: inputs, workspace, outputs.  ``segments``
+        batches share the chain: one row of unfinished counts each (one segment: the plain ``(max_length,)`` vector).
+        ``samples_per_clip`` decoder rows per clip: the inputs and the memory keep B rows, the workspace and every per-row
+        output have B * samples_per_clip, clip-major."""
         f32 = dict(device=dev, dtype=torch.float32)
-        ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), B, max_length)
+        R = B * samples_per_clip
+        ws_n = _lib.load().ac_trm_workspace_floats(ctypes.byref(self.weights()), R, max_length)
+        if ws_n <= 0:
+            raise _lib.HipLibraryError(f"ac_trm_workspace_floats rejected {R} rows of {max_length} positions")
         return {
             **self._extra_buffers(dev, B),
             "key": key, "graph": None, "uses": 0, "segments": segments,
             "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
             "memkv": torch.empty(self.nlayers, B * Tm, 2 * self.d_model, **f32),
             "tmp": torch.empty(B * Tm, self.d_model, **f32), "ws": torch.empty(ws_n, **f32),
-            "seq": torch.empty(B, max_length, device=dev, dtype=torch.int64),
-            "logit": torch.empty(B, max_length, self.vocab_size, **f32),
-            "sampled_logprob": torch.empty(B, max_length, **f32),
-            "embed": torch.empty(B, max_length, self.d_model, **f32),
+            "seq": torch.empty(R, max_length, device=dev, dtype=torch.int64),
+            "logit": torch.empty(R, max_length, self.vocab_size, **f32),
+            "sampled_logprob": torch.empty(R, max_length, **f32),
+            "embed": torch.empty(R, max_length, self.d_model, **f32),
             "unfinished_cnt": torch.empty((segments, max_length) if segments > 1 else (max_length,), device=dev,
                                           dtype=torch.int32),
         }
@@ -384,7 +389,8 @@ class TransformerDecoder(BaseDecoder):
         return self._search(self._greedy_state, key, parts, attn_emb_len, max_length, segments, more, extra,
                             lambda st: self._greedy_launch(st, max_length, start_idx, end_idx, pad_idx))
 
-    def _search(self, states, key, parts, attn_emb_len, max_length, segments, more, extra, launch, seed=None):
+    def _search(self, states, key, parts, attn_emb_len, max_length, segments, more, extra, launch, seed=None,
+                samples_per_clip=1):
         """The body of ``greedy`` and ``sample``: the state of ``key`` (``_search_buffers`` and what ``more()`` adds; batches of
         changing length keep 8 shapes), every batch of ``parts`` copied into its rows of the static input, ``launch(st)`` run or
         replayed (``search_state.run``), the outputs cloned out."""
@@ -392,7 +398,7 @@ class TransformerDecoder(BaseDecoder):
 
         def build():
             B, (Tm, A) = sum(p_.shape[0] for p_ in parts), parts[0].shape[1:]
-            return {**self._search_buffers(key, dev, B, Tm, A, max_length, segments), **more()}
+            return {**self._search_buffers(key, dev, B, Tm, A, max_length, segments, samples_per_clip), **more()}
         st = search_state.lookup(states, key, build, 8)
         r0 = 0
         for p_ in parts:
@@ -408,16 +414,23 @@ class TransformerDecoder(BaseDecoder):
             out["cluster_error"] = st["cluster_ws"][:1].clone()
         return out
 
-    def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params):
+    def _sample_launch(self, st, max_length, start_idx, end_idx, pad_idx, params, samples_per_clip=1):
         """Memory preparation + the whole sampled search on the current stream (capturable; the seed is read on the device)."""
         B, Tm, _ = st["attn_emb"].shape
         method, k, top_p, temp = params
         self._memory_launch(st)
+        if samples_per_clip != 1:      # the memory of the B clips once; samples_per_clip rows per clip read it
+            self._trm("sample_multi", None, ptr(st["memkv"]), ptr(st["mem_len"]), B, int(samples_per_clip), Tm, max_length,
+                      start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
+                      ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p),
+                      float(temp), ptr(st["seed"]))
+            return
         self._trm("sample", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, Tm, max_length, start_idx, end_idx, pad_idx,
                   ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]), ptr(st["unfinished_cnt"]),
                   ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st["seed"]))
 
-    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed, extra=None):
+    def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed, extra=None,
+               samples_per_clip=1):
         """On-device sampled search (base.py:152-170 with a sampling ``sample_method``; csrc/sample.hip).  ``method``, ``k``,
         ``top_p``, ``temp``: ``sampling.parse_sample_method``; ``seed``: 64-bit Philox key - row b of step t draws from
         counter (t, b), so a caption depends on (seed, row, step) only.  Returns what ``greedy`` returns.
@@ -425,17 +438,33 @@ class TransformerDecoder(BaseDecoder):
         Always the launch chain (the one-launch cluster form picks the argmax only).  Like ``greedy``, the launch sequence
         is captured per shape AND sampling parameters (second use) into a HIP graph over static buffers and replayed; the
         seed lives in a device word that is written before every launch or replay, so one graph serves every seed.
-        AUDIOCAPTION_DECODE_GRAPH=0 launches eagerly."""
+        AUDIOCAPTION_DECODE_GRAPH=0 launches eagerly.
+
+        ``samples_per_clip`` = S > 1: S captions per clip from ONE memory projection (``ac_trm_sample_multi``).  The outputs
+        have B * S rows, clip-major (row r is caption r % S of clip r // S), and row r of step t draws from counter (t, r):
+        the result of this call on ``attn_emb.repeat_interleave(S, 0)`` with the same seed, without projecting a clip's
+        memory S times.  S is part of the state key: a graph captured for one S is never replayed for another; S = 1 is
+        the call above, with its key and graph."""
         from .sampling import seed_word
         dev, (B, Tm, _) = attn_emb.device, attn_emb.shape
         params = (int(method), int(k), float(top_p), float(temp))
+        if isinstance(samples_per_clip, bool) or not isinstance(samples_per_clip, int) or samples_per_clip < 1:
+            raise ValueError(f"samples_per_clip must be an int >= 1, got {samples_per_clip!r}")
         key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key()) + self._extra_key(extra)
+        if samples_per_clip != 1:
+            if extra is not None:
+                raise NotImplementedError(f"{type(self).__name__}: samples_per_clip (several sampled captions per clip) is "
+                                          "not built for a conditioned decoder")
+            if B * samples_per_clip * (max_length + 1) >= 2 ** 31:
+                raise ValueError(f"samples_per_clip: {B} clips x {samples_per_clip} captions x {max_length} positions exceed "
+                                 "the search's row index")
+            key += (("samples_per_clip", samples_per_clip),)
         if getattr(self, "_sample_state", None) is None:
             self._sample_state = {}
         return self._search(self._sample_state, key, [attn_emb], attn_emb_len, max_length, 1,
                             lambda: {"seed": torch.zeros(1, device=dev, dtype=torch.int64)}, extra,
-                            lambda st: self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params),
-                            seed=seed_word(seed))
+                            lambda st: self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params, samples_per_clip),
+                            seed=seed_word(seed), samples_per_clip=samples_per_clip)
 
     def beam_step(self, memkv, mem_len, B, beam, Tm, max_length, t, temp, tokens, mask, cum, ws, kwp=None):
         """One beam-search step outside a search state.  ``kwp`` (B, d): the clips' projected keywords, for a decoder that

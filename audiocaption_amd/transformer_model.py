@@ -41,6 +41,9 @@ class CaptionMetaMixin:
         cls.pad_idx = pad_idx
 
 
+N_SAMPLES = "n_samples (several sampled captions per clip from one encoder pass)"   # how the refusals name the feature
+
+
 class CaptionModel(nn.Module, CaptionMetaMixin):
 
     compatible_decoders = (TransformerDecoder,)
@@ -66,6 +69,7 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             # call; ``logit`` comes back attached to autograd by a single bridge node (audiocaption_amd/train.py)
             from .train import train_forward
             return train_forward(self, input_dict)
+        self._check_n_samples(input_dict)      # refused on the host, before the encoder runs
         encoder_output_dict = self.encoder(input_dict)
         output = self.forward_decoder(input_dict, encoder_output_dict)
         flags = _device_flags(output)
@@ -109,10 +113,18 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             raise _lib.HipLibraryError("f16_overflow raised by a tier without fp16 activations")
         return self.forward(dict(input_dict, conv_algo="bf16x3"))
 
+    def _check_n_samples(self, input_dict):
+        """``input_dict["n_samples"]``, several sampled captions per clip from one encoder pass, is built for
+        ``TransformerModel`` (which overrides this): NotImplementedError naming the feature everywhere else."""
+        if input_dict.get("n_samples") is not None:
+            raise NotImplementedError(f"{type(self).__name__}: {N_SAMPLES} is built for TransformerModel only")
+        return None
+
     def forward_decoder(self, input_dict, encoder_output_dict):
         if input_dict["mode"] == "train":
             raise NotImplementedError("mode='train' is handled by CaptionModel.forward as one fused step")
         elif input_dict["mode"] == "inference":
+            self._check_n_samples(input_dict)
             output = self.inference_forward(self._inference_dict(input_dict, encoder_output_dict))
         else:
             raise Exception("mode should be either 'train' or 'inference'")
@@ -133,6 +145,8 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             forward_dict["seed"] = input_dict["seed"]
         if input_dict.get("_seq_on_device"):      # ScstWrapper's baseline: the device copy of the words as well ("seq_dev")
             forward_dict["_seq_on_device"] = True
+        if input_dict.get("n_samples") is not None:    # sampling: this many captions per clip (checked by _check_n_samples)
+            forward_dict["n_samples"] = input_dict["n_samples"]
         forward_dict.update(encoder_output_dict)
         return forward_dict
 
@@ -277,6 +291,8 @@ class TransformerModel(CaptionModel):
         single requests are not delayed.  True / "1" always waits for a full group, False / "0" never.  A batch without a
         partner is decoded on its own as soon as its ``result()`` is asked for."""
         method = input_dict.get("sample_method", "greedy")
+        if input_dict.get("n_samples") is not None:
+            raise NotImplementedError(f"forward_async: {N_SAMPLES} is not built for it; use model(input_dict)")
         if input_dict.get("mode") != "inference" or method not in ("greedy", "beam"):
             raise NotImplementedError("forward_async: greedy or beam inference only; use model(input_dict) otherwise")
         if method == "beam":
@@ -545,6 +561,20 @@ class TransformerModel(CaptionModel):
         ``decoder.greedy`` / ``decoder.sample`` that carries it (none here)."""
         return {}
 
+    def _check_n_samples(self, input_dict):
+        """``input_dict["n_samples"]`` as an int (None when the key is absent).  ValueError, before anything is launched, for
+        a value that is not an int >= 1 and for ``greedy`` / ``beam``, which have one answer per clip."""
+        n = input_dict.get("n_samples")
+        if n is None:
+            return None
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n_samples must be an int >= 1, got {n!r}")
+        method = input_dict.get("sample_method", "greedy")
+        if method in ("greedy", "beam"):
+            raise ValueError(f"n_samples: sample_method={method!r} has one caption per clip; {N_SAMPLES} takes a sampling "
+                             "sample_method ('sample', 'top<k>', 'top<p>', 'gumbel')")
+        return n
+
     # ---- greedy (base.py:152-218) -----------------------------------------------------------------
     def greedy_search(self, input_dict):
         if input_dict.get("temp", 1.0) != 1.0:
@@ -577,14 +607,30 @@ class TransformerModel(CaptionModel):
         ``torch.manual_seed`` makes runs reproducible as in the reference.  Gumbel-max is exactly a categorical draw from
         softmax(lp), so "gumbel" takes the same one-uniform inverse-CDF draw as plain sampling at temp 1 (the stored
         ``sampled_logprob`` is lp[w], per row - the reference's gather keeps a trailing dimension that fails for batches
-        larger than one)."""
+        larger than one).
+
+        ``input_dict["n_samples"]`` = S: S captions per clip from this one encoder pass and ONE projection of the audio memory
+        (``TransformerDecoder.sample(samples_per_clip=S)``): ``seq`` and ``sampled_logprob`` (B, S, max_length) on the CPU - the
+        shape ``n_best`` uses -, ``logit`` (B, S, max_length, V), ``embed`` (B, S, max_length, d); caption s of clip b draws
+        with Philox row b * S + s.  With ``_seq_on_device`` also ``seq_dev`` (B, S, max_length) on the device, what
+        ``Diversity.score_groups`` takes as it is."""
         from .sampling import draw_seed, parse_sample_method
+        S = self._check_n_samples(input_dict)
         method, k, top_p, temp = parse_sample_method(input_dict["sample_method"], self.vocab_size, input_dict.get("temp", 1.0))
         seed = input_dict.get("seed")
         seed = draw_seed() if seed is None else int(seed)
+        more = {} if S is None else {"samples_per_clip": S}
         res = self.decoder.sample(input_dict["attn_emb"], input_dict["attn_emb_len"], int(input_dict["max_length"]),
                                   self.start_idx, self.end_idx, self.pad_idx, method, k, top_p, temp, seed,
-                                  **self._search_kwargs(input_dict))
+                                  **self._search_kwargs(input_dict), **more)
+        if S is not None:
+            B = input_dict["attn_emb"].shape[0]
+            res = {k_: (v if k_ == "unfinished_cnt" else v.view(B, S, *v.shape[1:])) for k_, v in res.items()}
+            out = {"seq": res["seq"].cpu(), "logit": res["logit"], "sampled_logprob": res["sampled_logprob"].cpu(),
+                   "embed": res["embed"], "unfinished_cnt": res["unfinished_cnt"]}
+            if input_dict.get("_seq_on_device"):
+                out["seq_dev"] = res["seq"]
+            return out
         return {
             "seq": res["seq"].cpu(),                          # CPU as in base.py:122
             "logit": res["logit"],
@@ -708,7 +754,8 @@ class KeywordCondTransformerModel(TransformerModel):
     Inference through the blocking ``model(input_dict)``: greedy, beam (with ``n_best`` / ``n_best_size``) and every sampling
     method of ``sampling.parse_sample_method``; ``mode="train"`` through ``train.train_forward`` (the autograd bridge).
     Not built (NotImplementedError): ``forward_async``, membership in an ``EnsembleModel``, ``ScstWrapper`` /
-    ``TrainEngine.rollout``, the fused ``TrainEngine.step`` (also with ``kd=``), the encoder-KD wrappers, and ``dbs``."""
+    ``TrainEngine.rollout``, the fused ``TrainEngine.step`` (also with ``kd=``), the encoder-KD wrappers, ``n_samples``, and
+    ``dbs``."""
 
     compatible_decoders = (KeywordProbTransformerDecoder,)
 
@@ -726,6 +773,11 @@ class KeywordCondTransformerModel(TransformerModel):
     def forward_async(self, input_dict, pair=None):
         raise NotImplementedError("KeywordCondTransformerModel: forward_async (shared greedy chains, deferred beam searches) is "
                                   "not built for keyword conditioning; use model(input_dict)")
+
+    def _check_n_samples(self, input_dict):
+        if input_dict.get("n_samples") is not None:
+            raise NotImplementedError(f"KeywordCondTransformerModel: {N_SAMPLES} is not built for keyword conditioning")
+        return None
 
     def _search_kwargs(self, input_dict):
         return {"keyword": check_keyword(input_dict.get("keyword"), input_dict["attn_emb"].shape[0],

@@ -388,6 +388,20 @@ int ac_trm_sample(const ac_trm_weights* w, const float* memkv, const int* mem_le
                   float* embed, int* unfinished_cnt, float* ws, int method, int k, float top_p, float temp,
                   const uint64_t* seed_dev, void* stream);
 
+/* Several sampled captions per clip from ONE memory projection: ac_trm_sample over R = B * samples_per_clip rows, clip-major -
+ * row r belongs to clip r / samples_per_clip and reads ITS memory K / V and length, as the rows of a beam do.  memkv (from
+ * ac_trm_memory over the B clips) and mem_len have B entries; seq, logit, logprob and embed have R rows; unfinished_cnt
+ * [max_len] counts over all R rows (one segment: the search ends when every row has emitted <end>, a row that has ended
+ * emits end_idx while its siblings go on).  Row r of step t draws with counter (t, r): by definition the result of
+ * ac_trm_sample on the batch with every clip repeated samples_per_clip times and the same seed - bit for bit where the
+ * memory projection takes the same kernel for B * Tm rows as for R * Tm (ac_linear: up to 128 rows / beyond), to the
+ * last bits of the logits otherwise.  samples_per_clip == 1 is ac_trm_sample.  ws: ac_trm_workspace_floats(w, R, max_len)
+ * floats.  AC_ERR_ARG, nothing launched: samples_per_clip < 1, R * (max_len + 1) >= 2^31, and what ac_trm_sample refuses. */
+int ac_trm_sample_multi(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int samples_per_clip,
+                        int Tm, int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
+                        float* logprob, float* embed, int* unfinished_cnt, float* ws, int method, int k, float top_p,
+                        float temp, const uint64_t* seed_dev, void* stream);
+
 /* Decoder forward on given tokens (teacher forcing / plugin call, transformer_decoder.py:80-103):
  * tokens [N][T] int32; key_mask [N][T] uint8 (1 = masked key, the reference's cap_padding_mask /
  * tgt_key_padding_mask, transformer_model.py:22-23,55) or NULL.  embed [N][T][d], logit [N][T][V]. */
@@ -973,6 +987,33 @@ long ac_diversity_workspace_bytes(int N, int T);
 int ac_diversity_scores(const int* hyp, long hyp_ld, int N, int T, int start_idx, int end_idx, const int* canon,
                         int vocab_size, void* workspace, long workspace_bytes, int* stats, int* sent_distinct, int* totals,
                         double* self_bleu, double* summary, void* stream);
+/* ---- Diversity WITHIN groups of captions (csrc/diversity.hip): the captions of one clip scored against each other ------
+ * ac_diversity_scores with one more input: group_off, device int32 [G + 1], 0 = group_off[0] <= ... <= group_off[G] = N;
+ * rows [group_off[g], group_off[g + 1]) are group g (ragged groups allowed).  "The others" of sentence i are the other
+ * sentences OF ITS GROUP, in num[n], in ref_len and everywhere else; the table of distinct n-grams is still one table for
+ * the call, with the group as a part of an n-gram's identity: the same words in two groups hold two slots and never count
+ * as each other's references.  hyp, T, the sentence rule, canon and the out-of-range rule as in ac_diversity_scores.
+ * Outputs, all in device memory:
+ *   stats         int32 [N][10], sent_distinct int32 [N][4], self_bleu f64 [N]   as defined for ac_diversity_scores
+ *   mbleu         f64 [N][4]    column k - 1 = nltk's sentence_bleu(the others, sentence i, weights 1/k each over the orders
+ *                               1 .. k, smoothing method1): 0 when num[1] == 0, else bp * exp(sum_{n <= k} (1 / k) * log(p[n]))
+ *                               over the SAME num / den / ref_len integers, so mbleu[i][3] == self_bleu[i] bit for bit
+ *   group_totals  int32 [G][5]  = words of the group, distinct n-grams of the group for n = 1 .. 4 (div-n of a clip is
+ *                               group_totals[g][n] / group_totals[g][0])
+ *   group_mean    f64 [G][5]    = mean of mbleu[.][0 .. 3] over the group's sentences, then their mean Self-BLEU
+ *   summary       f64 [5]       = the means of group_mean over the groups, in the order of the groups
+ * Richness is not part of the grouped call (its document frequencies are a property of the pooled corpus).
+ * Every group needs two rows or more (a single sentence has no "other"): G < 1 or G > N / 2 is AC_ERR_ARG, and callers that
+ * hold the offsets on the host check them there (audiocaption_amd/diversity.py).  On the device the offsets are
+ * range-checked before they index anything: offsets that are not ascending from 0 to N make every output NaN / -1; a group
+ * of fewer than two rows gets NaN / -1 for itself and its rows (and so for summary), and nothing outside it is read.
+ * workspace: 256-byte aligned, ac_diversity_group_workspace_bytes(N, T, G) bytes.  Integer counts, float64 in closed formulas
+ * and sums of fixed order, every probe bounded by the table size: bitwise repeatable.  AC_ERR_ARG: nothing launched. */
+long ac_diversity_group_workspace_bytes(int N, int T, int G);
+int ac_diversity_group_scores(const int* hyp, long hyp_ld, int N, int T, int start_idx, int end_idx, const int* canon,
+                              int vocab_size, const int* group_off, int G, void* workspace, long workspace_bytes,
+                              int* stats, int* sent_distinct, double* self_bleu, double* mbleu, int* group_totals,
+                              double* group_mean, double* summary, void* stream);
 /* ac_gru_layer that also keeps (r, z, n, W_hn h + b_hn) per (clip, step, direction): save [B][T][2][4H]. */
 int ac_gru_layer_train(const float* gx, const float* whhT, const float* bhh, const int* lens, float* out, float* save,
                        int B, int T, int hidden, void* stream);
