@@ -13,6 +13,7 @@ from .attn_model import ConditionalSeq2SeqAttnModel, Seq2SeqAttnModel, TemporalS
 from .loss import SpecificityLossWrapper
 from .sed_model import Cnn8rnnSedModel
 from .ensemble import EnsembleModel
+from .logit_rules import LogitRules
 from .rl_model import ScstWrapper
 from .cider import Cider
 from .caption_metrics import Bleu, Rouge
@@ -25,4 +26,4 @@ __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "Tran
            "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "ConditionalBahAttnDecoder", "SpecificityBahAttnDecoder",
            "ConditionalSeq2SeqAttnModel", "SpecificityLossWrapper", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
            "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config",
-           "KeywordProbTransformerDecoder", "KeywordCondTransformerModel", "cnn14rnn_keyword_trm_config"]
+           "KeywordProbTransformerDecoder", "KeywordCondTransformerModel", "cnn14rnn_keyword_trm_config", "LogitRules"]

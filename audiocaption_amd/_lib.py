@@ -37,6 +37,12 @@ class AcTrmKeyword(ctypes.Structure):
     _fields_ = [("kwp", ctypes.c_void_p), ("ln_w", ctypes.c_void_p), ("ln_b", ctypes.c_void_p), ("row_div", ctypes.c_int32)]
 
 
+class AcLogitRules(ctypes.Structure):
+    """ac_logit_rules: the constraints a search applies to every step's logits (csrc/logit_rules.hip)."""
+    _fields_ = [("repetition_penalty", ctypes.c_float), ("no_repeat_ngram", ctypes.c_int32), ("min_length", ctypes.c_int32),
+                ("end_idx", ctypes.c_int32), ("n_bad", ctypes.c_int32), ("bad_words", ctypes.c_void_p)]
+
+
 class AcBahWeights(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "emb_dim", "d_model", "attn_size", "attn_emb_dim", "fc_emb_dim", "vocab", "n_tags", "variant")] + [
@@ -119,6 +125,11 @@ SIGNATURES = {
     "ac_ens_greedy_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_sample_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_beam_step_select": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    # repetition and word constraints (csrc/logit_rules.hip); `rules` is ctypes.byref(AcLogitRules)
+    "ac_logit_rules_apply": (_I, [_P, _L, _P, _L, _I, _I, _P, _L, _I, _P, _P]),
+    "ac_trm_search_rules": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _L,
+                                 _P]),
+    "ac_trm_beam_step_rules": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # Bahdanau-attention GRU decoder (csrc/attn_gru.hip)
     "ac_bah_workspace_floats": (_L, [_BP, _I, _I, _I, _I]),
     "ac_bah_memory": (_I, [_BP, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -18,6 +18,7 @@
 // Projections run on the f32 matrix cores through ac_linear; softmax / LayerNorm reductions are
 // 64-lane wavefront shuffles.
 #include "ac_common.h"
+#include "ac_logit_rules.h"
 #include "ac_sample.h"
 #include "ac_beam.h"
 #include "../../include/audiocaption_hip.h"
@@ -1660,8 +1661,11 @@ extern "C" long ac_trm_workspace_floats(const ac_trm_weights* w, int rows, int m
 static int trm_search(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int segments, int Tm,
                       int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
                       float* embed, int* unfinished_cnt, float* ws_base, const SampleParams* sp, void* stream,
-                      const ac_trm_keyword* kw = nullptr, int row_div = 1) {
+                      const ac_trm_keyword* kw = nullptr, int row_div = 1, const ac_logit_rules* rules = nullptr,
+                      float* plane = nullptr, long ld_plane = 0) {
   AC_TRY(check_weights(w));
+  // rules: every step's pick reads the constrained copy of the step's logits in `plane` (csrc/logit_rules.hip)
+  if (rules && (ac_logit_rules_check(rules, w->vocab) != AC_OK || !plane || ld_plane < w->vocab)) return AC_ERR_ARG;
   if (!memkv || !mem_len || !seq || !logit || !logprob || !embed || !unfinished_cnt || !ws_base) return AC_ERR_ARG;
   if (B <= 0 || Tm <= 0 || Tm > MAX_KEYS || max_len <= 0 || max_len > w->max_pos) return AC_ERR_ARG;
   if (segments <= 0 || B % segments || row_div <= 0 || B % row_div) return AC_ERR_ARG;
@@ -1683,9 +1687,16 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
                         &fin, s, live, kw));
     AC_TRY(classifier_step(w, fin, B, embed + (size_t)t * d, (long)max_len * d, logit + (size_t)t * V,
                            (long)max_len * V, s, live));
+    const float* picked = logit + (size_t)t * V;   // what the pick reads: the step's logits, or their constrained copy
+    long ld_picked = (long)max_len * V;
+    if (rules) {
+      AC_TRY(ac_logit_rules_launch(picked, ld_picked, plane, ld_plane, B, V, ws.tok, max_len + 1, t, rules, unfinished_cnt,
+                                   live.seg_rows, max_len, s));
+      picked = plane; ld_picked = ld_plane;
+    }
     if (sp) {
       SampleParams q = *sp;
-      q.logit = logit + (size_t)t * V; q.ldl = (long)max_len * V; q.rows = B; q.V = V; q.t = t; q.word = nullptr;
+      q.logit = picked; q.ldl = ld_picked; q.rows = B; q.V = V; q.t = t; q.word = nullptr;
       q.logprob = logprob + t; q.ld_lp = max_len;
       q.seq = seq; q.max_len = max_len; q.end_idx = end_idx; q.pad_idx = pad_idx;
       q.tok = ws.tok; q.mask = ws.mask; q.unfinished = ws.unfinished; q.cnt = unfinished_cnt; q.seg_rows = live.seg_rows;
@@ -1693,7 +1704,7 @@ static int trm_search(const ac_trm_weights* w, const float* memkv, const int* me
       continue;
     }
     PickParams p;
-    p.logit = logit + (size_t)t * V; p.ldl = (long)max_len * V;
+    p.logit = picked; p.ldl = ld_picked;
     p.V = V; p.t = t; p.max_len = max_len; p.end_idx = end_idx; p.pad_idx = pad_idx;
     p.seq = seq; p.logprob = logprob; p.tok = ws.tok; p.mask = ws.mask; p.unfinished = ws.unfinished;
     p.cnt = unfinished_cnt; p.seg_rows = live.seg_rows;
@@ -1788,9 +1799,11 @@ extern "C" int ac_trm_step_logits(const ac_trm_weights* w, const float* memkv, c
 
 static int beam_step(const ac_trm_weights* w, const ac_trm_keyword* kw, const float* memkv, const int* mem_len, int B,
                      int beam, int Tm, int max_len, int t, float temp, const int* tokens, const unsigned char* key_mask,
-                     const float* cum_logprob, float* top_val, int* top_idx, float* ws_base, void* stream) {
+                     const float* cum_logprob, float* top_val, int* top_idx, float* ws_base, void* stream,
+                     const ac_logit_rules* rules = nullptr, float* plane = nullptr) {
   AC_TRY(check_weights(w));
   if (!memkv || !mem_len || !tokens || !cum_logprob || !top_val || !top_idx || !ws_base) return AC_ERR_ARG;
+  if (rules && (ac_logit_rules_check(rules, w->vocab) != AC_OK || !plane)) return AC_ERR_ARG;
   if (B <= 0 || beam <= 0 || beam > 64 || Tm <= 0 || Tm > MAX_KEYS || t < 0 || t >= max_len) return AC_ERR_ARG;
   if (max_len > w->max_pos || !(temp > 0.f)) return AC_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -1800,20 +1813,25 @@ static int beam_step(const ac_trm_weights* w, const ac_trm_keyword* kw, const fl
   AC_TRY(decoder_step(w, memkv, mem_len, R, beam, Tm, max_len, t, tokens, key_mask, max_len + 1,
                       ws.cache[t & 1], ws, &fin, s, Live(), kw));
   AC_TRY(classifier_step(w, fin, R, nullptr, 0, ws.lg, V, s, Live(), ws.att));   // ws.att: dead once the last layer has consumed it
+  float* lg = ws.lg;   // the rows the scores are formed from: the step's logits, or their constrained copy
+  if (rules) {
+    AC_TRY(ac_logit_rules_launch(ws.lg, V, plane, V, R, V, tokens, max_len + 1, t, rules, nullptr, 1, 0, s));
+    lg = plane;
+  }
   static const bool two_kernels = getenv("AUDIOCAPTION_BEAM_TOPK") && !strcmp(getenv("AUDIOCAPTION_BEAM_TOPK"), "scan");
   if (beam <= 8 && V <= 8192 && !two_kernels) {
     // scores + per-row candidates in one pass over registers, then a one-wave merge per clip; the candidates (2 x R x
     // beam words) go into the QKV scratch of the decoder step, which is dead until the next step starts
     float* cand_val = ws.qkv;
     int* cand_idx = (int*)(cand_val + (size_t)R * beam);
-    if (V <= 5120) hipLaunchKernelGGL(beam_row_topk_kernel<20>, dim3(R), dim3(256), 0, s, ws.lg, cum_logprob, temp, beam, V, cand_val, cand_idx);
-    else hipLaunchKernelGGL(beam_row_topk_kernel<32>, dim3(R), dim3(256), 0, s, ws.lg, cum_logprob, temp, beam, V, cand_val, cand_idx);
+    if (V <= 5120) hipLaunchKernelGGL(beam_row_topk_kernel<20>, dim3(R), dim3(256), 0, s, lg, cum_logprob, temp, beam, V, cand_val, cand_idx);
+    else hipLaunchKernelGGL(beam_row_topk_kernel<32>, dim3(R), dim3(256), 0, s, lg, cum_logprob, temp, beam, V, cand_val, cand_idx);
     AC_TRY(ac_check_launch());
     hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(64), 0, s, cand_val, cand_idx, beam, t == 0 ? 1 : beam, top_val, top_idx);
     return ac_check_launch();
   }
-  float* lp = ws.lg;  // in place: every element is read before it is written by the same thread
-  hipLaunchKernelGGL(beam_logprob_kernel, dim3(R), dim3(256), 0, s, ws.lg, cum_logprob, temp, lp, V);
+  float* lp = lg;  // in place: every element is read before it is written by the same thread
+  hipLaunchKernelGGL(beam_logprob_kernel, dim3(R), dim3(256), 0, s, lg, cum_logprob, temp, lp, V);
   AC_TRY(ac_check_launch());
   hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(256), 0, s, lp, beam, t == 0 ? 1 : beam, V, top_val,
                      top_idx);
@@ -1826,6 +1844,31 @@ extern "C" int ac_trm_beam_step(const ac_trm_weights* w, const float* memkv, con
                                 int* top_idx, float* ws_base, void* stream) {
   return beam_step(w, nullptr, memkv, mem_len, B, beam, Tm, max_len, t, temp, tokens, key_mask, cum_logprob, top_val, top_idx,
                    ws_base, stream);
+}
+
+// ---- the same searches with the rules of csrc/logit_rules.hip between a step's logits and its pick -------------------------
+extern "C" int ac_trm_search_rules(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
+                                   int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit,
+                                   float* logprob, float* embed, int* unfinished_cnt, float* ws_base, int method, int k,
+                                   float top_p, float temp, const uint64_t* seed_dev, const ac_logit_rules* rules,
+                                   float* plane, long ld_plane, void* stream) {
+  // the row indices of the search (tokens, masks, the initialisation) are ints
+  if (!rules || R <= 0 || max_len <= 0 || (long)R * ((long)max_len + 1) > 0x7fffffffL) return AC_ERR_ARG;
+  if (rules->end_idx != end_idx) return AC_ERR_ARG;
+  SampleParams sp = {};
+  sp.method = method; sp.k = k; sp.top_p = top_p; sp.temp = temp; sp.seed = seed_dev;
+  return trm_search(w, memkv, mem_len, R, 1, Tm, max_len, start_idx, end_idx, pad_idx, seq, logit, logprob, embed,
+                    unfinished_cnt, ws_base, method == AC_SEARCH_GREEDY ? nullptr : &sp, stream, nullptr, row_div, rules, plane,
+                    ld_plane);
+}
+
+extern "C" int ac_trm_beam_step_rules(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam, int Tm,
+                                      int max_len, int t, float temp, const int* tokens, const unsigned char* key_mask,
+                                      const float* cum_logprob, float* top_val, int* top_idx, float* ws_base,
+                                      const ac_logit_rules* rules, float* plane, void* stream) {
+  if (!rules) return AC_ERR_ARG;
+  return beam_step(w, nullptr, memkv, mem_len, B, beam, Tm, max_len, t, temp, tokens, key_mask, cum_logprob, top_val, top_idx,
+                   ws_base, stream, rules, plane);
 }
 
 // ---- keyword-conditioned decoder (KeywordProbTransformerDecoder): the same searches with the keyword operands --------------

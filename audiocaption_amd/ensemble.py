@@ -32,6 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import logit_rules
 from . import search_state
 from ._lib import check, ptr, stream
 from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder
@@ -89,6 +90,7 @@ class EnsembleModel(nn.Module):
         if input_dict.get("n_samples") is not None:
             from .transformer_model import N_SAMPLES
             raise NotImplementedError(f"EnsembleModel: {N_SAMPLES} is not built for ensembles")
+        logit_rules.refuse(input_dict, "EnsembleModel", "a single TransformerModel's blocking model(input_dict)")
         encs = [m.encoder(input_dict) for m in self.models]   # one after the other on the current stream
         args = {k: input_dict[k] for k in ("sample_method", "max_length", "temp", "beam_size", "n_best", "n_best_size", "seed")
                 if input_dict.get(k) is not None}

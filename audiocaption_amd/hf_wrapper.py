@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import logit_rules
 from .attn_model import TemporalSeq2SeqAttnModel
 from .cnn_encoder import Cnn14Encoder
 from .config import merge_load_state_dict
@@ -65,14 +66,23 @@ except Exception:   # noqa: BLE001
             pass
 
 
-def _input_dict(device, audio, audio_length, sample_method, beam_size, max_length, temp):
+def _input_dict(device, audio, audio_length, sample_method, beam_size, max_length, temp, rules=None):
+    """``rules``: the repetition and word constraints of the call (``logit_rules.KEYS``), passed on when they are set."""
     if not isinstance(audio, torch.Tensor):
         audio = torch.as_tensor(np.asarray(audio))
     d = {"wav": audio.to(device), "wav_len": audio_length, "specaug": False, "mode": "inference",
          "sample_method": sample_method, "max_length": max_length, "temp": temp}
     if sample_method == "beam":
         d["beam_size"] = beam_size
+    d.update(rules or {})
     return d
+
+
+def _rules(repetition_penalty, no_repeat_ngram_size, bad_words, min_length):
+    """The four controls of a call as ``input_dict`` keys; the defaults (off) add none."""
+    given = {"repetition_penalty": repetition_penalty, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
+             "min_length": min_length}
+    return {k: v for k, v in given.items() if logit_rules.first_active_key({k: v}) is not None}
 
 
 class Effb2TrmConfig(PretrainedConfig):
@@ -152,9 +162,12 @@ class Effb2TrmCaptioningModel(PreTrainedModel):
         return merge_load_state_dict(state_dict, self, output_fn)
 
     @torch.no_grad()
-    def forward(self, audio, audio_length, sample_method="beam", beam_size=3, max_length=20, temp=1.0):
-        return self.model(_input_dict(self.device, audio, audio_length, sample_method, beam_size, max_length,
-                                      temp))["seq"].cpu()
+    def forward(self, audio, audio_length, sample_method="beam", beam_size=3, max_length=20, temp=1.0,
+                repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words=(), min_length=0):
+        """The last four: the repetition and word constraints of ``logit_rules`` (default off)."""
+        rules = _rules(repetition_penalty, no_repeat_ngram_size, bad_words, min_length)
+        return self.model(_input_dict(self.device, audio, audio_length, sample_method, beam_size, max_length, temp,
+                                      rules))["seq"].cpu()
 
 
 class Cnn14RnnTempAttnGruConfig(PretrainedConfig):
@@ -245,7 +258,10 @@ class Cnn14RnnTempAttnGruModel(PreTrainedModel):
         return sed_tag.cpu().long()
 
     @torch.no_grad()
-    def forward(self, audio, audio_length, temporal_tag=None, sample_method="beam", beam_size=3, max_length=20, temp=1.0):
+    def forward(self, audio, audio_length, temporal_tag=None, sample_method="beam", beam_size=3, max_length=20, temp=1.0,
+                repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words=(), min_length=0):
+        rules = _rules(repetition_penalty, no_repeat_ngram_size, bad_words, min_length)
+        logit_rules.refuse(rules, type(self).__name__)     # before the tagger runs: the attention-GRU search has no rules
         d = _input_dict(self.device, audio, audio_length, sample_method, beam_size, max_length, temp)
         d["temporal_tag"] = self.temporal_tags(d["wav"], temporal_tag)
         return self.cap_model(d)["seq"].cpu()
@@ -269,6 +285,11 @@ class CaptioningModel(nn.Module):
         self.config = config or CaptioningConfig(vocab_size=model.vocab_size)
 
     @torch.no_grad()
-    def forward(self, audio, audio_length, sample_method="beam", beam_size=3, max_length=20, temp=1.0):
+    def forward(self, audio, audio_length, sample_method="beam", beam_size=3, max_length=20, temp=1.0,
+                repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words=(), min_length=0):
+        """The last four: the repetition and word constraints of ``logit_rules`` (default off; a model that does not build
+        them raises NotImplementedError naming the key)."""
         device = next(self.model.parameters()).device
-        return self.model(_input_dict(device, audio, audio_length, sample_method, beam_size, max_length, temp))["seq"].cpu()
+        rules = _rules(repetition_penalty, no_repeat_ngram_size, bad_words, min_length)
+        return self.model(_input_dict(device, audio, audio_length, sample_method, beam_size, max_length, temp,
+                                      rules))["seq"].cpu()

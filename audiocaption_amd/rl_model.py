@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import logit_rules
 from ._lib import check, ptr, stream
 from .cider import Cider
 from .transformer_model import CaptionMetaMixin, KeywordCondTransformerModel, TransformerModel
@@ -131,7 +132,9 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
         """The greedy baseline: the inference path in eval mode without gradients.  Returns its words as the inference
         path hands them out (CPU, int64) and the decoder's device copy of them as int32."""
         model = self.model
-        d = {k: v for k, v in input_dict.items() if k not in ("seed", "dropout_seed", "_scst_words", "_cnn_attn")}
+        # (the rollout and the baseline stay unconstrained: the repetition and word constraints are not part of the policy)
+        d = {k: v for k, v in input_dict.items()
+             if k not in ("seed", "dropout_seed", "_scst_words", "_cnn_attn") + logit_rules.KEYS}
         d.update(mode="inference", sample_method="greedy", max_length=max_length, _seq_on_device=True)
         model.eval()
         with torch.no_grad():

@@ -305,9 +305,31 @@ class TransformerDecoder(BaseDecoder):
                       start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
                       ptr(st["embed"]), ptr(st["unfinished_cnt"]), ptr(st["cluster_ws"]), int(st["early_stop"]))
             return
+        if st.get("rules") is not None:
+            self._rules_search_launch(st, B, 1, max_length, start_idx, end_idx, pad_idx, None)
+            return
         self._trm("greedy_segments", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, st["segments"], Tm, max_length,
                   start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
                   ptr(st["unfinished_cnt"]), ptr(st["ws"]))
+
+    def _rules_search_launch(self, st, B, row_div, max_length, start_idx, end_idx, pad_idx, params):
+        """The greedy (``params`` None) or sampled search over B * row_div rows with the state's logit rules between every
+        step's logits and its pick (``ac_trm_search_rules``): always the launch chain, ``logit`` keeps the raw logits."""
+        Tm = st["attn_emb"].shape[1]
+        method, k, top_p, temp = (-1, 0, 0.0, 1.0) if params is None else params   # -1: AC_SEARCH_GREEDY
+        self._trm("search_rules", None, ptr(st["memkv"]), ptr(st["mem_len"]), B * row_div, int(row_div), Tm, max_length,
+                  start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]), ptr(st["embed"]),
+                  ptr(st["unfinished_cnt"]), ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st.get("seed")),
+                  ctypes.byref(st["rules"]), ptr(st["rules_plane"]), st["ld_plane"])
+
+    def _rules_key(self, rules, extra):
+        """The part of a search state's key that names the logit rules (none: the key of the unconstrained search)."""
+        if rules is None:
+            return ()
+        if extra is not None:
+            raise NotImplementedError(f"{type(self).__name__}: repetition and word constraints are not built for a "
+                                      "conditioned decoder")
+        return (("rules", rules.key()),)
 
     def _search_buffers(self, key, dev, B, Tm, A, max_length, segments=1, samples_per_clip=1):
         """Static buffers of an on-device search (greedy or sampled) over B clips: inputs, workspace, outputs.  ``segments``
@@ -333,7 +355,8 @@ class TransformerDecoder(BaseDecoder):
                                           dtype=torch.int32),
         }
 
-    def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None, extra=None):
+    def greedy(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, alone=False, mode=None, extra=None,
+               rules=None):
         """On-device greedy search.  Returns device tensors seq (int64), logit, logprob, embed, cnt.  ``attn_emb`` /
         ``attn_emb_len``: one batch, or lists of batches of the same (frames, width) decoded as one chain.  Batches of one
         row count are the chain's segments: each stops when ITS rows have all emitted <end>, as the reference's loop over
@@ -355,7 +378,11 @@ class TransformerDecoder(BaseDecoder):
         The ~370 short launches of a decode are latency-bound, so the fixed launch sequence (memory
         preparation + max_length decoder steps) is captured once per shape (on its second use) into a HIP graph over
         static buffers and replayed; inputs are copied in, outputs are cloned out (fresh tensors per call, as the
-        reference returns).  Set AUDIOCAPTION_DECODE_GRAPH=0 to launch eagerly."""
+        reference returns).  Set AUDIOCAPTION_DECODE_GRAPH=0 to launch eagerly.
+
+        ``rules`` (a non-neutral ``logit_rules.LogitRules``; None: the search above, with its key and graphs): the
+        constrained search - always the launch chain, one launch more per step (csrc/logit_rules.hip between the classifier
+        and the pick); ``logit`` keeps the raw logits.  The rules are part of the state key."""
         parts = list(attn_emb) if isinstance(attn_emb, (list, tuple)) else [attn_emb]   # several batches, one chain: each is
         dev = parts[0].device                                                           # copied into its rows of the static buffer
         B, Tm = sum(p_.shape[0] for p_ in parts), parts[0].shape[1]
@@ -363,22 +390,27 @@ class TransformerDecoder(BaseDecoder):
         mode = mode or os.environ.get("AUDIOCAPTION_GREEDY", "auto")
         if mode not in ("auto", "chain", "cluster"):
             raise ValueError(f"AUDIOCAPTION_GREEDY={mode!r}: 'auto', 'chain' or 'cluster'")
+        if rules is not None and mode == "auto":
+            mode = "chain"                                         # the one-launch form picks from the raw logits
         wanted = mode == "cluster" or (mode == "auto" and alone)   # the weights are repacked for it only when it can be chosen
         covered = wanted and self.cluster_covers(B, Tm, max_length, dev) and self.cluster_pack() is not None
-        if mode == "cluster" and not covered:
-            raise _lib.HipLibraryError("the one-launch greedy search does not cover this decoder shape / row count")
+        if mode == "cluster" and (not covered or rules is not None):
+            raise _lib.HipLibraryError("the one-launch greedy search does not cover this decoder shape / row count" if
+                                       rules is None else "the one-launch greedy search applies no logit rules")
         cluster = wanted and covered
-        if cluster:
-            segments = 1   # the one-launch form stops on the whole row set
+        if cluster or rules is not None:
+            segments = 1   # the one-launch form (and the constrained search) stops on the whole row set
         # AUDIOCAPTION_CLUSTER_EARLY_STOP=0: the one-launch form runs all max_length steps like the launch chain (benchmarks that
         # compare the two at equal work; the outputs are the same either way)
         early = os.environ.get("AUDIOCAPTION_CLUSTER_EARLY_STOP", "1") != "0"
         key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, cluster, early, self._weights_key(), segments) + \
-            self._extra_key(extra)
+            self._extra_key(extra) + self._rules_key(rules, extra)
         if self._greedy_state is None:
             self._greedy_state = {}
 
         def more():
+            if rules is not None:
+                return rules.buffers(dev, B, self.vocab_size, end_idx)
             if not cluster:
                 return {}
             nb = _lib.load().ac_trm_cluster_workspace_bytes(B)
@@ -419,6 +451,9 @@ class TransformerDecoder(BaseDecoder):
         B, Tm, _ = st["attn_emb"].shape
         method, k, top_p, temp = params
         self._memory_launch(st)
+        if st.get("rules") is not None:
+            self._rules_search_launch(st, B, samples_per_clip, max_length, start_idx, end_idx, pad_idx, params)
+            return
         if samples_per_clip != 1:      # the memory of the B clips once; samples_per_clip rows per clip read it
             self._trm("sample_multi", None, ptr(st["memkv"]), ptr(st["mem_len"]), B, int(samples_per_clip), Tm, max_length,
                       start_idx, end_idx, pad_idx, ptr(st["seq"]), ptr(st["logit"]), ptr(st["sampled_logprob"]),
@@ -430,7 +465,7 @@ class TransformerDecoder(BaseDecoder):
                   ptr(st["ws"]), int(method), int(k), float(top_p), float(temp), ptr(st["seed"]))
 
     def sample(self, attn_emb, attn_emb_len, max_length, start_idx, end_idx, pad_idx, method, k, top_p, temp, seed, extra=None,
-               samples_per_clip=1):
+               samples_per_clip=1, rules=None):
         """On-device sampled search (base.py:152-170 with a sampling ``sample_method``; csrc/sample.hip).  ``method``, ``k``,
         ``top_p``, ``temp``: ``sampling.parse_sample_method``; ``seed``: 64-bit Philox key - row b of step t draws from
         counter (t, b), so a caption depends on (seed, row, step) only.  Returns what ``greedy`` returns.
@@ -444,13 +479,16 @@ class TransformerDecoder(BaseDecoder):
         have B * S rows, clip-major (row r is caption r % S of clip r // S), and row r of step t draws from counter (t, r):
         the result of this call on ``attn_emb.repeat_interleave(S, 0)`` with the same seed, without projecting a clip's
         memory S times.  S is part of the state key: a graph captured for one S is never replayed for another; S = 1 is
-        the call above, with its key and graph."""
+        the call above, with its key and graph.
+
+        ``rules``: as in ``greedy`` - the draw is from the constrained row, ``sampled_logprob`` its value there."""
         from .sampling import seed_word
         dev, (B, Tm, _) = attn_emb.device, attn_emb.shape
         params = (int(method), int(k), float(top_p), float(temp))
         if isinstance(samples_per_clip, bool) or not isinstance(samples_per_clip, int) or samples_per_clip < 1:
             raise ValueError(f"samples_per_clip must be an int >= 1, got {samples_per_clip!r}")
-        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key()) + self._extra_key(extra)
+        key = (dev, B, Tm, max_length, start_idx, end_idx, pad_idx, params, self._weights_key()) + self._extra_key(extra) + \
+            self._rules_key(rules, extra)
         if samples_per_clip != 1:
             if extra is not None:
                 raise NotImplementedError(f"{type(self).__name__}: samples_per_clip (several sampled captions per clip) is "
@@ -462,7 +500,9 @@ class TransformerDecoder(BaseDecoder):
         if getattr(self, "_sample_state", None) is None:
             self._sample_state = {}
         return self._search(self._sample_state, key, [attn_emb], attn_emb_len, max_length, 1,
-                            lambda: {"seed": torch.zeros(1, device=dev, dtype=torch.int64)}, extra,
+                            lambda: {"seed": torch.zeros(1, device=dev, dtype=torch.int64),
+                                     **({} if rules is None else
+                                        rules.buffers(dev, B * samples_per_clip, self.vocab_size, end_idx))}, extra,
                             lambda st: self._sample_launch(st, max_length, start_idx, end_idx, pad_idx, params, samples_per_clip),
                             seed=seed_word(seed), samples_per_clip=samples_per_clip)
 
@@ -478,7 +518,13 @@ class TransformerDecoder(BaseDecoder):
         return top_val, top_idx
 
     def _beam_step_launch(self, st, B, beam, Tm, max_length, t, temp, tokens):
-        """Step t of a beam search over the static buffers of its state (``TransformerModel._beam_begin``; capturable)."""
+        """Step t of a beam search over the static buffers of its state (``TransformerModel._beam_begin``; capturable).  A
+        state with logit rules scores the constrained rows (``ac_trm_beam_step_rules``)."""
+        if st.get("rules") is not None:
+            self._trm("beam_step_rules", None, ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length, t, float(temp),
+                      ptr(tokens), ptr(st["mask"]), ptr(st["cum"]), ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]),
+                      ctypes.byref(st["rules"]), ptr(st["rules_plane"]))
+            return
         self._trm("beam_step", st.get("kw"), ptr(st["memkv"]), ptr(st["mem_len"]), B, beam, Tm, max_length, t, float(temp),
                   ptr(tokens), ptr(st["mask"]), ptr(st["cum"]), ptr(st["top_val"]), ptr(st["top_idx"]), ptr(st["ws"]))
 

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from . import logit_rules
 from . import search_state
 from ._lib import check, ptr, stream
 from .transformer_decoder import KeywordProbTransformerDecoder, TransformerDecoder, check_keyword
@@ -70,6 +71,7 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             from .train import train_forward
             return train_forward(self, input_dict)
         self._check_n_samples(input_dict)      # refused on the host, before the encoder runs
+        self._check_logit_rules(input_dict)
         encoder_output_dict = self.encoder(input_dict)
         output = self.forward_decoder(input_dict, encoder_output_dict)
         flags = _device_flags(output)
@@ -120,11 +122,18 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             raise NotImplementedError(f"{type(self).__name__}: {N_SAMPLES} is built for TransformerModel only")
         return None
 
+    def _check_logit_rules(self, input_dict):
+        """The repetition and word constraints of a request (``logit_rules.KEYS``) are built for ``TransformerModel`` (which
+        overrides this): NotImplementedError naming the key everywhere else.  Neutral values are accepted."""
+        logit_rules.refuse(input_dict, type(self).__name__)
+        return None
+
     def forward_decoder(self, input_dict, encoder_output_dict):
         if input_dict["mode"] == "train":
             raise NotImplementedError("mode='train' is handled by CaptionModel.forward as one fused step")
         elif input_dict["mode"] == "inference":
             self._check_n_samples(input_dict)
+            self._check_logit_rules(input_dict)
             output = self.inference_forward(self._inference_dict(input_dict, encoder_output_dict))
         else:
             raise Exception("mode should be either 'train' or 'inference'")
@@ -147,6 +156,9 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             forward_dict["_seq_on_device"] = True
         if input_dict.get("n_samples") is not None:    # sampling: this many captions per clip (checked by _check_n_samples)
             forward_dict["n_samples"] = input_dict["n_samples"]
+        for key in logit_rules.KEYS:                   # repetition and word constraints (checked by _check_logit_rules)
+            if input_dict.get(key) is not None:
+                forward_dict[key] = input_dict[key]
         forward_dict.update(encoder_output_dict)
         return forward_dict
 
@@ -293,6 +305,7 @@ class TransformerModel(CaptionModel):
         method = input_dict.get("sample_method", "greedy")
         if input_dict.get("n_samples") is not None:
             raise NotImplementedError(f"forward_async: {N_SAMPLES} is not built for it; use model(input_dict)")
+        logit_rules.refuse(input_dict, "forward_async (shared greedy chains, deferred beam searches)")
         if input_dict.get("mode") != "inference" or method not in ("greedy", "beam"):
             raise NotImplementedError("forward_async: greedy or beam inference only; use model(input_dict) otherwise")
         if method == "beam":
@@ -575,6 +588,15 @@ class TransformerModel(CaptionModel):
                              "sample_method ('sample', 'top<k>', 'top<p>', 'gumbel')")
         return n
 
+    def _check_logit_rules(self, input_dict):
+        """The request's ``LogitRules``, or None for a neutral request (keys absent, or 1.0 / 0 / [] / 0), which takes the
+        unconstrained code path.  ValueError, before anything is launched, for a value the rules do not take."""
+        if all(input_dict.get(k) is None for k in logit_rules.KEYS):
+            return None
+        rules = logit_rules.LogitRules.parse(input_dict, self.vocab_size, int(input_dict.get("max_length", self.max_length)),
+                                             self.start_idx, self.end_idx)
+        return None if rules.neutral else rules
+
     # ---- greedy (base.py:152-218) -----------------------------------------------------------------
     def greedy_search(self, input_dict):
         if input_dict.get("temp", 1.0) != 1.0:
@@ -583,6 +605,9 @@ class TransformerModel(CaptionModel):
                 self.pad_idx)
         # the blocking call: nothing else runs on the GPU while this batch decodes -> the one-launch form where it applies
         kw = self._search_kwargs(input_dict)
+        rules = self._check_logit_rules(input_dict)
+        if rules is not None:     # the constrained search: the launch chain with the rules ahead of every pick
+            kw = dict(kw, rules=rules)
         res = self.decoder.greedy(*args, alone=True, **kw)
         if "cluster_error" in res and int(res["cluster_error"].item() & 0xffffffff) != 0:
             import warnings
@@ -620,6 +645,9 @@ class TransformerModel(CaptionModel):
         seed = input_dict.get("seed")
         seed = draw_seed() if seed is None else int(seed)
         more = {} if S is None else {"samples_per_clip": S}
+        rules = self._check_logit_rules(input_dict)
+        if rules is not None:
+            more["rules"] = rules
         res = self.decoder.sample(input_dict["attn_emb"], input_dict["attn_emb_len"], int(input_dict["max_length"]),
                                   self.start_idx, self.end_idx, self.pad_idx, method, k, top_p, temp, seed,
                                   **self._search_kwargs(input_dict), **more)
@@ -672,8 +700,9 @@ class TransformerModel(CaptionModel):
         dec.weights()                              # first: an unsupported decoder shape is refused before any buffer exists
         cap = beam * max_length                    # upper bound of finished beams per clip
         extra = self._search_kwargs(input_dict).get("keyword")   # a conditioned decoder's per-clip input (None for the plain one)
+        rules = self._check_logit_rules(input_dict)              # None: the unconstrained search, its key and its graphs
         key = (dev, B, Tm, A, beam, max_length, temp, self.start_idx, self.end_idx, self.pad_idx, dec._weights_key(), slot) + \
-            dec._extra_key(extra)
+            dec._extra_key(extra) + dec._rules_key(rules, extra)
         if getattr(self, "_beam_state", None) is None:
             self._beam_state = {}
 
@@ -681,6 +710,7 @@ class TransformerModel(CaptionModel):
             f32 = dict(device=dev, dtype=torch.float32)
             ws_n = lib.ac_trm_workspace_floats(ctypes.byref(dec.weights()), R, max_length)
             return {**dec._extra_buffers(dev, B, beam), "graphs": {},
+                    **({} if rules is None else rules.buffers(dev, R, V, self.end_idx)),
                     "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
                     "memkv": torch.empty(dec.nlayers, B * Tm, 2 * dec.d_model, **f32),
                     "tmp": torch.empty(B * Tm, dec.d_model, **f32), "ws": torch.empty(ws_n, **f32),
@@ -777,6 +807,10 @@ class KeywordCondTransformerModel(TransformerModel):
     def _check_n_samples(self, input_dict):
         if input_dict.get("n_samples") is not None:
             raise NotImplementedError(f"KeywordCondTransformerModel: {N_SAMPLES} is not built for keyword conditioning")
+        return None
+
+    def _check_logit_rules(self, input_dict):
+        logit_rules.refuse(input_dict, "KeywordCondTransformerModel")
         return None
 
     def _search_kwargs(self, input_dict):

@@ -519,6 +519,47 @@ int ac_ens_sample_pick(const float* const* logits, int n_models, long ld, int ro
 int ac_ens_beam_step_select(const float* const* logits, int n_models, long ld, int B, int beam, int V, int t, float temp,
                             const float* cum_logprob, float* top_val, int* top_idx, float* scratch, void* stream);
 
+/* ---- repetition and word constraints of a search (csrc/logit_rules.hip) -------------
+ * At step t (0-based) a row has generated g = tokens[1 .. t] - t words, the start token in column 0 is not one of them - and
+ * z is its row of raw logits.  In this order:
+ *   1. repetition_penalty rho (finite, > 0; 1 = off): for every word w of g, z'[w] = z[w] / rho if z[w] > 0, else z[w] * rho -
+ *      computed from z, once per word however often it occurs;
+ *   2. no_repeat_ngram n (0 = off): if t >= n - 1, with p the last n - 1 words of g (none for n = 1), every i with
+ *      i + n - 1 < t and g[i .. i + n - 2] == p bans the word g[i + n - 1] (overlapping occurrences count);
+ *   3. bad_words [n_bad] (device, n_bad <= 256): always banned;
+ *   4. min_length: while t < min_length, end_idx is banned.
+ * Banned: z'[w] = -inf.  Every pick of this library treats a -inf column as absent and renormalises over the others; a
+ * row must keep at least one finite column (the caller's business: the kernel does not count them).
+ *
+ * ac_logit_rules_apply: rows of z at logit + r * ld_in -> z' at out + r * ld_out, out of place (the planes must not overlap;
+ * logit is never written), tokens row r at tokens + r * ld_tok.  One workgroup per row; 16-byte accesses when both planes
+ * are 16-byte aligned with strides that are multiples of 4.  No allocation, no synchronisation: capturable.  AC_ERR_ARG,
+ * nothing launched: V > 16384, t < 0 or t >= ld_tok, n_bad > 256 (or < 0, or without bad_words), rho not finite or <= 0,
+ * negative n or min_length, end_idx outside [0, V), a stride below V, a NULL plane.
+ *
+ * ac_trm_search_rules: ac_trm_greedy (method = AC_SEARCH_GREEDY; k, top_p, temp, seed_dev unused) or ac_trm_sample_multi
+ * (method = AC_SAMPLE_*) over R rows, row_div rows per clip, with the rules between every step's logits and its pick:
+ * `logit` [R][max_len][V] keeps the decoder's RAW logits; the constrained row of a step lives in `plane` (R rows of
+ * ld_plane >= V floats, overwritten by every step), and logprob holds the constrained distribution's values.
+ * ac_trm_beam_step_rules: ac_trm_beam_step with the rules applied to the B * beam rows of raw logits before the scores are
+ * formed; plane: B * beam * V floats. */
+#define AC_SEARCH_GREEDY (-1)
+typedef struct {
+  float repetition_penalty;
+  int32_t no_repeat_ngram, min_length, end_idx, n_bad;
+  const int32_t* bad_words; /* device */
+} ac_logit_rules;
+int ac_logit_rules_apply(const float* logit, long ld_in, float* out, long ld_out, int rows, int V, const int* tokens,
+                         long ld_tok, int t, const ac_logit_rules* rules, void* stream);
+int ac_trm_search_rules(const ac_trm_weights* w, const float* memkv, const int* mem_len, int R, int row_div, int Tm,
+                        int max_len, int start_idx, int end_idx, int pad_idx, int64_t* seq, float* logit, float* logprob,
+                        float* embed, int* unfinished_cnt, float* ws, int method, int k, float top_p, float temp,
+                        const uint64_t* seed_dev, const ac_logit_rules* rules, float* plane, long ld_plane, void* stream);
+int ac_trm_beam_step_rules(const ac_trm_weights* w, const float* memkv, const int* mem_len, int B, int beam, int Tm,
+                           int max_len, int t, float temp, const int* tokens, const unsigned char* key_mask,
+                           const float* cum_logprob, float* top_val, int* top_idx, float* ws,
+                           const ac_logit_rules* rules, float* plane, void* stream);
+
 /* ---- Bahdanau-attention GRU decoder (rnn_decoder.py:10-36,74-113,159-216, hf_wrapper.py:1377-1554) -------------
  * BahAttnCatFcDecoder / TemporalBahAttnDecoder for inference, csrc/attn_gru.hip.  One GRU layer, unidirectional.  With
  * E = emb_dim, d = d_model, S = attn_size, A = attn_emb_dim, F = fc_emb_dim (each a multiple of 32 up to 1024), V = vocab
