@@ -187,6 +187,7 @@ SIGNATURES = {
     # self-critical sequence training (csrc/scst.hip)
     "ac_scst_pick": (_I, [_P, _L, _I, _I, _F, _P, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P]),
     "ac_scst_loss": (_I, [_P, _P, _L, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "ac_scst_group_reward": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     # token-level knowledge distillation (csrc/kd.hip)
     "ac_kd_loss": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _F, _P, _P]),
     # encoder-level knowledge distillation (csrc/enc_kd.hip)

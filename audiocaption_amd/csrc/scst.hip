@@ -8,6 +8,9 @@
 //                 loss = (1 / N) sum row_loss, dlogit = -(reward * mask / (N * temp)) * (onehot(w) - softmax(logit)).
 //                 One 256-thread workgroup per (clip, step) row, fp32 wave reductions (like the cross entropy of
 //                 csrc/train.hip).
+//   ac_scst_group_reward  the reward of K rollouts per clip from their scores [K][N]: against the greedy caption's score,
+//                 or against the mean score of the clip's other K - 1 rollouts (leave-one-out).  One thread per clip,
+//                 sums in the order j = 0 .. K-1.
 #include "ac_sample.h"
 #include "../../include/audiocaption_hip.h"
 
@@ -83,7 +86,38 @@ __global__ __launch_bounds__(256) void scst_sum_kernel(const float* x, long n, f
   if (threadIdx.x == 0) out[0] = a * scale;
 }
 
+// reward[k][n] of clip n (one thread per clip): mode greedy s[k][n] - g[n]; mode mean s[k][n] - (sum_j s[j][n] - s[k][n]) /
+// (K - 1), the sum taken once in the order j = 0 .. K-1
+__global__ __launch_bounds__(256) void scst_group_reward_kernel(const float* scores, int K, int N, int mode,
+                                                                const float* greedy, float* reward) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  if (mode == AC_SCST_BASELINE_GREEDY) {
+    const float g = greedy[n];
+    for (int k = 0; k < K; ++k) reward[(long)k * N + n] = scores[(long)k * N + n] - g;
+    return;
+  }
+  float sum = 0.f;
+  for (int j = 0; j < K; ++j) sum += scores[(long)j * N + n];
+  const float others = (float)(K - 1);
+  for (int k = 0; k < K; ++k) {
+    const float s = scores[(long)k * N + n];
+    reward[(long)k * N + n] = s - (sum - s) / others;
+  }
+}
+
 }  // namespace
+
+extern "C" int ac_scst_group_reward(const float* scores, int K, int N, int mode, const float* greedy_scores, float* reward,
+                                    void* stream) {
+  if (!scores || !reward || K < 1 || K > AC_SCST_MAX_ROLLOUTS || N < 1 ||
+      (mode != AC_SCST_BASELINE_GREEDY && mode != AC_SCST_BASELINE_MEAN) || (mode == AC_SCST_BASELINE_GREEDY && !greedy_scores) ||
+      (mode == AC_SCST_BASELINE_MEAN && K < 2))
+    return AC_ERR_ARG;
+  hipLaunchKernelGGL(scst_group_reward_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, scores, K, N, mode,
+                     greedy_scores, reward);
+  return ac_check_launch();
+}
 
 extern "C" int ac_scst_pick(const float* logit, long ld, int N, int V, float temp, const uint64_t* seed_dev, int t,
                             int end_idx, const int* forced, long forced_ld, int* done, int* drawn, int* seq, long seq_ld,

@@ -21,6 +21,23 @@ current keys.  For ``mode == "train"``:
    bridge node, so ``loss.backward()`` fills ``.grad`` of every trainable parameter;
 5. output ``{"greedy_seqs", "sampled_seqs", "reward", "score", "loss"}``; the model is left in ``train()`` mode.
 
+``ScstWrapper(model, n_rollouts=K, baseline="greedy" | "mean")`` (K in 1..8; the defaults are the recipe above, launch for
+launch) is the multi-rollout form (Luo 2020, "A Better Variant of Self-Critical Sequence Training"), for ``TransformerModel``:
+
+* K rollouts per clip from ONE train-mode encoder pass: the decoder runs over J = K*N rollout rows, row j = k*N + n on clip
+  n's audio memory (``TrainEngine.rollout(input_dict, n_rollouts=K)``);
+* ``baseline="mean"``: the baseline of a rollout is the mean score of the clip's other K - 1 rollouts - no greedy decode, no
+  ``eval()`` switch, no ``greedy_seqs``; ``baseline="greedy"``: step 1 above, one greedy caption per clip;
+* scores: the built-in ``Cider`` reads the K row blocks of the rollout's words (and the greedy words) on the device, at most
+  ``cider.MAX_SETS`` hypothesis sets per ``score_ids`` call; any other scorer gets one ``compute_batch_score`` per set on
+  the host (clips sharing a key are scored once within a set, never across rollouts) and one upload of all the scores;
+* reward on the device (csrc/scst.hip ac_scst_group_reward), f32, sums in the order j = 0..K-1:
+  greedy ``r[k, n] = s[k, n] - g[n]``, mean ``r[k, n] = s[k, n] - (sum_j s[j, n] - s[k, n]) / (K - 1)``;
+* the loss kernel over the J rows with ``reward`` (J,): ``loss = mean_j sum_t -(sampled_logprob * reward * mask)``; the
+  backward sums the K rollouts' gradients into clip n's audio memory;
+* output ``sampled_seqs`` (N, K, T), ``reward`` and ``score`` (N, K), ``loss``, and ``greedy_seqs`` (N, T) with the greedy
+  baseline only.
+
 The wrapped model is a ``TransformerModel``, or a ``Seq2SeqAttnModel`` / ``TemporalSeq2SeqAttnModel`` over a ``CrnnEncoder``
 (``temporal_tag`` then goes to both the baseline and the rollout).  Any other mode is forwarded to the wrapped model.
 The caller's ``input_dict`` is not modified (the reference overwrites its ``mode`` and ``sample_method``).
@@ -103,10 +120,32 @@ def scst_loss(logit, seq, reward, temp, end_idx):
     return _ScstLossFn.apply(logit, seq, reward, float(temp), int(end_idx))
 
 
+MAX_ROLLOUTS = 8       # include/audiocaption_hip.h AC_SCST_MAX_ROLLOUTS
+BASELINES = ("greedy", "mean")      # AC_SCST_BASELINE_GREEDY, AC_SCST_BASELINE_MEAN
+
+
+def group_reward(scores, mode, greedy_scores=None):
+    """``reward`` (K*N,) f32 on the device of ``scores`` (K, N) f32: csrc/scst.hip ac_scst_group_reward."""
+    K, N = scores.shape
+    scores = scores.float().contiguous()
+    if greedy_scores is not None:
+        greedy_scores = greedy_scores.to(device=scores.device, dtype=torch.float32).contiguous()
+    reward = torch.empty(K * N, device=scores.device, dtype=torch.float32)
+    check(_lib.load().ac_scst_group_reward(ptr(scores), K, N, BASELINES.index(mode), ptr(greedy_scores), ptr(reward),
+                                           stream()), "ac_scst_group_reward")
+    return reward
+
+
 class ScstWrapper(nn.Module, CaptionMetaMixin):
 
-    def __init__(self, model):
+    def __init__(self, model, n_rollouts=1, baseline="greedy"):
         super().__init__()
+        if isinstance(n_rollouts, bool) or not isinstance(n_rollouts, int) or not 1 <= n_rollouts <= MAX_ROLLOUTS:
+            raise ValueError(f"ScstWrapper: n_rollouts must be an int in 1..{MAX_ROLLOUTS}, got {n_rollouts!r}")
+        if baseline not in BASELINES:
+            raise ValueError(f"ScstWrapper: baseline must be 'greedy' or 'mean', got {baseline!r}")
+        if baseline == "mean" and n_rollouts < 2:
+            raise ValueError("ScstWrapper: baseline='mean' is the mean score of a clip's OTHER rollouts; it needs n_rollouts >= 2")
         from .attn_model import ConditionalSeq2SeqAttnModel, Seq2SeqAttnModel
         from .crnn_trm_encoder import CrnnEncoder
         if isinstance(model, ConditionalSeq2SeqAttnModel):
@@ -121,7 +160,12 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
             raise NotImplementedError(f"ScstWrapper: the wrapped model must be a TransformerModel, or a Seq2SeqAttnModel / "
                                       f"TemporalSeq2SeqAttnModel over a CrnnEncoder (the HIP training engines' rollouts), "
                                       f"got {model.__class__.__name__}{over}")
+        if self._attn_gru and (n_rollouts > 1 or baseline == "mean"):
+            raise NotImplementedError("ScstWrapper: n_rollouts > 1 and baseline='mean' (several rollouts per clip from one "
+                                      "encoder pass) are built for TransformerModel; the attention-GRU engines draw one "
+                                      "rollout per clip against the greedy baseline")
         self.model = model
+        self.n_rollouts, self.baseline = n_rollouts, baseline
 
     def forward(self, input_dict):
         if input_dict["mode"] == "train":
@@ -155,7 +199,8 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
         model = self.model
         if input_dict.get("n_samples") is not None:
             from .transformer_model import N_SAMPLES
-            raise NotImplementedError(f"ScstWrapper: {N_SAMPLES} is not built for the SCST rollout")
+            raise NotImplementedError(f"ScstWrapper: {N_SAMPLES} is not built for the SCST rollout; several rollouts per "
+                                      "clip at training time are the constructor argument n_rollouts")
         for k in ("keys", "key2refs", "vocabulary", "scorer"):
             if input_dict.get(k) is None:
                 raise ValueError(f"ScstWrapper: input_dict[{k!r}] is required for mode 'train' (run.py:35-41)")
@@ -175,6 +220,8 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
                 from .train import TrainEngine
                 engine = model._train_engine = TrainEngine(model)
         keys = list(input_dict["keys"])
+        if self.n_rollouts > 1 or self.baseline == "mean":
+            return self._scst_multi(input_dict, engine, keys, max_length, temp)
 
         greedy, greedy_i32 = self._baseline(input_dict, max_length)
         model.train()
@@ -208,3 +255,46 @@ class ScstWrapper(nn.Module, CaptionMetaMixin):
         loss = scst_loss(logit, out["seq_i32"], reward_dev, temp, model.end_idx)
         return {"greedy_seqs": greedy, "sampled_seqs": sampled, "reward": torch.as_tensor(reward),
                 "score": torch.as_tensor(score["sampled"]), "loss": loss}
+
+    def _scst_multi(self, input_dict, engine, keys, max_length, temp):
+        """K rollouts per clip from one encoder pass, against the greedy caption or the mean of the clip's other rollouts
+        (the module's docstring)."""
+        from .cider import MAX_SETS
+        from .train import _TrainBridge
+        model, K, mean = self.model, self.n_rollouts, self.baseline == "mean"
+        N = len(keys)
+        greedy = greedy_i32 = None
+        if not mean:
+            greedy, greedy_i32 = self._baseline(input_dict, max_length)
+        model.train()
+        out = engine.rollout(dict(input_dict, max_length=max_length, temp=temp), n_rollouts=K)
+        seq_i32 = out["seq_i32"]                      # (J, T), row j = k*N + n
+        if seq_i32.shape[0] != K * N:
+            raise ValueError(f"ScstWrapper: {N} keys for a batch of {seq_i32.shape[0] // K} clips")
+        T = seq_i32.shape[1]
+        sets = [seq_i32[k * N:(k + 1) * N] for k in range(K)] + ([] if mean else [greedy_i32])
+        if isinstance(input_dict["scorer"], Cider):
+            # on the device, where the decoders left the words: at most MAX_SETS hypothesis sets per call (each call's one
+            # upload is the batch's packed references); nothing is downloaded before the loss is launched
+            rows = []
+            for i in range(0, len(sets), MAX_SETS):
+                res = input_dict["scorer"].score_ids(input_dict["key2refs"], input_dict["vocabulary"], model.vocab_size, keys,
+                                                     tuple(sets[i:i + MAX_SETS]), model.start_idx, model.end_idx)
+                rows.append(res["scores"])
+            all_scores = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+        else:
+            host = np.stack([compute_batch_score(w.cpu().numpy(), input_dict["key2refs"], keys, model.start_idx, model.end_idx,
+                                                 input_dict["vocabulary"], input_dict["scorer"]) for w in sets])
+            all_scores = torch.from_numpy(host.astype(np.float32)).to(seq_i32.device)          # the one upload
+        scores = all_scores[:K]
+        reward = group_reward(scores, self.baseline, None if mean else all_scores[K])
+        logit = out["logit"]
+        if torch.is_grad_enabled():
+            logit = _TrainBridge.apply(engine, logit, *engine.flat.params)
+        loss = scst_loss(logit, seq_i32, reward, temp, model.end_idx)
+        res = {"sampled_seqs": out["seq"].view(K, N, T).transpose(0, 1).contiguous().cpu(),
+               "reward": reward.view(K, N).t().contiguous().cpu().double(),
+               "score": scores.t().contiguous().cpu().double(), "loss": loss}
+        if not mean:
+            res["greedy_seqs"] = torch.as_tensor(greedy).cpu()
+        return res

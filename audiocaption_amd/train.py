@@ -528,8 +528,11 @@ class TrainEngine:
             _lib.bump_param_generation(self.flat.params)
 
     @staticmethod
-    def _layout(N, T, Tm, teacher_forcing, device):
-        """Static index tables of the row space."""
+    def _layout(N, T, Tm, teacher_forcing, device, K=1):
+        """Static index tables of the row space.  ``K`` > 1 (multi-rollout SCST): the decoder's batch is the J = K*N rollout
+        rows, row j = k*N + n of every pass belonging to clip n - the row space of a batch of J clips, whose ``clip``
+        column folds back onto the N clips of the encoder."""
+        clips, N = N, K * N
         if teacher_forcing:
             passes = [(T, 0)]
         else:
@@ -546,7 +549,7 @@ class TrainEngine:
         cls_rows = torch.empty(N * T, dtype=torch.int32)
         for t, (L, off) in enumerate(passes):
             pos[off:off + N * L] = torch.arange(L, dtype=torch.int32).repeat(N)
-            clip[off:off + N * L] = torch.arange(N, dtype=torch.int32).repeat_interleave(L)
+            clip[off:off + N * L] = (torch.arange(N, dtype=torch.int32) % clips).repeat_interleave(L)
             qrow0[t * N:(t + 1) * N] = off + torch.arange(N, dtype=torch.int32) * L
             qlen[t * N:(t + 1) * N] = L
             if teacher_forcing:
@@ -560,7 +563,9 @@ class TrainEngine:
         return lay
 
     # ---- host side of one iteration: shapes, static input buffers, scheduled-sampling draws, seed -------------
-    def _prepare(self, input_dict, rollout=False):
+    def _prepare(self, input_dict, rollout=False, K=1):
+        """``K`` (the SCST rollout only): rollouts per clip.  ``cap`` then has J = K*N rows, the decoder's batch; the encoder's
+        batch, ``wav`` and ``wav_len`` stay at the N clips."""
         model = self.model
         enc, dec = model.encoder, model.decoder
         # A model in eval() (a distillation teacher, run_kd.py:42,133; a teacher-forced validation loss) runs the same
@@ -576,7 +581,8 @@ class TrainEngine:
             raise _lib.HipLibraryError("the training step needs tensors on a ROCm device; there is no CPU fallback")
         self._ensure(dev)
         cap = input_dict["cap"]
-        N, Tc = cap.shape
+        J, Tc = cap.shape
+        N = J // K
         T = Tc - 1
         ss_ratio = input_dict["ss_ratio"]
         teacher_forcing = ss_ratio == 1
@@ -609,26 +615,28 @@ class TrainEngine:
             keyword = check_keyword(input_dict.get("keyword"), N, dec.keyword_classes_num)
             key += ("keyword", tuple(keyword.shape))
         if rollout:
-            key += ("rollout",)     # the SCST rollout's states never collide with the cross-entropy step's of the same shape
+            # the SCST rollout's states never collide with the cross-entropy step's of the same shape, nor those of
+            # different rollout counts with each other
+            key += ("rollout",) if K == 1 else ("rollout", K)
         if evalm:
             key += ("eval",)        # nor an eval-mode forward's with a train-mode one's whose dropout happens to be 0
         st = self._states.get(key)
         if st is None:
-            lay = self._layout(N, T, Tm, teacher_forcing, dev)
+            lay = self._layout(N, T, Tm, teacher_forcing, dev, K)
             S = lay["S"]
             if self._wsg is None or self._wsg.device != dev:
                 self._wsg = _Ws(dev)
-            st = {"key": key, "ws": self._wsg, "lay": lay, "N": N, "T": T, "Tc": Tc, "Tq": Tq, "Tm": Tm,
+            st = {"key": key, "ws": self._wsg, "lay": lay, "N": N, "J": J, "T": T, "Tc": Tc, "Tq": Tq, "Tm": Tm,
                   "teacher_forcing": teacher_forcing, "eval": evalm,
                   "p_dec": p_dec, "p_rnn": p_rnn, "p_cnn": p_cnn, "graphs": {}, "steps": 0,
                   "wav": torch.empty_like(wav, dtype=torch.float32) if hook is None else None,
                   "cnn_attn_in": torch.empty(N, Tq, 2048, device=dev) if hook is not None else None,
-                  "cap": torch.empty(N, Tc, device=dev, dtype=torch.int64),
+                  "cap": torch.empty(J, Tc, device=dev, dtype=torch.int64),
                   "keyword": torch.empty(keyword.shape, device=dev, dtype=torch.float32) if keyword is not None else None,
                   "specaug": torch.zeros(N, 4, 2, device=dev, dtype=torch.int32) if (specaug and hook is None) else None,
                   "specaug_pinned": [],
                   # one pinned staging block -> one device block (int32 words):
-                  #   seed (int64) | lens [N] | tgt_len [N] | use_cap [T] | mvalid [S]
+                  #   seed (int64) | lens [N] | tgt_len [N] | use_cap [T] | mvalid [S]   (S = passes x J sequences)
                   # a ring of staging blocks, each guarded by an event, because the host runs ahead of the device
                   "ring": [(torch.zeros(2 + 2 * N + max(T, 1) + S, dtype=torch.int32).pin_memory(), torch.cuda.Event())
                            for _ in range(4)],
@@ -719,8 +727,12 @@ class TrainEngine:
         nlay = dec.nlayers
         V = dec.vocab_size
         F = dec.dim_feedforward
+        J = st["J"]                # the decoder's batch: K rollout rows per clip (J == N outside multi-rollout SCST)
         rows_m = N * Tm
-        Rm = NP * rows_m
+        # every sequence (pass t, decoder row j) owns a replica of its clip's memory rows under its own dropout mask:
+        # replica t*J + j = t*J + k*N + n reads mem_a block n (row index modulo rows_m), so the replicas stay
+        # [replica][N][Tm] blocks whatever K is
+        Rm = NP * (J // N) * rows_m
         mem_a = ws.f("mem_a", rows_m, D)
         self._lin(s, attn_emb, *fp.wb(dp + "attn_proj.0."), mem_a, rows_m, D, A, relu=1)
         mem_pre, mem = ws.f("mem_pre", Rm, D), ws.f("mem", Rm, D)
@@ -743,8 +755,8 @@ class TrainEngine:
 
         # ---- the passes ------------------------------------------------------------------------------
         word = ws.i("word", R)
-        seq = ws.i("seq", N * T)
-        logit = ws.f("logit", N * T, V)
+        seq = ws.i("seq", J * T)
+        logit = ws.f("logit", J * T, V)
         pos, qrow0, qlen = lay["pos"].data_ptr(), lay["qrow0"].data_ptr(), lay["qlen"].data_ptr()
         mrow0, mklen = lay["mrow0"].data_ptr(), lay["mklen"].data_ptr()
         emb, pe, cls = fp.p(dp + "word_embedding.weight"), dec.pos_encoder.pe.data_ptr(), fp.p(dp + "classifier.weight")
@@ -900,7 +912,7 @@ class TrainEngine:
         s = _lib.stream()
         self._phase = "forward"
         ws, lay, c = st["ws"], st["lay"], st["ctx"]
-        N, T, Tc = st["N"], st["T"], st["Tc"]
+        N, T, Tc = st["J"], st["T"], st["Tc"]      # (the decoder's batch: the J rollout rows, the clips themselves otherwise)
         V, F, acts, word = st["V"], st["F"], st["acts"], st["word"]
         p_dec, teacher_forcing = st["p_dec"], st["teacher_forcing"]
         passes = lay["passes"]
@@ -965,7 +977,7 @@ class TrainEngine:
                                            s), "ac_scst_pick")
 
     def _outputs(self, st):
-        N, T, V = st["N"], st["T"], st["V"]
+        N, T, V = st["J"], st["T"], st["V"]
         out = {"logit": st["ws"].tensor("logit")[:N * T * V].view(N, T, V), "attn_emb_len": st["lens_host"]}
         if not st["teacher_forcing"]:
             out["seq"] = st["ws"].tensor("seq")[:N * T].view(N, T)
@@ -1004,7 +1016,20 @@ class TrainEngine:
         return ws.tensor("fc_emb")[:N * A].view(N, A)
 
     # ---- SCST rollout (rl_model.py:35-38: the model in train() mode, sample_method "sample") --------------------------
-    def rollout(self, input_dict):
+    MAX_ROLLOUTS = 8      # include/audiocaption_hip.h AC_SCST_MAX_ROLLOUTS
+
+    @staticmethod
+    def _check_row_space(N, K, T, Tm, widest):
+        """ValueError if the rollout's row space leaves the engine's int32 row indices: the J*T*(T+1)/2 decoder rows, the
+        T*J*Tm memory-replica rows, and the element offsets the index tables and the dropout sites are built for (a row
+        index times the widest row, ``widest`` floats)."""
+        J = K * N
+        R, Rm = J * T * (T + 1) // 2, T * J * Tm
+        if max(R, Rm) * widest >= 2 ** 31:
+            raise ValueError(f"rollout: {K} rollouts x {N} clips x max_length {T} is a row space of {R} decoder rows and {Rm} "
+                             f"memory rows, beyond the engine's int32 row indices; lower n_rollouts, the batch or max_length")
+
+    def rollout(self, input_dict, n_rollouts=1):
         """The sampled rollout of self-critical sequence training: the train-mode encoder, then ``max_length`` decoder passes,
         pass t on <start> plus the words drawn so far with the train-mode dropout masks of that pass (base.py:152-170); the
         word of step t is drawn on the device from softmax(log_softmax(logit_t) / temp) and a clip that has drawn <end>
@@ -1015,12 +1040,21 @@ class TrainEngine:
         ``input_dict``: wav / wav_len / specaug as for mode "train"; ``max_length`` (default the model's), ``temp`` (1.0);
         ``dropout_seed`` as in ``forward``; ``seed``: the sampler's 64-bit seed (default: the dropout seed of this call);
         ``_scst_words`` (parity hook, int64 N x T): these words instead of the draws, the finished-row rule still applies.
-        Returns ``logit`` (N, T, V), ``seq`` (int64) and ``seq_i32`` (N, T), ``sampled_logprob`` (N, T), all on the device."""
+        Returns ``logit`` (N, T, V), ``seq`` (int64) and ``seq_i32`` (N, T), ``sampled_logprob`` (N, T), all on the device.
+
+        ``n_rollouts`` = K > 1 (multi-rollout SCST): K rollouts per clip from ONE encoder pass.  The decoder runs over J = K*N
+        rollout rows, row j = k*N + n on clip n's audio memory; its row space, dropout-mask element indices and the sampler's
+        Philox counters (step, row) are those of this rollout for a batch of J clips, the encoder sites keep the indices of
+        a batch of N.  ``_scst_words`` is then (N, K, T), and the results have J rows in place of N."""
         import math
         model = self.model
         if input_dict.get("n_samples") is not None:
             from .transformer_model import N_SAMPLES
-            raise NotImplementedError(f"TrainEngine.rollout: {N_SAMPLES} is not built for the SCST rollout")
+            raise NotImplementedError(f"TrainEngine.rollout: {N_SAMPLES} is not built for the SCST rollout; the training-time "
+                                      "form is rollout(input_dict, n_rollouts=K) / ScstWrapper(model, n_rollouts=K)")
+        K = n_rollouts
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= self.MAX_ROLLOUTS:
+            raise ValueError(f"rollout: n_rollouts must be an int in 1..{self.MAX_ROLLOUTS}, got {K!r}")
         if self.keyword:
             raise NotImplementedError("TrainEngine.rollout: the SCST rollout is not built for keyword conditioning "
                                       "(KeywordCondTransformerModel)")
@@ -1034,17 +1068,27 @@ class TrainEngine:
         if not wav.is_cuda:
             raise _lib.HipLibraryError("the training step needs tensors on a ROCm device; there is no CPU fallback")
         N = wav.shape[0]
-        cap = torch.zeros(N, T + 1, device=wav.device, dtype=torch.int64)    # never read: no pass is teacher forced
+        J = K * N
+        if K > 1:
+            hook = input_dict.get("_cnn_attn")
+            Tq = model.encoder.cnn.geometry(wav.shape[1])[1][5] if hook is None else hook.shape[1]
+            dec = model.decoder
+            self._check_row_space(N, K, T, Tq + (self.enc_kind == "trm"), max(dec.dim_feedforward, 3 * D, dec.vocab_size))
+        cap = torch.zeros(J, T + 1, device=wav.device, dtype=torch.int64)    # never read: no pass is teacher forced
         d = {k: v for k, v in input_dict.items() if k not in ("cap_len",)}
         d.update(cap=cap, ss_ratio=0.0, _use_cap=[0] * T)
         base_seed = int(input_dict.get("dropout_seed", self.seed))
-        st = self._prepare(d, rollout=True)
+        st = self._prepare(d, rollout=True, K=K)
         seed = int(input_dict["seed"]) if input_dict.get("seed") is not None else base_seed
         forced = input_dict.get("_scst_words")
         if forced is not None:
-            forced = torch.as_tensor(forced).to(device=wav.device, dtype=torch.int32).contiguous()
-            if tuple(forced.shape) != (N, T):
-                raise ValueError(f"_scst_words must be ({N}, {T})")
+            forced = torch.as_tensor(forced).to(device=wav.device, dtype=torch.int32)
+            want = (N, T) if K == 1 else (N, K, T)
+            if tuple(forced.shape) != want:
+                raise ValueError(f"_scst_words must be {want}")
+            if K > 1:
+                forced = forced.permute(1, 0, 2).reshape(J, T)      # row j = k*N + n
+            forced = forced.contiguous()
         ro = st.get("rollout")
         if ro is None:
             ro = st["rollout"] = {"seed": torch.zeros(1, device=wav.device, dtype=torch.int64)}
@@ -1057,7 +1101,7 @@ class TrainEngine:
         out["logit"] = out["logit"].clone()
         out["seq_i32"] = out["seq"].clone()
         out["seq"] = out["seq_i32"].to(torch.int64)
-        out["sampled_logprob"] = st["ws"].tensor("scst_logprob")[:N * T].view(N, T).clone()
+        out["sampled_logprob"] = st["ws"].tensor("scst_logprob")[:J * T].view(J, T).clone()
         return out
 
     # ---- backward -----------------------------------------------------------------------------------------
@@ -1121,9 +1165,10 @@ class TrainEngine:
         ws, lay = sv["ws"], sv["lay"]
         N, T, Tq, V, F = sv["N"], sv["T"], sv["Tq"], sv["V"], sv["F"]
         B, Tm = N, sv["Tm"]
+        J = sv["J"]
         p_dec = sv["p_dec"]
         R, S = lay["R"], lay["S"]
-        NP = len(lay["passes"])
+        NP = len(lay["passes"]) * (J // N)     # memory replicas: one per (pass, rollout)
         rows_m = N * Tm
         Rm = NP * rows_m
         nh = dec.nhead
@@ -1135,7 +1180,7 @@ class TrainEngine:
         qrow0, qlen = lay["qrow0"].data_ptr(), lay["qlen"].data_ptr()
         mrow0, mklen = lay["mrow0"].data_ptr(), lay["mklen"].data_ptr()
         cls_rows = lay["cls_rows"].data_ptr()
-        NT = N * T
+        NT = J * T
 
         # ---- classifier --------------------------------------------------------------------------------
         xlast, dxlast = ws.f("xlast", NT, D), ws.f("dxlast", NT, D)

@@ -899,6 +899,18 @@ int ac_scst_pick(const float* logit, long ld, int N, int V, float temp, const ui
  * (softmax(logit[n][t]) - onehot(seq[n][t])), exactly 0 on masked rows.  V <= 16384, temp > 0 (AC_ERR_ARG otherwise). */
 int ac_scst_loss(const float* logit, const int* seq, long seq_ld, const float* reward, float temp, int end_idx, int N, int T,
                  int V, float* row_loss, float* loss, float* dlogit, const float* gscale_dev, void* stream);
+/* ac_scst_group_reward: the reward of K rollouts per clip (multi-rollout SCST).  scores f32 [K][N] (rollout k of clip n at
+ * k * N + n), reward f32 [K * N] in the same order - the row order of the rollout's decoder batch -, all device memory.
+ * mode AC_SCST_BASELINE_GREEDY: reward[k][n] = scores[k][n] - greedy_scores[n] (greedy_scores f32 [N]);
+ * mode AC_SCST_BASELINE_MEAN (leave-one-out): reward[k][n] = scores[k][n] - (sum_j scores[j][n] - scores[k][n]) / (K - 1),
+ * the sum in f32 in the order j = 0 .. K-1; greedy_scores is not read and may be NULL.  One launch, no allocation, no
+ * synchronisation (capturable).  AC_ERR_ARG, nothing launched: K < 1, K > AC_SCST_MAX_ROLLOUTS, the mean mode with K < 2,
+ * N < 1, an unknown mode, scores or reward NULL, greedy_scores NULL in the greedy mode. */
+#define AC_SCST_MAX_ROLLOUTS 8
+#define AC_SCST_BASELINE_GREEDY 0
+#define AC_SCST_BASELINE_MEAN 1
+int ac_scst_group_reward(const float* scores, int K, int N, int mode, const float* greedy_scores, float* reward,
+                         void* stream);
 /* ---- token-level knowledge distillation (kd_loss.py:8-49; csrc/kd.hip) ------------------------------
  * ac_kd_loss: SupKdLoss(LabelSmoothingLoss(smoothing), TokenLevelKdLoss(temp, "kl"), sup_weight) in one pass per row.
  * logit / tchr_logit [N][T][V] (student / frozen teacher), tgt int64 [N][tgt_ld], tgt_len int32 [N].  On a valid row
