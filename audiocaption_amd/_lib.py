@@ -125,6 +125,8 @@ SIGNATURES = {
     "ac_ens_greedy_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_sample_pick": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ac_ens_beam_step_select": (_I, [_P, _I, _L, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    # group (diverse) beam search (csrc/group_beam.hip); `prev_tok` is a ctypes array of c_void_p
+    "ac_group_beam_select": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _P, _P, _I, _L, _P, _P, _P, _P]),
     # repetition and word constraints (csrc/logit_rules.hip); `rules` is ctypes.byref(AcLogitRules)
     "ac_logit_rules_apply": (_I, [_P, _L, _P, _L, _I, _I, _P, _L, _I, _P, _P]),
     "ac_trm_search_rules": (_I, [_WP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _L,

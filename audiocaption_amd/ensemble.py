@@ -91,6 +91,9 @@ class EnsembleModel(nn.Module):
             from .transformer_model import N_SAMPLES
             raise NotImplementedError(f"EnsembleModel: {N_SAMPLES} is not built for ensembles")
         logit_rules.refuse(input_dict, "EnsembleModel", "a single TransformerModel's blocking model(input_dict)")
+        if input_dict.get("group_size") is not None:
+            from .transformer_model import GROUP_BEAM
+            raise NotImplementedError(f"EnsembleModel: {GROUP_BEAM} is not built for ensembles")
         encs = [m.encoder(input_dict) for m in self.models]   # one after the other on the current stream
         args = {k: input_dict[k] for k in ("sample_method", "max_length", "temp", "beam_size", "n_best", "n_best_size", "seed")
                 if input_dict.get(k) is not None}

@@ -7,7 +7,9 @@ eagerly on the first use of a state (also the warm-up a capture needs; a shape t
 and is captured into a HIP graph on the second and replayed from then on (``run``; AUDIOCAPTION_DECODE_GRAPH=0: always
 eager).  A beam search is the buffers of base.py:290-323's per-clip bookkeeping (``beam_buffers``), their reset to the start
 of a search (``beam_reset``), the device-side update of every step (``beam_update``) and the host-side ranking of the
-finished beams (``beam_rank``)."""
+finished beams (``beam_rank``).  A group beam search keeps one such book per group: the order of its steps
+(``group_steps``), the earlier groups' planes a selection reads (``group_prev_planes``) and its result (``group_rank``)."""
+import ctypes
 import os
 
 import numpy as np
@@ -112,3 +114,35 @@ def beam_rank(st, B, cap, max_length, end_idx, n_best, n_best_size):
             score[i, j] = scores[i, o]
     seq, score = torch.from_numpy(seq), torch.from_numpy(score)
     return (seq, score) if n_best else (seq[:, 0], score[:, 0])
+
+
+# ---- group beam search: G beam books staggered in time (base.py:413-417) --------------------------------------------------
+def group_steps(G, max_length):
+    """``(g, lt)`` of every group step in launch order: at global step t = 0 .. max_length + G - 2 the groups g = 0 .. G - 1 whose
+    local position lt = t - g lies in 0 .. max_length - 1."""
+    return [(g, t - g) for t in range(max_length + G - 1) for g in range(G) if 0 <= t - g < max_length]
+
+
+def group_prev_planes(books, g, lt, max_length):
+    """What ``ac_group_beam_select`` takes as ``prev_tok`` when group g stands at lt: the CURRENT token planes of the books
+    of groups 0 .. g - 1 as a ctypes array (None for group 0).  Group q has by then finished its step at
+    min(lt + g - q, max_length - 1), whose update wrote plane ``(step + 1) & 1``."""
+    if g == 0:
+        return None
+    planes = [books[q]["tok"][(min(lt + g - q, max_length - 1) + 1) & 1] for q in range(g)]
+    return (ctypes.c_void_p * g)(*[p.data_ptr() for p in planes])
+
+
+def group_rank(books, B, bdash, max_length, end_idx, beam_size, group_nbest):
+    """base.py:463-469: per group its ``bdash`` best finished beams (``beam_rank``); ``seq`` (B, beam_size, max_length) int64 on
+    the host with group 0's captions first (rows beyond G * bdash stay ``end_idx``), or (B, G, max_length), the best of each
+    group, without ``group_nbest``."""
+    G = len(books)
+    seq = torch.full((B, beam_size if group_nbest else G, max_length), end_idx, dtype=torch.int64)
+    for g, book in enumerate(books):
+        best, _ = beam_rank(book, B, bdash * max_length, max_length, end_idx, True, bdash)
+        if group_nbest:
+            seq[:, g * bdash:(g + 1) * bdash] = best
+        else:
+            seq[:, g] = best[:, 0]
+    return seq

@@ -15,6 +15,7 @@ call per step (the reference loops over clips, base.py:266) with the reference's
 device->host copy per step.
 """
 import ctypes
+import math
 import os
 import weakref
 
@@ -43,6 +44,7 @@ class CaptionMetaMixin:
 
 
 N_SAMPLES = "n_samples (several sampled captions per clip from one encoder pass)"   # how the refusals name the feature
+GROUP_BEAM = "group_size (group beam search: group_size groups of beam_size // group_size beams, a diversity penalty between them)"
 
 
 class CaptionModel(nn.Module, CaptionMetaMixin):
@@ -72,6 +74,7 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             return train_forward(self, input_dict)
         self._check_n_samples(input_dict)      # refused on the host, before the encoder runs
         self._check_logit_rules(input_dict)
+        self._check_group_beam(input_dict)
         encoder_output_dict = self.encoder(input_dict)
         output = self.forward_decoder(input_dict, encoder_output_dict)
         flags = _device_flags(output)
@@ -128,12 +131,20 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
         logit_rules.refuse(input_dict, type(self).__name__)
         return None
 
+    def _check_group_beam(self, input_dict):
+        """``input_dict["group_size"]``, beam search in groups with a diversity penalty between them, is built for
+        ``TransformerModel`` (which overrides this): NotImplementedError naming the key everywhere else."""
+        if input_dict.get("group_size") is not None:
+            raise NotImplementedError(f"{type(self).__name__}: {GROUP_BEAM} is built for TransformerModel only")
+        return None
+
     def forward_decoder(self, input_dict, encoder_output_dict):
         if input_dict["mode"] == "train":
             raise NotImplementedError("mode='train' is handled by CaptionModel.forward as one fused step")
         elif input_dict["mode"] == "inference":
             self._check_n_samples(input_dict)
             self._check_logit_rules(input_dict)
+            self._check_group_beam(input_dict)
             output = self.inference_forward(self._inference_dict(input_dict, encoder_output_dict))
         else:
             raise Exception("mode should be either 'train' or 'inference'")
@@ -150,6 +161,11 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
             forward_dict["beam_size"] = input_dict.get("beam_size", 3)
             forward_dict["n_best"] = input_dict.get("n_best", False)
             forward_dict["n_best_size"] = input_dict.get("n_best_size", forward_dict["beam_size"])
+            if input_dict.get("group_size") is not None:   # group beam search (checked by _check_group_beam), base.py:100-103
+                forward_dict["beam_size"] = input_dict.get("beam_size", 6)
+                forward_dict["group_size"] = input_dict["group_size"]
+                forward_dict["diversity_lambda"] = input_dict.get("diversity_lambda", 0.5)
+                forward_dict["group_nbest"] = input_dict.get("group_nbest", True)
         if input_dict.get("seed") is not None:    # sampling: the caller's 64-bit seed (otherwise drawn per call)
             forward_dict["seed"] = input_dict["seed"]
         if input_dict.get("_seq_on_device"):      # ScstWrapper's baseline: the device copy of the words as well ("seq_dev")
@@ -165,13 +181,16 @@ class CaptionModel(nn.Module, CaptionMetaMixin):
     def inference_forward(self, input_dict):
         method = input_dict["sample_method"]
         if method == "beam":
+            if input_dict.get("group_size") is not None:
+                return self.group_beam_search(input_dict)
             return self.beam_search(input_dict)
         if method == "greedy":
             return self.greedy_search(input_dict)
         if method == "dbs":
             # the reference's TransformerModel has no prepare_dbs_decoder_input either: it raises there too
             raise NotImplementedError(
-                "sample_method='dbs': diverse beam search is not on the accelerated path (SURVEY.md §2.1 row 7)")
+                "sample_method='dbs' is refused by name, as in the reference's TransformerModel; TransformerModel runs diverse "
+                "beam search as sample_method='beam' with group_size (diversity_lambda, group_nbest)")
         return self.sample_search(input_dict)
 
 
@@ -306,6 +325,8 @@ class TransformerModel(CaptionModel):
         if input_dict.get("n_samples") is not None:
             raise NotImplementedError(f"forward_async: {N_SAMPLES} is not built for it; use model(input_dict)")
         logit_rules.refuse(input_dict, "forward_async (shared greedy chains, deferred beam searches)")
+        if input_dict.get("group_size") is not None:
+            raise NotImplementedError(f"forward_async: {GROUP_BEAM} is not built for it; use model(input_dict)")
         if input_dict.get("mode") != "inference" or method not in ("greedy", "beam"):
             raise NotImplementedError("forward_async: greedy or beam inference only; use model(input_dict) otherwise")
         if method == "beam":
@@ -597,6 +618,42 @@ class TransformerModel(CaptionModel):
                                              self.start_idx, self.end_idx)
         return None if rules.neutral else rules
 
+    def _check_group_beam(self, input_dict):
+        """The group beam search of a request as ``(group_size, bdash, diversity_lambda, group_nbest)`` with the reference's
+        defaults (base.py:100-103), or None when ``group_size`` is absent or None: the plain searches.  ValueError, before
+        anything is launched, for a value the search does not take; NotImplementedError (naming the key) beside a non-neutral
+        logit rule.  ``sample_method="dbs"`` is left to the refusal of that name."""
+        G = input_dict.get("group_size")
+        method = input_dict.get("sample_method", "greedy")
+        if G is None or method == "dbs":
+            return None
+        if isinstance(G, bool) or not isinstance(G, int) or not 1 <= G <= 8:
+            raise ValueError(f"group_size must be an int in 1..8, got {G!r}")
+        if method != "beam":
+            raise ValueError(f"group_size: {GROUP_BEAM} takes sample_method='beam', got {method!r}")
+        beam = input_dict.get("beam_size", 6)
+        if isinstance(beam, bool) or not isinstance(beam, int) or not 1 <= beam // G <= 8:
+            raise ValueError(f"group_size={G}: beam_size // group_size must be in 1..8, got beam_size={beam!r}")
+        lam = input_dict.get("diversity_lambda", 0.5)
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam) or lam < 0:
+            raise ValueError(f"diversity_lambda must be a finite number >= 0, got {lam!r}")
+        nbest = input_dict.get("group_nbest", True)
+        if not isinstance(nbest, bool):
+            raise ValueError(f"group_nbest must be a bool, got {nbest!r}")
+        for key in ("n_best", "n_best_size"):
+            if input_dict.get(key) is not None:
+                raise ValueError(f"{key} ranks the beams of ONE search; with group_size the result is shaped by group_nbest")
+        temp = input_dict.get("temp", 1.0)
+        if isinstance(temp, bool) or not isinstance(temp, (int, float)) or not math.isfinite(temp) or temp <= 0:
+            raise ValueError(f"group_size: beam search needs a finite temp > 0, got {temp!r}")
+        if self.vocab_size > 8192:
+            raise ValueError(f"group_size: the group selection holds a row of at most 8192 logits in registers (vocabulary "
+                             f"{self.vocab_size})")
+        if self._check_logit_rules(input_dict) is not None:
+            raise NotImplementedError(f"{type(self).__name__}: {GROUP_BEAM} is not built beside repetition and word "
+                                      f"constraints ({', '.join(k for k in logit_rules.KEYS if input_dict.get(k) is not None)})")
+        return G, beam // G, float(lam), nbest
+
     # ---- greedy (base.py:152-218) -----------------------------------------------------------------
     def greedy_search(self, input_dict):
         if input_dict.get("temp", 1.0) != 1.0:
@@ -774,6 +831,88 @@ class TransformerModel(CaptionModel):
             "embed": torch.empty(B, max_length, dec.d_model, device=dev),
         }
 
+    # ---- group (diverse) beam search (base.py:363-471), all clips batched -------------------------------------
+    def group_beam_search(self, input_dict):
+        """``sample_method="beam"`` with ``group_size`` = G: G groups of bdash = beam_size // G beams per clip, staggered in
+        time (group g makes its step lt = t - g at global step t), each a beam search whose scores lose
+        ``diversity_lambda`` per row of an earlier group of the clip that holds the same word at the same position
+        (``ac_group_beam_select``).  No clip retires and nothing exits early, so the whole search is ONE fixed launch sequence -
+        per group step ``ac_trm_step_logits``, the selection, ``ac_trm_beam_update_all`` and ``ac_trm_beam_reorder``, the groups
+        one after another on the current stream - eager on the first use of a shape, one graph from the second on.
+
+        ``seq`` (B, beam_size, max_length) int64 on the CPU, group 0's bdash captions (best first), then group 1's ... (rows
+        beyond G * bdash stay ``end_idx``); with ``group_nbest=False`` (B, G, max_length), the best of each group.  ``logit``,
+        ``embed`` and ``sampled_logprob`` as ``beam_search`` returns them (unfilled).  With ``_seq_on_device`` also
+        ``seq_dev``, the same words on the device, what ``Diversity.score_groups`` takes as it is."""
+        dec = self.decoder
+        attn_emb = input_dict["attn_emb"]
+        dev = attn_emb.device
+        B, Tm, A = attn_emb.shape
+        beam = int(input_dict["beam_size"])
+        G = int(input_dict["group_size"])
+        bdash = beam // G
+        lam = float(input_dict.get("diversity_lambda", 0.5))
+        nbest = bool(input_dict.get("group_nbest", True))
+        max_length = int(input_dict["max_length"])
+        temp = float(input_dict["temp"])
+        V = self.vocab_size
+        R, cap = B * bdash, bdash * max_length
+        lib = _lib.load()
+        dec.weights()                              # first: an unsupported decoder shape is refused before any buffer exists
+        key = (dev, B, Tm, A, beam, max_length, temp, self.start_idx, self.end_idx, self.pad_idx, dec._weights_key(), 0,
+               G, bdash, lam, nbest)
+        if getattr(self, "_group_beam_state", None) is None:
+            self._group_beam_state = {}
+
+        def build():
+            f32 = dict(device=dev, dtype=torch.float32)
+            ws_n = lib.ac_trm_workspace_floats(ctypes.byref(dec.weights()), R, max_length)
+            if ws_n <= 0:
+                raise _lib.HipLibraryError(f"ac_trm_workspace_floats rejected {R} rows of {max_length} positions")
+            # per group a beam book and a decoder workspace (its own KV cache); ONE projected audio memory for all of them
+            books = [{**search_state.beam_buffers(dev, B, bdash, max_length, self.start_idx, self.end_idx, self.pad_idx),
+                      "ws": torch.empty(ws_n, **f32)} for _ in range(G)]
+            return {"graph": None, "books": books, "logit": torch.empty(R, V, **f32),
+                    "scratch": torch.empty(2 * R * bdash, **f32),
+                    "attn_emb": torch.empty(B, Tm, A, **f32), "mem_len": torch.empty(B, device=dev, dtype=torch.int32),
+                    "memkv": torch.empty(dec.nlayers, B * Tm, 2 * dec.d_model, **f32),
+                    "tmp": torch.empty(B * Tm, dec.d_model, **f32)}
+        st = search_state.lookup(self._group_beam_state, key, build, 4)
+        st["attn_emb"].copy_(K.f32c(attn_emb))
+        st["mem_len"].copy_(K.upload(input_dict["attn_emb_len"], dev, torch.int32))
+        books = st["books"]
+        w = ctypes.byref(dec.weights())
+
+        def launch():
+            for book in books:
+                search_state.beam_reset(book, B)
+            dec._memory_launch(st)
+            for g, lt in search_state.group_steps(G, max_length):
+                book = books[g]
+                check(lib.ac_trm_step_logits(w, ptr(st["memkv"]), ptr(st["mem_len"]), R, bdash, Tm, max_length, lt,
+                                             ptr(book["tok"][lt & 1]), ptr(book["mask"]), lt & 1, ptr(st["logit"]), V, None, 0,
+                                             ptr(book["ws"]), stream()), "ac_trm_step_logits")
+                check(lib.ac_group_beam_select(ptr(st["logit"]), V, B, bdash, V, lt, temp, lam, ptr(book["cum"]),
+                                               search_state.group_prev_planes(books, g, lt, max_length), g, max_length + 1,
+                                               ptr(book["top_val"]), ptr(book["top_idx"]), ptr(st["scratch"]), stream()),
+                      "ac_group_beam_select")
+                search_state.beam_update(book, lt, B, bdash, V, max_length, self.end_idx, self.pad_idx, cap, all_rows=True)
+                if lt + 1 < max_length:
+                    check(lib.ac_trm_beam_reorder(w, R, max_length, lt, ptr(book["src_row"]), ptr(book["ws"]), stream()),
+                          "ac_trm_beam_reorder")
+
+        search_state.run(st, dev, launch)
+        seq = search_state.group_rank(books, B, bdash, max_length, self.end_idx, beam, nbest)
+        out = {
+            "seq": seq,
+            "logit": torch.empty(B, max_length, V, device=dev),
+            "sampled_logprob": torch.zeros(B, max_length),
+            "embed": torch.empty(B, max_length, dec.d_model, device=dev),
+        }
+        if input_dict.get("_seq_on_device"):
+            out["seq_dev"] = seq.to(dev)
+        return out
+
 
 class KeywordCondTransformerModel(TransformerModel):
     """The reference's ``KeywordCondTransformerModel`` (transformer_model.py:223-264) over a
@@ -811,6 +950,11 @@ class KeywordCondTransformerModel(TransformerModel):
 
     def _check_logit_rules(self, input_dict):
         logit_rules.refuse(input_dict, "KeywordCondTransformerModel")
+        return None
+
+    def _check_group_beam(self, input_dict):
+        if input_dict.get("group_size") is not None:
+            raise NotImplementedError(f"KeywordCondTransformerModel: {GROUP_BEAM} is not built for keyword conditioning")
         return None
 
     def _search_kwargs(self, input_dict):

@@ -519,6 +519,28 @@ int ac_ens_sample_pick(const float* const* logits, int n_models, long ld, int ro
 int ac_ens_beam_step_select(const float* const* logits, int n_models, long ld, int B, int beam, int V, int t, float temp,
                             const float* cum_logprob, float* top_val, int* top_idx, float* scratch, void* stream);
 
+/* ---- group (diverse) beam search (base.py:363-471 diverse_beam_search; csrc/group_beam.hip) -------------
+ * G groups of bdash beams per clip, staggered in time: at global step t group g stands at its local position lt = t - g.  A
+ * group's step is ac_trm_step_logits over its own B * bdash rows, this selection, ac_trm_beam_update_all (t = lt, beam =
+ * bdash) and ac_trm_beam_reorder; the groups of a step run in the order g = 0, 1, ...
+ *
+ * ac_group_beam_select: logit holds B * bdash rows of V raw logits z at stride ldl >= V.  Per row
+ *   lp = log_softmax(log_softmax(z) / temp);  lp[w] -= count[w] * diversity_lambda;  cand = cum[row] + lp
+ * where count[w] is the number of rows, among the n_prev * bdash rows of the earlier groups of the same clip, whose word at
+ * local position lt is w (the product and the subtraction are each rounded to f32 once; with n_prev == 0 or lambda == 0
+ * the scores carry the bits of the un-penalised ones).  prev_tok: a HOST array of n_prev (0 .. AC_GROUP_BEAM_MAX_GROUPS - 1)
+ * device pointers, each one earlier group's CURRENT token plane [B * bdash][tok_ld] (column 0 the start token, so column
+ * lt + 1 is read; tok_ld >= lt + 2); the pointers are copied into the launch arguments, so a captured graph keeps them.
+ * Per clip the bdash best of the flattened bdash * V candidates (only the clip's first row at lt == 0), the lowest flattened
+ * index first among equals: top_val / top_idx [B][bdash], beam_i * V + word, as ac_trm_beam_update_all reads them.
+ * scratch: 2 * B * bdash * bdash words.  No allocation, no synchronisation.
+ * AC_ERR_ARG (nothing is launched): bdash outside 1 .. 8 or above V, n_prev outside 0 .. 7, V outside 1 .. 8192, ldl < V,
+ * lt < 0, temp not finite or <= 0, diversity_lambda not finite or < 0, B < 1, a null pointer. */
+#define AC_GROUP_BEAM_MAX_GROUPS 8
+int ac_group_beam_select(const float* logit, long ldl, int B, int bdash, int V, int lt, float temp,
+                         float diversity_lambda, const float* cum, const int* const* prev_tok, int n_prev, long tok_ld,
+                         float* top_val, int* top_idx, float* scratch, void* stream);
+
 /* ---- repetition and word constraints of a search (csrc/logit_rules.hip) -------------
  * At step t (0-based) a row has generated g = tokens[1 .. t] - t words, the start token in column 0 is not one of them - and
  * z is its row of raw logits.  In this order:
