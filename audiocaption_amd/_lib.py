@@ -234,6 +234,13 @@ SIGNATURES = {
     "ac_effnet_expand_depthwise": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     # waveform ingest (csrc/ingest.hip)
     "ac_ingest_resample": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    # HTS-AT encoder (csrc/htsat.hip)
+    "ac_htsat_patch_embed": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "ac_swin_window_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ac_swin_patch_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ac_htsat_pool": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ac_htsat_token_mean": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ac_gelu": (_I, [_P, _P, _L, _P]),
     "ac_mfma_bf16_probe": (_I, [_P, _I, _I, _P]),
     "ac_placement_probe": (_I, [_P, _I, _I, _I, _P]),
     "ac_stream_create_cu_mask": (_I, [_I, _I, _P]),

@@ -415,6 +415,58 @@ def trm_encoder_state(prefix="", attn_feat_dim=2048, d_model=256, nlayers=2, dim
     return out
 
 
+def htsat_state(prefix="", seed=BASE_SEED, depths=(2, 2, 6, 2), embed_dim=96, num_heads=(4, 8, 16, 32)):
+    """Htsat parameters and ``bn0`` (reference transformer_encoder.py:783-827); the ``relative_position_index`` /
+    ``attn_mask`` / ``melspec_extractor`` buffers are constants of the constructor and are not generated.  LayerNorm
+    weights and biases, linear biases and the relative-position tables are non-trivial, and the weights are scaled so that
+    every block changes the residual stream by a visible fraction (an initialisation-sized network would hide a wrong
+    window, mask or bias behind the skip connections)."""
+    out = {}
+
+    def ln(p, c):
+        out[p + ".weight"] = _uniform(p + ".weight", (c,), 0.8, 1.2, seed)
+        out[p + ".bias"] = _uniform(p + ".bias", (c,), -0.1, 0.1, seed)
+
+    def lin(p, n, k, std, bias=True):
+        out[p + ".weight"] = _normal(p + ".weight", (n, k), std, seed)
+        if bias:
+            out[p + ".bias"] = _uniform(p + ".bias", (n,), -0.1, 0.1, seed)
+
+    _bn(prefix + "bn0", 64, out, seed)
+    out[prefix + "bn0.running_mean"] = _uniform(prefix + "bn0.running_mean", (64,), -30.0, -20.0, seed)
+    out[prefix + "bn0.running_var"] = _uniform(prefix + "bn0.running_var", (64,), 25.0, 40.0, seed)
+    k = prefix + "patch_embed.proj.weight"
+    out[k] = _normal(k, (embed_dim, 1, 4, 4), 0.25, seed)
+    out[prefix + "patch_embed.proj.bias"] = _uniform(prefix + "patch_embed.proj.bias", (embed_dim,), -0.1, 0.1, seed)
+    ln(prefix + "patch_embed.norm", embed_dim)
+    for s, depth in enumerate(depths):
+        c, h = embed_dim << s, num_heads[s]
+        for b in range(depth):
+            bp = f"{prefix}layers.{s}.blocks.{b}."
+            ln(bp + "norm1", c)
+            k = bp + "attn.relative_position_bias_table"
+            out[k] = _normal(k, (225, h), 0.5, seed)
+            lin(bp + "attn.qkv", 3 * c, c, 1.0 / math.sqrt(c))
+            lin(bp + "attn.proj", c, c, 0.5 / math.sqrt(c))
+            ln(bp + "norm2", c)
+            lin(bp + "mlp.fc1", 4 * c, c, 1.0 / math.sqrt(c))
+            lin(bp + "mlp.fc2", c, 4 * c, 0.5 / math.sqrt(4 * c))
+        if s < len(depths) - 1:
+            ln(f"{prefix}layers.{s}.downsample.norm", 4 * c)
+            lin(f"{prefix}layers.{s}.downsample.reduction", 2 * c, 4 * c, 1.0 / math.sqrt(4 * c), bias=False)
+    ln(prefix + "norm", embed_dim << (len(depths) - 1))
+    return out
+
+
+def htsat_trm_state(vocab_size=4368, seed=BASE_SEED, depths=(2, 2, 6, 2)):
+    """State dict of the Htsat-Transformer captioner (``config.htsat_trm_config``): ``encoder.*`` from ``htsat_state``,
+    ``decoder.*`` a 2-layer TransformerDecoder over the 768-wide memory."""
+    out = {}
+    out.update(htsat_state("encoder.", seed, depths))
+    out.update(decoder_state("decoder.", vocab_size, 256, 768, 2, 1024, seed))
+    return out
+
+
 def synthetic_wav(batch, n_samples, seed=BASE_SEED, varied=False, sample_rate=32000):
     """wav = clip(0.1*N(0,1), -1, 1), fp32, shape (B, L).
 

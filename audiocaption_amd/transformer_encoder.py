@@ -96,3 +96,8 @@ class TransformerEncoder(nn.Module):
             x = torch.empty(N, L, d, **f32)
             add_ln(sub, y, layer.norm2, x, rows)
         return {"attn_emb": x, "fc_emb": x[:, 0], "attn_emb_len": lens}
+
+
+# The reference keeps its HTS-AT encoder in the same module (transformer_encoder.py:679-996); re-export ours so that
+# ``captioning.models.transformer_encoder.Htsat`` resolves after ``compat.install()``.
+from .htsat import Htsat  # noqa: E402,F401

@@ -1198,6 +1198,38 @@ int ac_ingest_resample(const void* src, int src_half, const long* src_off, const
                        const int* tap_hi, float* out, const int* out_len, const int* out_start, int B, int lmax, int orig,
                        int new_, int width, void* stream);
 
+/* ============================== HTS-AT encoder (transformer_encoder.py:679-996), csrc/htsat.hip ==============================
+ * A Swin Transformer over the log-mel folded into a 256 x 256 image.  Its linear layers run on ac_gemm / ac_gemm_bf16x3 and its
+ * pre-norm LayerNorms on ac_add_layernorm; the entry points below are everything else.  Tokens are row-major over (image
+ * row / 4, image column / 4), activations [B][H*W][C] f32.  Every entry point refuses a geometry it does not cover
+ * (AC_ERR_ARG) before it launches anything.
+ *
+ * Patch embedding in one kernel: x = the bn0-normalised log-mel rows of ac_logmel, [B][T][64] dense, T <= 1024.  T < 1024: the time axis is stretched to 1024 frames with torch's bicubic (align_corners,
+ * A = -0.75, clamped borders; transformer_encoder.py:940-941); frame f, mel m is image row (f / 256) * 64 + m, column
+ * f % 256 (:944-949); then the 4x4 / stride 4 convolution w [C][16] + bias and LayerNorm (:209-220).  out [B][4096][C],
+ * C <= 256; w 16-byte aligned. */
+int ac_htsat_patch_embed(const float* x, int B, int T, const float* w, const float* bias,
+                         const float* ln_w, const float* ln_b, float* out, int C, void* stream);
+/* (Shifted-)window attention over 8 x 8 windows, heads of width 24 (C = 24 * heads), H and W multiples of 8:
+ * qkv [B][H*W][3C] (q, k, v of all heads per token) -> out [B][H*W][C].  shift (0 .. 7; > 0 needs H, W > 8): the window grid
+ * lies on the image rolled by -shift along both axes (gathered and scattered by addressing), and scores between tokens of
+ * different regions of the rolled image (:500-519) get -100.  softmax(q k^T / sqrt(24) + bias[head] + mask) v with
+ * bias [heads][64][64] = relative_position_bias_table[relative_position_index] (:424-427), gathered by the caller once per
+ * weight pack.  Exact-f32 matrix products.  Replaces :411-442 and :533-555. */
+int ac_swin_window_attn(const float* qkv, const float* bias, float* out, int B, int H, int W, int C, int heads, int shift,
+                        void* stream);
+/* PatchMerging without its reduction (:592-601): out [B][H/2*W/2][4C] = LayerNorm over the concatenation of x(2i, 2j),
+ * x(2i+1, 2j), x(2i, 2j+1), x(2i+1, 2j+1); H, W even, 4C <= 1536. */
+int ac_swin_patch_merge(const float* x, const float* ln_w, const float* ln_b, float* out, int B, int H, int W, int C,
+                        void* stream);
+/* The tail (:903-912): x [B][Hh*Ww][C] (after the final LayerNorm); token row k * fbins + f is frequency bin f of time chunk
+ * k.  attn [B][(Hh/fbins)*Ww][C]: frame k * Ww + w = mean over f; fc [B][C] = mean over all frames (not masked by length). */
+int ac_htsat_pool(const float* x, float* attn, float* fc, int B, int Hh, int Ww, int C, int fbins, void* stream);
+/* out [B][C] = mean over the N tokens of x [B][N][C]: the layer_i embeddings (:888-897). */
+int ac_htsat_token_mean(const float* x, float* out, int B, int N, int C, void* stream);
+/* y[i] = x[i] * Phi(x[i]), the exact (erf) GELU of Mlp (:228-243); y may be x. */
+int ac_gelu(const float* x, float* y, long n, void* stream);
+
 /* Diagnostic (bench.py, not the hot path): `blocks` workgroups of 4 waves each issue iters x 32 dependent-free
  * v_mfma_f32_32x32x16_bf16 (8 accumulators per wave, no memory traffic); out[blocks * 256] receives the accumulator sums.
  * FLOPs = blocks * 4 * iters * 32 * 32768.  Timed by the caller, it gives the matrix rate the part sustains at the clock it
