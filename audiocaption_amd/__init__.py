@@ -1,7 +1,8 @@
 """MI355X-native audio-captioning forward/decode path (Cnn14Rnn-Trm), behind the plugin API of
 wsntxxn/AudioCaption.  See DESIGN.md / INTEGRATION.md."""
-from .cnn_encoder import Cnn14Encoder
-from .config import cnn14rnn_keyword_trm_config, cnn14rnn_trm_config, effb2_trm_config, htsat_trm_config, init_model_from_config
+from .cnn_encoder import Cnn6Encoder, Cnn10Encoder, Cnn14Encoder
+from .config import (cnn6rnn_trm_config, cnn10rnn_trm_config, cnn14rnn_keyword_trm_config, cnn14rnn_trm_config, effb2_trm_config,
+                     htsat_trm_config, init_model_from_config)
 from .effnet_encoder import EfficientNetB2
 from .htsat import Htsat
 from .crnn_trm_encoder import Cnn14RnnEncoder, CrnnEncoder
@@ -27,4 +28,5 @@ __all__ = ["Cnn14Encoder", "RnnEncoder", "CrnnEncoder", "Cnn14RnnEncoder", "Tran
            "Seq2SeqAttnModel", "TemporalSeq2SeqAttnModel", "ConditionalBahAttnDecoder", "SpecificityBahAttnDecoder",
            "ConditionalSeq2SeqAttnModel", "SpecificityLossWrapper", "Cnn8rnnSedModel", "EnsembleModel", "ScstWrapper", "Cider", "Bleu", "Rouge", "Diversity", "TokenLevelKdLoss", "SupKdLoss",
            "MseEncoderKdWrapper", "ContraEncoderKdWrapper", "ContraMseEncoderKdWrapper", "init_model_from_config", "cnn14rnn_trm_config",
-           "KeywordProbTransformerDecoder", "KeywordCondTransformerModel", "cnn14rnn_keyword_trm_config", "LogitRules", "Htsat", "htsat_trm_config"]
+           "KeywordProbTransformerDecoder", "KeywordCondTransformerModel", "cnn14rnn_keyword_trm_config", "LogitRules", "Htsat", "htsat_trm_config",
+           "Cnn6Encoder", "Cnn10Encoder", "cnn6rnn_trm_config", "cnn10rnn_trm_config"]

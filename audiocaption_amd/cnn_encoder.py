@@ -7,6 +7,10 @@ The torch.nn sub-modules below only OWN the parameters (so checkpoints, ``.to()`
 ``named_parameters`` behave exactly like the reference); the forward pass never calls them: it runs
 log-mel -> bn0 -> 12 x (conv3x3 + BN + ReLU [+ pool]) -> mean over mel entirely in the HIP kernels of
 ``csrc/logmel.hip`` and ``csrc/conv3x3.hip`` and fails loudly if they are unavailable.
+
+``Cnn10Encoder`` and ``Cnn6Encoder`` (reference cnn_encoder.py:222-327, :114-219) are the light encoders of the same family,
+for inference: Cnn10 is the first four conv blocks on the same conv tiers, Cnn6 four 5x5 convolutions on the kernels of
+``csrc/conv5x5.hip``.  The three classes share the mel front, the pack cache and the buffers (``_PannsEncoder``).
 """
 import dataclasses
 import os
@@ -279,10 +283,11 @@ def conv_tier(algo):
         raise ValueError(f"unknown conv_algo {algo!r}") from None
 
 
-class Cnn14Encoder(nn.Module):
+class _PannsEncoder(nn.Module):
+    """What the PANNs waveform encoders of this module share: the mel front (log-mel + bn0 in the conv stack's layout), the
+    cache of packed weights and the activation buffers.  A subclass gives ``geometry``, ``effective_algo`` and ``_pack``."""
 
-    def __init__(self, sample_rate=32000, freeze=False):
-        super().__init__()
+    def _init_front(self, sample_rate):
         sr_to_fmax = {32000: 14000, 16000: 8000}
         self.sample_rate = sample_rate
         self.n_fft = 32 * sample_rate // 1000
@@ -291,6 +296,79 @@ class Cnn14Encoder(nn.Module):
         self.melspec_extractor = MelSpectrogramBuffers(sample_rate, self.n_fft, self.f_min, self.f_max, 64, "slaney",
                                                        "slaney")
         self.bn0 = nn.BatchNorm2d(64)
+        self._tables = None
+        self._tables_key = None
+        self._packed = {}   # conv tier -> (key of the tensors it was packed from, packed weights)
+        self._bufs = {}
+
+    # ---- weight packing for the kernels (cached; invalidated by in-place updates / .to()) ----------
+    def _cached_pack(self, algo, layers, variant, build):
+        """The pack of ``algo``: ``build(fold)`` (``fold(bn)`` -> BN scale, shift) unless the cached one was built from the
+        same tensors - bn0 and the (conv, bn) pairs ``layers`` - and the same ``variant`` of the tier."""
+        tensors = [self.bn0.weight, self.bn0.bias, self.bn0.running_mean, self.bn0.running_var]
+        for conv, bn in layers:
+            tensors += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        # Keyed on the tensors themselves (address, torch version counter, and the per-tensor counter HIP optimisers
+        # bump), NOT on the global parameter generation: an optimiser step on the GRU / decoder must not repack the
+        # frozen Cnn14 - captured training graphs hold the addresses of this pack (and a repack costs ~0.3 s).
+        key = tuple((t.data_ptr(), t._version, K._lib.tensor_generation(t)) for t in tensors) + (algo, variant)
+        hit = self._packed.get(algo)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+
+        def fold(bn):
+            return K.fold_bn(bn.weight.float(), bn.bias.float(), bn.running_mean.float(), bn.running_var.float(), bn.eps)
+
+        with torch.no_grad():
+            pk = build(fold)
+        self._packed[algo] = (key, pk)
+        return pk
+
+    def _buf(self, name, numel, device, dtype=torch.float32):
+        b = self._bufs.get((name, dtype))
+        if b is None or b.numel() < numel or b.device != device:
+            b = torch.empty(numel, device=device, dtype=dtype)
+            self._bufs[(name, dtype)] = b
+        return b
+
+    def capture_token(self, algo):
+        """(identity, references) of everything a captured graph of this encoder's launches addresses: the packed weights
+        of ``algo`` and the shared activation buffers.  A graph owner keeps the references for as long as the graph lives
+        and re-captures when the identity changes (a larger batch shape re-allocates the buffers)."""
+        hit = self._packed.get(algo)
+        ident = (id(hit[1]) if hit is not None else None,) + tuple(sorted((k[0], str(k[1]), b.data_ptr())
+                                                                           for k, b in self._bufs.items()))
+        return ident, (hit, dict(self._bufs), self._tables)
+
+    def logmel_front(self, wav):
+        """The first kernel of ``encode`` on its own (log-mel + bn0 in the conv stack's layout), so that a caller can run it
+        on another stream ahead of the convolutions (TransformerModel.forward_async); pass the result back as ``x0``."""
+        dev = wav.device
+        self._ensure_tables(dev)
+        pk = self._pack(dev, self.effective_algo(None, False, None))
+        Hp = self.geometry(wav.shape[1])[2]
+        return K.logmel(wav, self._tables, pk["bn0"][0], pk["bn0"][1], rows_per_clip=Hp[0], channels_last=True)
+
+    def _fc_emb(self, attn_emb, feat_length):
+        """The encoder's own clip embedding relu(fc1(max_with_lens + mean_with_lens)) (cnn_encoder.py:208-213, :451-456)."""
+        lens = K.upload(feat_length, attn_emb.device, torch.int32)
+        pooled = K.mean_with_lens(attn_emb, lens, add_max=True)
+        return K.linear(pooled, self.fc1.weight.float(), self.fc1.bias.float(), relu=True)
+
+    def _ensure_tables(self, dev):
+        mkey = self.melspec_extractor.key()
+        if self._tables is None or self._tables.window.device != dev or self._tables_key != mkey:
+            self._tables = MelTables(self.sample_rate, self.n_fft, self.hop_length, self.f_min, self.f_max, 64,
+                                     "slaney", "slaney", dev, window=self.melspec_extractor.spectrogram.window,
+                                     fb=self.melspec_extractor.mel_scale.fb)
+            self._tables_key = mkey
+
+
+class Cnn14Encoder(_PannsEncoder):
+
+    def __init__(self, sample_rate=32000, freeze=False):
+        super().__init__()
+        self._init_front(sample_rate)
         for b in range(6):
             setattr(self, f"conv_block{b + 1}", ConvBlock(CHANNELS[b], CHANNELS[b + 1]))
         self.downsample_ratio = 32
@@ -304,10 +382,6 @@ class Cnn14Encoder(nn.Module):
         # The "f16x2" tier is MIXED (``ConvTier.block6``): block 6 runs on the split-bf16 kernel with f32 activations;
         # block 5's pooled output is then written as f32.  "f16x2" here restores the pure fp16 tier.
         self.f16x2_block6 = os.environ.get("AUDIOCAPTION_F16X2_BLOCK6", "bf16x3")
-        self._tables = None
-        self._tables_key = None
-        self._packed = {}   # conv tier -> (key of the tensors it was packed from, packed weights)
-        self._bufs = {}
 
     # ---- checkpoint hook (reference cnn_encoder.py:376-412: PANNs / COLA / BLAT layouts) ----------
     def load_pretrained(self, pretrained, output_fn=print):
@@ -330,28 +404,14 @@ class Cnn14Encoder(nn.Module):
             for name, param in self.named_parameters():
                 param.requires_grad = name not in loaded
 
-    # ---- weight packing for the kernels (cached; invalidated by in-place updates / .to()) ----------
     def _pack(self, device, algo=None):
         algo = algo or self.conv_algo
         tier = conv_tier(algo)
         tier6 = conv_tier(tier.block6) if tier.block6 is not None and tier.block6 == self.f16x2_block6 else tier
         layers = [(b, conv, bn) for b, blk in enumerate(getattr(self, f"conv_block{b + 1}") for b in range(6))
                   for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2))]
-        tensors = [self.bn0.weight, self.bn0.bias, self.bn0.running_mean, self.bn0.running_var]
-        for _, conv, bn in layers:
-            tensors += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        # Keyed on the tensors themselves (address, torch version counter, and the per-tensor counter HIP optimisers
-        # bump), NOT on the global parameter generation: an optimiser step on the GRU / decoder must not repack the
-        # frozen Cnn14 - captured training graphs hold the addresses of this pack (and a repack costs ~0.3 s).
-        key = tuple((t.data_ptr(), t._version, K._lib.tensor_generation(t)) for t in tensors) + (algo, tier6 is not tier)
-        hit = self._packed.get(algo)
-        if hit is not None and hit[0] == key:
-            return hit[1]
 
-        def fold(bn):
-            return K.fold_bn(bn.weight.float(), bn.bias.float(), bn.running_mean.float(), bn.running_var.float(), bn.eps)
-
-        with torch.no_grad():
+        def build(fold):
             # "convs": (pack, BN scale, BN shift) of the 12 layers; "block6": the tier that packed, and launches, conv block 6;
             # "block1": what the tier's one-kernel block 1 reads beside them
             pk = {"bn0": fold(self.bn0), "convs": [], "block6": tier6, "block1": None}
@@ -367,24 +427,9 @@ class Cnn14Encoder(nn.Module):
                 pk["convs"].append((wp, sc, sh))
             if tier.pack_block1 is not None:
                 pk["block1"] = tier.pack_block1(self.conv_block1.conv2.weight.detach().float())
-        self._packed[algo] = (key, pk)
-        return pk
+            return pk
 
-    def _buf(self, name, numel, device, dtype=torch.float32):
-        b = self._bufs.get((name, dtype))
-        if b is None or b.numel() < numel or b.device != device:
-            b = torch.empty(numel, device=device, dtype=dtype)
-            self._bufs[(name, dtype)] = b
-        return b
-
-    def capture_token(self, algo):
-        """(identity, references) of everything a captured graph of this encoder's launches addresses: the packed weights
-        of ``algo`` and the shared activation buffers.  A graph owner keeps the references for as long as the graph lives
-        and re-captures when the identity changes (a larger batch shape re-allocates the buffers)."""
-        hit = self._packed.get(algo)
-        ident = (id(hit[1]) if hit is not None else None,) + tuple(sorted((k[0], str(k[1]), b.data_ptr())
-                                                                           for k, b in self._bufs.items()))
-        return ident, (hit, dict(self._bufs), self._tables)
+        return self._cached_pack(algo, [(conv, bn) for _, conv, bn in layers], tier6 is not tier, build)
 
     def geometry(self, n_samples):
         """Valid (H) and physical (Hp) row counts of the 6 resolution levels for an L-sample batch."""
@@ -395,23 +440,6 @@ class Cnn14Encoder(nn.Module):
         hp6 = (H[5] + 4) & ~3  # >= H6 + 1 and a multiple of 4 (a row quad of F(4,3) / a pooling pair never straddles clips)
         Hp = [hp6 << (5 - k) for k in range(6)]
         return T, H, Hp
-
-    def logmel_front(self, wav):
-        """The first kernel of ``encode`` on its own (log-mel + bn0 in the conv stack's layout), so that a caller can run it
-        on another stream ahead of the convolutions (TransformerModel.forward_async); pass the result back as ``x0``."""
-        dev = wav.device
-        self._ensure_tables(dev)
-        pk = self._pack(dev, self.effective_algo(None, False, None))
-        Hp = self.geometry(wav.shape[1])[2]
-        return K.logmel(wav, self._tables, pk["bn0"][0], pk["bn0"][1], rows_per_clip=Hp[0], channels_last=True)
-
-    def _ensure_tables(self, dev):
-        mkey = self.melspec_extractor.key()
-        if self._tables is None or self._tables.window.device != dev or self._tables_key != mkey:
-            self._tables = MelTables(self.sample_rate, self.n_fft, self.hop_length, self.f_min, self.f_max, 64,
-                                     "slaney", "slaney", dev, window=self.melspec_extractor.spectrogram.window,
-                                     fb=self.melspec_extractor.mel_scale.fb)
-            self._tables_key = mkey
 
     def encode(self, wav, dropout=None, specaug=None, train=False, min_frames=None, algo=None, overflow=None,
                clip_frames=None, x0=None, block6_f23=False):
@@ -554,11 +582,213 @@ class Cnn14Encoder(nn.Module):
             # TransformerModel re-runs such a batch on the split-bf16 tier; stand-alone callers check it themselves
             out["f16_overflow"] = flag
         if not skip_fc:
-            # Cnn14's own clip embedding (cnn_encoder.py:451-456); CrnnEncoder discards it.
-            lens = K.upload(feat_length, wav.device, torch.int32)
-            pooled = K.mean_with_lens(attn_emb, lens, add_max=True)
-            out["fc_emb"] = K.linear(pooled, self.fc1.weight.float(), self.fc1.bias.float(), relu=True)
+            out["fc_emb"] = self._fc_emb(attn_emb, feat_length)   # CrnnEncoder discards it
         return out
+
+
+class ConvBlock5x5(nn.Module):
+    """Parameter container for one bias-free 5x5 conv + BatchNorm (reference cnn_encoder.py:78-94)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels, out_channels, (5, 5), (1, 1), (2, 2), bias=False)
+        self.bn1 = nn.BatchNorm2d(out_channels)
+        nn.init.xavier_uniform_(self.conv1.weight)
+
+
+class _CnnSmallEncoder(_PannsEncoder):
+    """The four-block PANNs encoders (reference cnn_encoder.py:114-327): 1 -> 64 -> 128 -> 256 -> 512 channels, a 2x2
+    average pool after every block, the mean over the 4 remaining mel columns, ``fc1`` (512 -> 512).  Inference only.  A
+    subclass names its block class and gives ``effective_algo``, ``_pack_layer`` and ``conv_stack``."""
+    block = None
+
+    def __init__(self, sample_rate=32000, freeze=False):
+        super().__init__()
+        self._init_front(sample_rate)
+        for b in range(4):
+            setattr(self, f"conv_block{b + 1}", self.block(CHANNELS[b], CHANNELS[b + 1]))
+        self.downsample_ratio = 16
+        self.fc1 = nn.Linear(512, 512, bias=True)
+        nn.init.xavier_uniform_(self.fc1.weight)
+        nn.init.zeros_(self.fc1.bias)
+        self.fc_emb_size = 512
+        self.freeze = freeze
+
+    def load_pretrained(self, pretrained, output_fn=print):
+        """cnn_encoder.py:159-173 / :267-281: ``checkpoint["model"]`` merged by key and shape; with ``freeze`` the loaded
+        parameters stop training and the others keep training."""
+        from .config import merge_load_state_dict
+        checkpoint = torch.load(pretrained, map_location="cpu")
+        if "model" not in checkpoint:
+            raise Exception("Unkown checkpoint format")
+        loaded = merge_load_state_dict(checkpoint["model"], self, output_fn)
+        if self.freeze:
+            for name, param in self.named_parameters():
+                param.requires_grad = name not in loaded
+
+    def geometry(self, n_samples):
+        """Valid (H) and physical (Hp) row counts of the 5 resolution levels (4 conv levels and the output) for an L-sample
+        batch.  The last level is even and >= H + 2, and Hp_k = 2 * Hp_{k+1}: every conv level then has Hp_k >= H_k + 3 (a
+        5x5 conv reads two rows beyond a clip: they are the clip's own zero rows, csrc/conv5x5.hip), Hp_k % 4 == 0 (a row
+        quad of F(4,3)), and a pooling pair never straddles clips."""
+        T = n_samples // self.hop_length + 1
+        H = [T >> k for k in range(5)]
+        if H[4] < 1:
+            raise ValueError(f"clips of {n_samples} samples ({T} frames) are shorter than one {type(self).__name__} output "
+                             f"frame (16 frames)")
+        hp4 = (H[4] + 3) & ~1
+        return T, H, [hp4 << (4 - k) for k in range(5)]
+
+    def _pack(self, device, algo=None):
+        algo = self.effective_algo(algo)
+        blocks = [getattr(self, f"conv_block{b + 1}") for b in range(4)]
+        layers = [(b, getattr(blk, f"conv{j}"), getattr(blk, f"bn{j}")) for b, blk in enumerate(blocks)
+                  for j in (1, 2) if hasattr(blk, f"conv{j}")]
+
+        def build(fold):
+            # "convs": (pack, BN scale, BN shift) per layer; layer 0 (one input channel) is the plain 64 x taps array
+            pk = {"bn0": fold(self.bn0), "convs": []}
+            for i, (b, conv, bn) in enumerate(layers):
+                w = conv.weight.detach().float()
+                wp, inv = (w.reshape(64, -1).contiguous(), None) if i == 0 else self._pack_layer(algo, w, b, conv.weight)
+                sc, sh = fold(bn)
+                if inv is not None:
+                    sc = (sc * inv).contiguous()
+                pk["convs"].append((wp, sc, sh))
+            self._pack_extra(algo, pk)
+            return pk
+
+        return self._cached_pack(algo, [(conv, bn) for _, conv, bn in layers], None, build)
+
+    def _pack_extra(self, algo, pk):
+        pass
+
+    def encode(self, wav, algo=None, x0=None, blocks=None):
+        """wav (B, L) on the ROCm device -> attn_emb (B, T // 16, 512).  ``x0``: the result of ``logmel_front`` (computed on
+        another stream); ``blocks``: a list that receives a float32 (B, C, H, W) copy of every pooled block output (tests)."""
+        if wav.dim() != 2:
+            raise ValueError("wav must be (batch, samples)")
+        dev = wav.device
+        self._ensure_tables(dev)
+        algo = self.effective_algo(algo)
+        pk = self._pack(dev, algo)
+        B, L = wav.shape
+        T, H, Hp = self.geometry(L)
+        if x0 is None:
+            x0 = K.logmel(wav, self._tables, pk["bn0"][0], pk["bn0"][1], rows_per_clip=Hp[0], channels_last=True)
+        return self.conv_stack(x0, B, H, Hp, pk, algo, blocks=blocks)
+
+    def _head(self, pooled, B, H, Hp, blocks):
+        """Block 4's pooled output [B*Hp[4]][4][512] -> attn_emb (B, H[4], 512): the mean over the 4 mel columns."""
+        attn = torch.empty(B, H[4], 512, device=pooled.device, dtype=torch.float32)
+        return K.rows_mean_w(pooled, attn, B, Hp[4], H[4], 4, 512)
+
+    @staticmethod
+    def _keep(blocks, pooled, B, H, Hp, lvl, W, cout):
+        if blocks is not None:
+            blk = pooled[:B * Hp[lvl] * W * cout].reshape(B, Hp[lvl], W, cout)[:, :H[lvl]]
+            blocks.append(blk.permute(0, 3, 1, 2).float().clone())
+
+    def forward(self, input_dict, skip_fc=False):
+        if self.training:
+            name = type(self).__name__
+            raise NotImplementedError(
+                f"{name} (HIP path): inference only - call .eval(); the train-mode forward (SpecAugment, dropout) and the "
+                f"backward through the convolutions are not built, and the whole-model training step "
+                f"(audiocaption_amd.train.TrainEngine) trains over Cnn14Encoder only")
+        wav = input_dict["wav"]
+        algo = self.effective_algo(input_dict.get("conv_algo"))   # (refusals come before anything is launched)
+        self.geometry(wav.shape[1])
+        feat_length = cnn14_feat_len(input_dict["wav_len"], self.hop_length, self.downsample_ratio)
+        attn_emb = self.encode(wav, algo=algo, x0=input_dict.get("_logmel"))
+        out = {"attn_emb": attn_emb, "attn_emb_len": feat_length}
+        if not skip_fc:
+            out["fc_emb"] = self._fc_emb(attn_emb, feat_length)
+        return out
+
+
+class Cnn10Encoder(_CnnSmallEncoder):
+    """``captioning.models.cnn_encoder.Cnn10Encoder`` (cnn_encoder.py:222-327): the first four conv blocks of Cnn14, on any
+    tier of ``TIERS``.  Dense: ragged batches convolve their padding."""
+    block = ConvBlock
+
+    def __init__(self, sample_rate=32000, freeze=False):
+        super().__init__(sample_rate, freeze)
+        self.conv_algo = os.environ.get("AUDIOCAPTION_CONV_ALGO", "wino43")   # the conv tier: a name of ``TIERS``
+
+    def effective_algo(self, algo=None, train=False, min_frames=None):
+        """The conv tier a call runs on: the mean over mel reads f32, so a tier with half-precision activations hands over
+        to its declared fallback (``Cnn8rnnSedModel.effective_algo``)."""
+        algo = algo or self.conv_algo
+        tier = conv_tier(algo)
+        if tier.act != torch.float32:
+            if tier.fallback is None:
+                raise ValueError(f"conv tier {algo!r} keeps no f32 activations and declares no fallback")
+            return tier.fallback
+        return algo
+
+    def _pack_layer(self, algo, w, b, weight):
+        return conv_tier(algo).pack(w, b, weight)
+
+    def _pack_extra(self, algo, pk):
+        tier = conv_tier(algo)
+        pk["block1"] = tier.pack_block1(self.conv_block1.conv2.weight.detach().float()) if tier.pack_block1 else None
+
+    def conv_stack(self, x0, B, H, Hp, pk, algo, blocks=None):
+        """The four conv blocks on a bn0-normalised log-mel x0 [B*Hp[0]][64] -> attn_emb (B, H[4], 512)."""
+        dev = x0.device
+        tier = conv_tier(algo)
+        full = self._buf("full", B * Hp[0] * 64 * 64, dev)       # conv1 outputs (largest: level 1)
+        pooled = self._buf("pooled", B * Hp[1] * 32 * 64, dev)   # block outputs (largest: block 1)
+        offer = {"workspace": None}
+        if os.environ.get("AUDIOCAPTION_W1_SPLITK", "1") != "0":
+            offer["workspace"] = lambda n: self._buf("w1_splitk", n, dev)
+        fuse1 = os.environ.get("AUDIOCAPTION_FUSE_BLOCK1", "1") != "0"
+        W = 64
+        for b in range(4):
+            cin, cout = CHANNELS[b], CHANNELS[b + 1]
+            conv1, conv2 = pk["convs"][2 * b], pk["convs"][2 * b + 1]
+            one_kernel = b == 0 and fuse1 and tier.block1 is not None \
+                and tier.block1(x0, conv1, conv2, pk["block1"], pooled, B, Hp[0], H[0], None, None, None)
+            if b == 0 and not one_kernel:
+                K.conv3x3_first(x0, *conv1, full, B, Hp[0], H[0], W)
+            elif b > 0:
+                tier.launch(pooled, *conv1, full, B, Hp[b], H[b], W, cin, cout, 0, **offer)
+            if not one_kernel:
+                tier.launch(full, *conv2, pooled, B, Hp[b], H[b], W, cout, cout, 1, **offer)
+            W //= 2
+            self._keep(blocks, pooled, B, H, Hp, b + 1, W, cout)
+        return self._head(pooled, B, H, Hp, blocks)
+
+
+class Cnn6Encoder(_CnnSmallEncoder):
+    """``captioning.models.cnn_encoder.Cnn6Encoder`` (cnn_encoder.py:114-219): four blocks of ONE 5x5 conv + BN + ReLU + 2x2
+    average pool.  One arithmetic: the 5x5 kernels of csrc/conv5x5.hip (block 1 in f32, blocks 2-4 on split-bf16 operands,
+    the 2^-16 operand grade of the "bf16x3" tier)."""
+    block = ConvBlock5x5
+    conv_algo = "conv5x5"
+
+    def effective_algo(self, algo=None, train=False, min_frames=None):
+        if algo is not None and algo != self.conv_algo:
+            raise ValueError(f"Cnn6Encoder runs on its own 5x5 kernels only (conv_algo {self.conv_algo!r}), not {algo!r}")
+        return self.conv_algo
+
+    def _pack_layer(self, algo, w, b, weight):
+        return K.pack_conv5x5_weight(w), None
+
+    def conv_stack(self, x0, B, H, Hp, pk, algo, blocks=None):
+        """The four conv blocks on a bn0-normalised log-mel x0 [B*Hp[0]][64] -> attn_emb (B, H[4], 512)."""
+        dev = x0.device
+        bufs = [self._buf("pooled", B * Hp[1] * 32 * 64, dev), self._buf("pooled_b", B * Hp[2] * 16 * 128, dev)]
+        src = K.conv5x5_first(x0, *pk["convs"][0], bufs[0], B, Hp[0], H[0])
+        self._keep(blocks, src, B, H, Hp, 1, 32, 64)
+        W = 32
+        for b in range(1, 4):
+            cin, cout = CHANNELS[b], CHANNELS[b + 1]
+            src = K.conv5x5_bn_relu_bf16x3(src, *pk["convs"][b], bufs[b & 1], B, Hp[b], H[b], W, cin, cout, 1)
+            W //= 2
+            self._keep(blocks, src, B, H, Hp, b + 1, W, cout)
+        return self._head(src, B, H, Hp, blocks)
 
 
 # The reference keeps its EfficientNet-B2 encoder in the same module (cnn_encoder.py:770-839); re-export ours so that

@@ -13,6 +13,8 @@ import torch
 
 ALIASES = {
     "captioning.models.cnn_encoder.Cnn14Encoder": "audiocaption_amd.cnn_encoder.Cnn14Encoder",
+    "captioning.models.cnn_encoder.Cnn10Encoder": "audiocaption_amd.cnn_encoder.Cnn10Encoder",
+    "captioning.models.cnn_encoder.Cnn6Encoder": "audiocaption_amd.cnn_encoder.Cnn6Encoder",
     "captioning.models.rnn_encoder.RnnEncoder": "audiocaption_amd.rnn_encoder.RnnEncoder",
     "captioning.models.crnn_trm_encoder.CrnnEncoder": "audiocaption_amd.crnn_trm_encoder.CrnnEncoder",
     "captioning.models.crnn_trm_encoder.Cnn14RnnEncoder": "audiocaption_amd.crnn_trm_encoder.Cnn14RnnEncoder",
@@ -149,6 +151,23 @@ def htsat_trm_config(vocab_size=4368, depths=(2, 2, 6, 2)):
         "type": "captioning.models.transformer_model.TransformerModel",
         "args": {},
     }
+
+
+def _cnn_small_rnn_trm_config(cnn, vocab_size):
+    config = cnn14rnn_trm_config(vocab_size)
+    config["encoder"]["cnn"]["type"] = f"captioning.models.cnn_encoder.{cnn}"
+    config["encoder"]["rnn"]["args"].update(fc_feat_dim=512, attn_feat_dim=512)
+    return config
+
+
+def cnn10rnn_trm_config(vocab_size=4368):
+    """``cnn14rnn_trm_config`` over the reference's ``Cnn10Encoder`` (cnn_encoder.py:222): 512-wide features at T // 16."""
+    return _cnn_small_rnn_trm_config("Cnn10Encoder", vocab_size)
+
+
+def cnn6rnn_trm_config(vocab_size=4368):
+    """``cnn14rnn_trm_config`` over the reference's ``Cnn6Encoder`` (cnn_encoder.py:114): 512-wide features at T // 16."""
+    return _cnn_small_rnn_trm_config("Cnn6Encoder", vocab_size)
 
 
 def effb2_trm_config(vocab_size=4981):

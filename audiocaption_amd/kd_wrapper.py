@@ -75,6 +75,14 @@ class _EncoderKdWrapper(nn.Module, CaptionMetaMixin):
     def forward(self, input_dict):
         unsup = input_dict.get("unsup", False)
         kd = "tchr_output" in input_dict
+        if kd and input_dict.get("mode") == "train" and not unsup:
+            from .cnn_encoder import Cnn14Encoder
+            cnn = getattr(getattr(self.model, "encoder", None), "cnn", None)
+            if cnn is not None and not isinstance(cnn, Cnn14Encoder):
+                raise NotImplementedError(f"{type(self).__name__}: encoder knowledge distillation in mode='train' runs on the "
+                                          f"training engines, which are built around Cnn14Encoder; training over "
+                                          f"{type(cnn).__name__} is not built.  Use mode='inference' (or unsup=True) for a "
+                                          f"head-only loss")
         if kd and input_dict.get("mode") == "train" and not unsup and not _trains_encoder(self.model):
             raise NotImplementedError(
                 f"{type(self).__name__}: encoder knowledge distillation in mode='train' needs the gradient of enc_kd_loss "

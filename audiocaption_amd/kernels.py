@@ -154,6 +154,35 @@ def conv3x3_bn_relu_bf16x3_gw(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cou
     return out
 
 
+def conv5x5_first(x, w, scale, shift, out, B, Hp, H):
+    """Block 1 of Cnn6 in one kernel (csrc/conv5x5.hip): x [B*Hp][64] f32, w [64][25], out [B*Hp/2][32][64] f32 = the
+    2x2 average pool of ReLU(BN(conv5x5)).  Hp even and >= H + 2."""
+    check(_lib.load().ac_conv5x5_first(ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(out), B, Hp, H, stream()),
+          "ac_conv5x5_first")
+    return out
+
+
+def conv5x5_bn_relu_bf16x3(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode):
+    """5x5 conv + BN + ReLU (+ 2x2 average pool, ``mode`` 1) on split-bf16 operands (csrc/conv5x5.hip); ``wfrag`` from
+    ``pack_conv5x5_weight``.  W in (8, 16, 32), Cin % 32 == 0, Cout % 128 == 0, Hp even and >= H + 2."""
+    with _observed("conv5x5", B, Hp, H, W, Cin, Cout, mode):
+        check(_lib.load().ac_conv5x5_bn_relu_bf16x3(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                    Cout, mode, stream()), "ac_conv5x5_bn_relu_bf16x3")
+    return out
+
+
+def pack_conv5x5_weight(w):
+    """OIHW f32 (Cout, Cin, 5, 5) on the device -> split bf16 in MFMA fragment order [Cin/32][25][2 ks][Cout/32][2 (hi,
+    lo)][64 lanes][8], packed by a kernel (the layout ``pack_conv_weight_bf16x3_frag`` gives 25 taps)."""
+    cout, cin = w.shape[0], w.shape[1]
+    if tuple(w.shape[2:]) != (5, 5):
+        raise ValueError("pack_conv5x5_weight: OIHW with a 5x5 kernel")
+    w = f32c(_dev(w))
+    out = torch.empty(cin // 32, 25, 2, cout // 32, 2, 64, 8, device=w.device, dtype=torch.bfloat16)
+    check(_lib.load().ac_pack_conv5x5_weight_bf16x3(ptr(w), ptr(out), cin, cout, stream()), "ac_pack_conv5x5_weight_bf16x3")
+    return out
+
+
 def wino1d_splitk_floats(B, Hp, W, Cin, Cout):
     """Floats of workspace ``conv3x3_bn_relu_wino1d(..., workspace=...)`` needs to run this geometry K-sliced (launches of
     a few workgroups: single clips); 0 = the launch is not split."""

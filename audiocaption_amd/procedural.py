@@ -64,6 +64,47 @@ def cnn14_state(prefix="", seed=BASE_SEED, with_fc1=True):
     return out
 
 
+def _cnn_small_state(prefix, seed, kernel, convs, with_fc1):
+    """The four-block PANNs encoders: ``convs`` convolutions of ``kernel`` x ``kernel`` taps per block, 512-wide ``fc1``."""
+    out = {}
+    p = prefix + "bn0"
+    _bn(p, 64, out, seed)
+    out[p + ".running_mean"] = _uniform(p + ".running_mean", (64,), -30.0, -20.0, seed)   # (see cnn14_state)
+    out[p + ".running_var"] = _uniform(p + ".running_var", (64,), 25.0, 40.0, seed)
+    for b in range(4):
+        cin, cout = CNN14_CHANNELS[b], CNN14_CHANNELS[b + 1]
+        for j in range(1, convs + 1):
+            ci = cin if j == 1 else cout
+            k = f"{prefix}conv_block{b + 1}.conv{j}.weight"
+            out[k] = _normal(k, (cout, ci, kernel, kernel), math.sqrt(2.0 / (kernel * kernel * ci)), seed)
+            _bn(f"{prefix}conv_block{b + 1}.bn{j}", cout, out, seed)
+    if with_fc1:
+        k = prefix + "fc1.weight"
+        out[k] = _normal(k, (512, 512), math.sqrt(1.0 / 512), seed)
+        out[prefix + "fc1.bias"] = _uniform(prefix + "fc1.bias", (512,), -0.01, 0.01, seed)
+    return out
+
+
+def cnn10_state(prefix="", seed=BASE_SEED, with_fc1=True):
+    """Cnn10Encoder tensors (reference ctor: cnn_encoder.py:222-261): four blocks of two 3x3 convs."""
+    return _cnn_small_state(prefix, seed, 3, 2, with_fc1)
+
+
+def cnn6_state(prefix="", seed=BASE_SEED, with_fc1=True):
+    """Cnn6Encoder tensors (reference ctor: cnn_encoder.py:114-153): four blocks of one 5x5 conv."""
+    return _cnn_small_state(prefix, seed, 5, 1, with_fc1)
+
+
+def cnn_small_rnn_trm_state(cnn_state, vocab_size=4368, seed=BASE_SEED):
+    """State dict of ``config.cnn10rnn_trm_config`` / ``cnn6rnn_trm_config``: ``cnn_state`` is ``cnn10_state`` or
+    ``cnn6_state``; 3 bi-GRU layers over the 512-wide features, a 2-layer TransformerDecoder."""
+    out = {}
+    out.update(cnn_state("encoder.cnn.", seed))
+    out.update(gru_state("encoder.rnn.", 512, 256, 3, seed))
+    out.update(decoder_state("decoder.", vocab_size, 256, 512, 2, 1024, seed))
+    return out
+
+
 def gru_state(prefix="", input_size=2048, hidden=256, layers=3, seed=BASE_SEED):
     """nn.GRU(bidirectional) tensors under ``network.`` (reference rnn_encoder.py:23-29)."""
     out = {}

@@ -302,8 +302,14 @@ class _Ws:
 class TrainEngine:
 
     def __init__(self, model, seed=0):
+        from .cnn_encoder import Cnn14Encoder
         from .crnn_trm_encoder import Cnn14TransformerEncoder, CrnnEncoder
         enc = model.encoder
+        cnn = getattr(enc, "cnn", None)
+        if isinstance(enc, (CrnnEncoder, Cnn14TransformerEncoder)) and not isinstance(cnn, Cnn14Encoder):
+            raise NotImplementedError(
+                f"{type(self).__name__}: the training step is built around Cnn14Encoder (2048-wide features at T // 32, its "
+                f"train-mode forward with dropout and SpecAugment); training over {type(cnn).__name__} is not built")
         if isinstance(enc, Cnn14TransformerEncoder) and enc.freeze_cnn_bn:
             self.enc_kind = "trm"
         elif isinstance(enc, CrnnEncoder) and enc.freeze_cnn_bn:

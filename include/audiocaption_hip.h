@@ -218,6 +218,27 @@ int ac_conv3x3_first(const float* in, const float* w, const float* scale, const 
 int ac_conv3x3_first_f16(const float* in, const float* w, const float* scale, const float* shift, void* out,
                          int B, int Hp, int H, int W, unsigned int* overflow_flag, void* stream);
 
+/* ---- Cnn6: 5x5 / stride 1 / pad 2 convolutions (csrc/conv5x5.hip) ---------------------------------
+ * Same [B*Hp][W][C] f32 channels-last rows as the 3x3 kernels, with a stronger row rule: a 5x5 conv reads TWO rows beyond
+ * a clip, so Hp >= H + 2 and Hp even (AC_ERR_ARG otherwise).  Input rows at or beyond a clip's own H are read as zeros
+ * whatever the buffer holds; output rows at or beyond H (H / 2 of a pooled output) are written as zeros.
+ * Replace ConvBlock5x5.forward (cnn_encoder.py:96-111) + F.avg_pool2d of Cnn6Encoder.forward (cnn_encoder.py:192-199). */
+/* Block 1 (Cin = 1, 25 taps, f32 FMAs) + BN + ReLU + 2x2 average pool in one kernel: in [B*Hp][64] (log-mel after bn0),
+ * w [64][25] (OIHW), out [B*Hp/2][32][64]; an odd H loses its last row, as F.avg_pool2d does. */
+int ac_conv5x5_first(const float* in, const float* w, const float* scale, const float* shift, float* out,
+                     int B, int Hp, int H, void* stream);
+/* Implicit GEMM (M = pixels, N = Cout, K = 25 * Cin) on split-bf16 operands: x = hi + lo (RNE both), three
+ * v_mfma_f32_32x32x16_bf16 products per f32 product, f32 accumulation - the arithmetic of ac_conv3x3_bn_relu_bf16x3_gw.
+ * BN folded to scale / shift on the f32 accumulator, ReLU; mode 0 = full output [B*Hp][W][Cout], 1 = 2x2 average pool
+ * (ReLU before the pool) [B*Hp/2][W/2][Cout].  wfrag from ac_pack_conv5x5_weight_bf16x3.  W = 8, 16 or 32, Cin % 32 == 0,
+ * Cout % 128 == 0. */
+int ac_conv5x5_bn_relu_bf16x3(const float* in, const void* wfrag, const float* scale, const float* shift, float* out,
+                              int B, int Hp, int H, int W, int Cin, int Cout, int mode, void* stream);
+/* w OIHW f32 [Cout][Cin][5][5] (device) -> wfrag: hi = RNE_bf16(w), lo = RNE_bf16(w - hi) in MFMA fragment order
+ * [Cin/32][25 taps][2 k-steps][Cout/32][2 (hi, lo)][64 lanes][8] bf16, lane = (cout % 32) + 32 * ((cin % 16) / 8),
+ * element = cin % 8: Cin * Cout * 100 bytes.  Cin % 32 == 0, Cout % 32 == 0. */
+int ac_pack_conv5x5_weight_bf16x3(const float* w, void* wfrag, int Cin, int Cout, void* stream);
+
 /* ---- dense projection ---------------------------------------------------------------------------
  * Y[M,N] = act(X[M,K] W[N,K]^T + bias): every F.linear of the path (rnn_encoder.py:41 input
  * projections, transformer_decoder.py:86,95-101).  K % 32 == 0, ldx/ldw % 4 == 0, 16-byte aligned X/W. */
