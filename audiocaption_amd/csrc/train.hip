@@ -169,14 +169,15 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmP p) {
     const int am = m0 + lr + 32 * i, bn = n0 + lr + 32 * i;
     aok[i] = am < p.M;
     bok[i] = bn < p.N;
-    ap[i] = p.A + (long)min(am, p.M - 1) * p.sam + lk;
-    bp[i] = p.B + (long)min(bn, p.N - 1) * p.sbn + lk;
-    gp[i] = p.a_scale ? p.a_scale + (long)(min(am, p.M - 1) / p.a_rows) * p.K + lk : nullptr;
+    ap[i] = p.A + (long)min(am, p.M - 1) * p.sam;
+    bp[i] = p.B + (long)min(bn, p.N - 1) * p.sbn;
+    gp[i] = p.a_scale ? p.a_scale + (long)(min(am, p.M - 1) / p.a_rows) * p.K : nullptr;
   }
   f32x4 ra[NL], rb[NL];
   auto load = [&](int k0) {
     const bool kok = k0 + lk < kend;                       // K % 4 == 0: a float4 is inside or outside as a whole
-    const int kc = kok ? k0 : kbeg;                        // clamped (valid) address, zeroed below
+    const int kc = min(k0 + lk, kend - 4);                 // clamped to the slice's last float4 (a slice may be shorter than
+                                                           // a chunk: K = 16, the tail of a split-K cut), zeroed below
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       f32x4 va = *(const f32x4*)(ap[i] + kc);

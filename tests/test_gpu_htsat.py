@@ -93,9 +93,11 @@ def canary(*shape):
 
 
 # ---- kernels ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("T", [1024, 1001, 33])
+@pytest.mark.parametrize("T", [1024, 1001, 33, 32, 513, 1023, 1])
 def test_patch_embed(lib, state, T):
-    """Identity (1024), a mild stretch (1001) and a 31-times stretch with clamped borders (33)."""
+    """Identity (1024), a mild stretch (1001) and a 31-times stretch with clamped borders (33); the shortest clip the encoder
+    takes (32), a stretch by almost two (513), by 1023 / 1022 (every fraction occurs once) and a single frame (all four taps
+    clamped onto it)."""
     B, C = 2, 96
     x = randn(B, T, 64, seed=T, scale=1.5)
     w, b, lw, lb = (state["encoder.patch_embed." + k] for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias"))
@@ -149,10 +151,87 @@ def test_pool_token_mean_and_gelu(lib):
     mean = canary(B, 192)
     assert lib.ac_htsat_token_mean(P(y.cuda()), P(mean), B, 1024, 192, S()) == 0
     assert rel("token mean 1024 x 192", mean, R.token_mean(y)) < KERNEL_BAR
-    z = torch.cat([randn(70001, seed=23, scale=3.0), torch.tensor([0.0, -0.0, 10.0, -10.0])])    # more than one grid pass
+    z = torch.cat([randn(70001, seed=23, scale=3.0), torch.tensor([0.0, -0.0, 10.0, -10.0])])    # 274 blocks with a partly empty
+    # last one: ONE pass of the grid-stride loop (the grid is capped at 65 536 blocks; test_gelu_in_place_beyond_one_grid_pass)
     g = canary(z.numel())
     assert lib.ac_gelu(P(z.cuda()), P(g), z.numel(), S()) == 0
     assert rel("gelu", g, R.gelu(z.double())) < KERNEL_BAR
+
+
+@pytest.mark.parametrize("B,H,W,heads,shift", [(2, 32, 32, 8, 0), (2, 32, 32, 8, 4), (2, 16, 16, 16, 0), (2, 16, 16, 16, 4),
+                                               (2, 8, 8, 32, 0), (2, 16, 24, 2, 0), (2, 16, 24, 2, 4), (2, 24, 16, 2, 0),
+                                               (2, 24, 16, 2, 4)])
+def test_window_attention_encoder_stages_and_rectangles(lib, B, H, W, heads, shift):
+    """The head counts and image sides of the encoder's stages 1 - 3 (8, 16 and 32 heads: the head offset into a 3C-wide row
+    reaches 3 * 768 floats), and images with H != W (six windows: the window index splits into (row, column) by W / 8, the
+    roll and the region bands take H and W separately)."""
+    C = heads * 24
+    qkv = randn(B, H * W, 3 * C, seed=H * 100 + W + shift + heads)
+    bias = R.relative_bias(randn(225, heads, seed=5))
+    out = canary(B, H * W, C)
+    rc = lib.ac_swin_window_attn(P(qkv.cuda()), P(bias.contiguous().cuda()), P(out), B, H, W, C, heads, shift, S())
+    assert rc == 0
+    want = R.window_attn(qkv, bias, H, W, heads, shift)
+    if shift:
+        assert float((want - R.window_attn(qkv, bias, H, W, heads, 0)).abs().max()) > 0.1
+    if H != W:      # the transposed image is another problem: a swapped H and W fails
+        assert float((want - R.window_attn(qkv, bias, W, H, heads, shift)).abs().max()) > 0.1
+    assert rel(f"window attention {B}x{H}x{W}x{C} heads {heads} shift {shift}", out, want) < KERNEL_BAR
+
+
+@pytest.mark.parametrize("B,H,W,C", [(2, 16, 16, 96), (2, 16, 8, 192), (1, 6, 10, 384), (2, 8, 8, 384)])
+def test_patch_merge_encoder_widths(lib, B, H, W, C):
+    """The encoder's widths (4C = 1536 is the kernel's register bound, 64 lanes x 24), a rectangular image, and 15 merged
+    tokens: a last workgroup with one idle wave."""
+    x = randn(B, H, W, C, seed=H + W + C)
+    x[:, 0::2, 0::2] += 1.0
+    x[:, 1::2, 0::2] -= 2.0
+    x[:, 0::2, 1::2] += 3.0
+    x = x.reshape(B, H * W, C)
+    lw, lb = 1.0 + 0.2 * randn(4 * C, seed=12), 0.1 * randn(4 * C, seed=13)
+    out = canary(B, H * W // 4, 4 * C)
+    assert lib.ac_swin_patch_merge(P(x.cuda()), P(lw.cuda()), P(lb.cuda()), P(out), B, H, W, C, S()) == 0
+    assert rel(f"patch merge {B}x{H}x{W}x{C}", out, R.patch_merge(x, H, W, lw, lb)) < KERNEL_BAR
+
+
+def test_patch_merge_refuses_a_width_beyond_its_registers(lib):
+    from audiocaption_amd import _lib
+    buf = torch.zeros(2 * 2 * 4 * 385, device="cuda")
+    assert lib.ac_swin_patch_merge(P(buf), P(buf), P(buf), P(buf), 1, 2, 2, 385, S()) == _lib.AC_ERR_ARG
+    torch.cuda.synchronize()
+    assert float(buf.abs().max()) == 0.0      # nothing was launched
+
+
+@pytest.mark.parametrize("B,N,C", [(2, 1, 96), (2, 3, 96), (3, 1023, 96), (2, 1023, 192)])
+def test_token_mean_token_counts(lib, B, N, C):
+    """Fewer tokens than waves (1, 3), a count that is no multiple of the four waves (1023), and C = 96: the second channel
+    block is half empty."""
+    x = randn(B, N, C, seed=N + C) + 0.3
+    mean = canary(B, C)
+    assert lib.ac_htsat_token_mean(P(x.cuda()), P(mean), B, N, C, S()) == 0
+    assert rel(f"token mean {N} x {C}", mean, R.token_mean(x)) < KERNEL_BAR
+
+
+@pytest.mark.parametrize("B,Hh,Ww,C,fbins", [(2, 8, 8, 768, 1), (2, 8, 8, 768, 4), (3, 4, 6, 96, 2), (2, 6, 4, 300, 3)])
+def test_pool_bins_and_rectangles(lib, B, Hh, Ww, C, fbins):
+    """One bin per frame (the pool is a copy), four, and token grids with Hh != Ww; C = 300: a second, partly empty block."""
+    x = randn(B, Hh * Ww, C, seed=Hh * 10 + Ww + fbins) + 0.2
+    attn, fc = canary(B, Hh // fbins * Ww, C), canary(B, C)
+    assert lib.ac_htsat_pool(P(x.cuda()), P(attn), P(fc), B, Hh, Ww, C, fbins, S()) == 0
+    want_attn, want_fc = R.pool(x, Hh, Ww, fbins)
+    assert rel(f"pool attn_emb {Hh}x{Ww} / {fbins}", attn, want_attn) < KERNEL_BAR
+    assert rel(f"pool fc_emb {Hh}x{Ww} / {fbins}", fc, want_fc) < KERNEL_BAR
+
+
+def test_gelu_in_place_beyond_one_grid_pass(lib):
+    """As the encoder calls it: in place, on more elements than the capped grid (65 536 blocks of 256) covers in one pass."""
+    n = 65536 * 256 + 1000
+    z = randn(n, seed=24, scale=3.0)
+    zd = z.cuda()
+    assert lib.ac_gelu(P(zd), P(zd), n, S()) == 0
+    want = R.gelu(z.double())
+    assert rel("gelu in place, first pass", zd[:65536 * 256], want[:65536 * 256]) < KERNEL_BAR
+    assert rel("gelu in place, second pass", zd[65536 * 256:], want[65536 * 256:]) < KERNEL_BAR
 
 
 # ---- the whole encoder -----------------------------------------------------------------------------------------------
@@ -209,6 +288,60 @@ def test_wav_to_encoder(model, clips):
     for k in OUTPUTS:
         assert rel(f"B = 1 vs row 0 of the batch: {k}", one[k], got[k][:1]) < ENCODER_BAR
     assert torch.equal(model.encoder(clips["inp"])["attn_emb"], got["attn_emb"])        # and back to B = 3
+
+
+class _RecordingLib:
+    """Forwards every call to the library and records (M, N, K, has_bias, beta) of the ``ac_gemm_bf16x3`` calls (the proxy of
+    tools/launch_trace.py, cut down to one symbol)."""
+
+    def __init__(self, lib, calls):
+        self._lib, self._calls = lib, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != "ac_gemm_bf16x3":
+            return fn
+
+        def call(*a):
+            self._calls.append((a[8], a[9], a[10], a[11] is not None, float(a[13])))
+            return fn(*a)
+
+        return call
+
+
+def _encode_recording(encoder, inp):
+    from audiocaption_amd import _lib
+    calls, real = [], _lib.load
+    proxy = _RecordingLib(real(), calls)
+    _lib.load = lambda: proxy
+    try:
+        out = encoder(inp)
+        torch.cuda.synchronize()
+    finally:
+        _lib.load = real
+    return out, calls
+
+
+def test_encoder_at_eight_clips_and_its_gemm_calls(model, clips):
+    """Eight clips are where the linear layers of stage 0 first take the 128 x 128 split-bf16 tile and those of stage 1 all
+    leave the exact kernels (tests/_gemm_routes.py): the fixture's three clips tiled to eight rows, every row against the
+    restatement's row for the same clip, and the issued ``ac_gemm_bf16x3`` calls against ``htsat_linear_calls`` - the list
+    whose routes tests/test_gemm_routes_cpu.py pins.  The same for one clip (stage 0's proj on the exact nt<1> kernel)."""
+    import _gemm_routes as G
+    rows = [0, 1, 2, 0, 1, 2, 0, 1]
+    inp = {"wav": clips["wav"][rows].contiguous(), "wav_len": [CLIP_LENS[r] for r in rows], "specaug": False}
+    got, calls = _encode_recording(model.encoder, inp)
+    assert calls == [c[1:] for c in G.htsat_linear_calls(8)]
+    assert got["attn_emb_len"].tolist() == [[31, 25, 17][r] for r in rows]
+    want = clips["want"]
+    for k in OUTPUTS:
+        assert tuple(got[k].shape) == (8,) + tuple(want[k].shape[1:])
+        for i, r in enumerate(rows):
+            assert rel(f"B = 8, row {i} (clip {r}): {k}", got[k][i], want[k][r]) < ENCODER_BAR
+    one, calls = _encode_recording(model.encoder, {"wav": clips["wav"][:1], "wav_len": CLIP_LENS[:1], "specaug": False})
+    assert calls == [c[1:] for c in G.htsat_linear_calls(1)]
+    for k in OUTPUTS:
+        assert rel(f"B = 1: {k}", one[k][0], want[k][0]) < ENCODER_BAR
 
 
 def test_repack_after_load_state_dict(model, state, clips):

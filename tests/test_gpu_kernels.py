@@ -113,6 +113,39 @@ def test_add_layernorm(K):
     assert _report("layernorm", got, torch.nn.functional.layer_norm(x, (256,), w, b)) < 5e-6
 
 
+@pytest.mark.parametrize("d", [96, 192, 384, 768, 1024, 100])
+def test_add_layernorm_widths(K, d):
+    """The widths the HTS-AT encoder normalises (96: half of the lanes hold one element, the others two; 768), the kernel's
+    bound (1024: sixteen elements per lane) and a width that is no multiple of 4; 70 rows: the last workgroup is half empty.
+    With and without the added tensor, against float64, and once on views with a row stride beyond d whose pad columns keep
+    their bits."""
+    g = torch.Generator().manual_seed(d)
+    rows = 70
+    x, y = torch.randn(rows, d, generator=g), torch.randn(rows, d, generator=g)
+    w, b = torch.rand(d, generator=g) + 0.5, torch.randn(d, generator=g)
+    ln = lambda t: torch.nn.functional.layer_norm(t, (d,), w.double(), b.double())   # noqa: E731
+    got = K.add_layernorm(x.cuda(), y.cuda(), w.cuda(), b.cuda())
+    assert _report(f"add_layernorm d={d}", got, ln(x.double() + y.double())) < 5e-6
+    got = K.add_layernorm(x.cuda(), None, w.cuda(), b.cuda())
+    assert _report(f"layernorm d={d}", got, ln(x.double())) < 5e-6
+    xs, ys = torch.randn(rows, d + 8, generator=g), torch.randn(rows, d + 20, generator=g)
+    out = torch.full((rows + 2, d + 12), 7.0).cuda()
+    K.add_layernorm(xs.cuda()[:, :d], ys.cuda()[:, 4:4 + d], w.cuda(), b.cuda(), out=out[:rows, :d])
+    assert _report(f"add_layernorm d={d}, strided rows", out[:rows, :d], ln(xs[:, :d].double() + ys[:, 4:4 + d].double())) < 5e-6
+    assert torch.equal(out[:, d:].cpu(), torch.full((rows + 2, 12), 7.0)) and torch.equal(out[rows:].cpu(), torch.full((2, d + 12), 7.0))
+
+
+def test_add_layernorm_refuses_a_width_beyond_its_registers(K):
+    from audiocaption_amd._lib import HipLibraryError
+    d = 1025
+    x, w = torch.randn(4, d).cuda(), torch.ones(d).cuda()
+    out = torch.full((4, d), 7.0).cuda()
+    with pytest.raises(HipLibraryError, match="AC_ERR_ARG"):
+        K.add_layernorm(x, None, w, w, out=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), torch.full((4, d), 7.0))      # nothing was launched
+
+
 @pytest.mark.parametrize("L,B", [(320000, 2), (64000, 3), (35231, 2)])
 def test_logmel_matches_oracle(K, L, B):
     """fp32 log-mel in dB vs the oracle (torch.stft path).  Tolerance 2e-3 dB absolute: both are fp32
