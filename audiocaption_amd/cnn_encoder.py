@@ -58,7 +58,7 @@ def _wino1d_clip_chunk(B, Hp, W, Cin):
 
 
 def _conv_wino1d(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None,
-                 overflow=None, cold=False):
+                 overflow=None, cold=False, train=False):
     """The "wino1d" tier's launcher (``_pack_wino1d`` packs a layer's weights for the kernel ``wino1d_covers`` names; the
     call signature is ``ConvTier.launch``).  A batch whose input exceeds the kernel's 2 GiB addressing range is convolved
     in clip chunks (clips do not interact; rows are per clip)."""
@@ -100,21 +100,58 @@ def wino43_covers(W, cout):
     return W in (32, 16, 8, 4, 2) and cout % 128 == 0
 
 
+# Row SEXTETS (F(6,3) along time, ``K.conv3x3_bn_relu_wino63``): a tile form of the F(4,3) kernel with 11 % fewer MFMAs per
+# output row and 1.5 x the rows per workgroup.  A layer (W, Cin, Cout) is listed here - with the tiles per wave it runs at -
+# only if its launch MEASURED faster than the quad form at the benchmark's shape (64 clips of 10 s; EXPERIMENTS.md "Row
+# sextets"); conv blocks 5-6 never are (one or two rounds of workgroups: a sextet workgroup is 1.5 x as long and saves no
+# round).
+def _sextet_layers(default):
+    """AUDIOCAPTION_W63_LAYERS="32x128x128x2,16x128x256x1" (W x Cin x Cout x tiles per wave; "" = none) replaces the measured
+    list: experiments."""
+    env = os.environ.get("AUDIOCAPTION_W63_LAYERS")
+    if env is None:
+        return dict(default)
+    return {tuple(v[:3]): v[3] for v in (tuple(int(t) for t in item.split("x")) for item in env.split(",") if item.strip())}
+
+
+# inside the benchmark run (kernel trace, 78 launches each): conv2 of block 2 481 -> 463 us at two tiles per wave, conv1 of
+# block 3 279 -> 264 us at one; conv2 of block 4 measured 9 us faster alone and 8 us slower inside the run, and every other
+# layer of blocks 2-4 was inside its spread or slower: they stay on quads
+SEXTET_LAYERS = _sextet_layers({(32, 128, 128): 2, (16, 128, 256): 1})
+# ... and only for launches of at least this many quad-form workgroups (``K.wino43_workgroups``): four rounds of the chip,
+# the smallest launch it was measured at; single clips and the K-sliced launches are far below it
+SEXTET_MIN_WORKGROUPS = int(os.environ.get("AUDIOCAPTION_W63_MIN_WG", "1024"))
+
+
+def sextet_route(B, Hp, W, Cin, Cout):
+    """Does the inference forward run this layer on row sextets?"""
+    return (W, Cin, Cout) in SEXTET_LAYERS and Hp % 4 == 0 and K.wino43_workgroups(B, Hp, W, Cout) >= SEXTET_MIN_WORKGROUPS
+
+
 class Wino43Pack(NamedTuple):
     """The packs of one layer on the "wino43" tier."""
     f23: torch.Tensor             # what ``_conv_wino1d`` launches: small launches (single clips) take the K-sliced F(2,3) form
     f43: torch.Tensor = None      # F(4,3), where ``wino43_covers`` the layer
     skinny: "_LazyPack" = None    # blocks 5-6 (W = 4, 2): the skinny form
+    f63: torch.Tensor = None      # F(6,3), for the ``SEXTET_LAYERS``
 
 
 def _conv_wino43(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None,
-                 overflow=None, cold=False):
+                 overflow=None, cold=False, train=False):
     """The "wino43" tier's launcher (``w``: a ``Wino43Pack``).  F(4,3) when the kernel covers the layer and the launch fills
     the chip (a workgroup owns a CU: single clips run the K-sliced F(2,3) form instead)."""
     # (AUDIOCAPTION_RAGGED_EXACT=1 only: batches of uneven lengths then keep block 6 on F(2,3) - the caller passes it the F(2,3)
     # pack only: its tiles are taller than a clip, nothing can be skipped there anyway, and the quad-wide input window of
     # F(4,3) would cost every layer upstream four more valid rows per clip - ``rows_needed``.  In the default mode ragged
     # batches run F(4,3) on block 6 too and valid frames are within 5e-5 of the dense run, not bit-identical)
+    # row sextets: the inference forward of uniform batches.  The training forward (``train``: with or without dropout) keeps
+    # its routing: ``sextet_route`` depends on the launch's size, and a training step's gradient has to stay linear in the
+    # batch - a clip's features may not change form between a batch and its halves; the row windows of ragged batches -
+    # ``rows_needed`` - are those of quads
+    if w.f63 is not None and need is None and dropout is None and not train and mode != 2 \
+            and sextet_route(B, Hp, W, Cin, Cout):
+        return K.conv3x3_bn_relu_wino63(x, w.f63, scale, shift, out, B, Hp, H, W, Cin, Cout, mode,
+                                        tiles_per_wave=SEXTET_LAYERS[(W, Cin, Cout)])
     if w.f43 is not None and (mode != 1 if W == 2 else mode != 2) and Hp % 4 == 0 \
             and K.wino43_workgroups(B, Hp, W, Cout) >= W43_MIN_WORKGROUPS:
         return K.conv3x3_bn_relu_wino43(x, w.f43, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=need, dropout=dropout)
@@ -192,7 +229,7 @@ class ConvTier:
     """What a conv tier (``Cnn14Encoder.conv_algo``) is: how it packs a layer, how it launches one, and what callers may ask
     of it.  ``pack(w, b, weight)``: OIHW f32 weights of a layer of conv block ``b`` (0..5), ``weight`` the parameter itself
     -> (pack, inv_scale[Cout] to fold into the BN scale or None).  ``launch(x, pack, scale, shift, out, B, Hp, H, W, Cin,
-    Cout, mode, need=, dropout=, workspace=, overflow=, cold=)``: one layer, with all that ``conv_stack`` has for it; a
+    Cout, mode, need=, dropout=, workspace=, overflow=, cold=, train=)``: one layer, with all that ``conv_stack`` has for it; a
     tier uses what it can and refuses ``need`` (``rows_needed`` of a ragged batch) / ``dropout`` when it cannot."""
     pack: object
     launch: object
@@ -213,7 +250,7 @@ class ConvTier:
 def _plain(kernel, takes_overflow=False):
     """``ConvTier.launch`` of a tier whose kernel takes the layer and nothing else (the fp16 tier: and its overflow word)."""
     def launch(x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, need=None, dropout=None, workspace=None, overflow=None,
-               cold=False):
+               cold=False, train=False):
         if need is not None or dropout is not None:
             raise ValueError("this conv tier has neither dead-row skipping nor a dropout epilogue")
         if takes_overflow:
@@ -233,7 +270,8 @@ def _pack_wino1d(w, b, weight):
 def _pack_wino43(w, b, weight):
     return Wino43Pack(_pack_wino1d(w, b, weight)[0],
                       K.pack_conv_weight_wino43_frag(w) if wino43_covers(64 >> b, w.shape[0]) else None,
-                      _LazyPack(weight) if b >= 4 else None), None
+                      _LazyPack(weight) if b >= 4 else None,
+                      K.pack_conv_weight_wino63_frag(w) if (64 >> b, w.shape[1], w.shape[0]) in SEXTET_LAYERS else None), None
 
 
 def _block1_wino43(x0, conv1, conv2, f43, out, B, Hp, H, need, dropout, overflow):
@@ -476,7 +514,7 @@ class Cnn14Encoder(_PannsEncoder):
         if specaug is not None:
             K.specaug_(x0, specaug, pk["bn0"][1], B, Hp[0], T)
         return self.conv_stack(x0, B, H, Hp, pk, algo, dropout, overflow=overflow, clip_frames=clip_frames,
-                               block6_f23=block6_f23)
+                               block6_f23=block6_f23, train=train or dropout is not None)
 
     def effective_algo(self, algo=None, train=False, min_frames=None):
         """The conv tier a call runs on: the fp16-activation tier is left for the train-mode forward and for batches
@@ -488,7 +526,7 @@ class Cnn14Encoder(_PannsEncoder):
         return algo
 
     def conv_stack(self, x0, B, H, Hp, pk, algo, dropout=None, blocks=None, overflow=None, clip_frames=None,
-                   block6_f23=False):
+                   block6_f23=False, train=False):
         """The six conv blocks on a bn0-normalised log-mel x0 [B*Hp[0]][64] -> attn_emb (B, H[5], 2048).
         ``blocks``: a list that receives a float32 (B, C, H, W) copy of every pooled block output (tests)."""
         dev = x0.device
@@ -497,8 +535,9 @@ class Cnn14Encoder(_PannsEncoder):
         pooled = self._buf("pooled", B * Hp[1] * 32 * 64, dev, tiers[0].act)  # block outputs (largest: block 1)
         W = 64
         # what every launch is offered beside its layer.  "workspace": single clips - layers of a few workgroups run K-sliced
-        # over a shared workspace; "cold": the training step - weights come from HBM every iteration
-        offer = {"workspace": None, "overflow": overflow, "cold": dropout is not None}
+        # over a shared workspace; "cold": the training step - weights come from HBM every iteration; "train": the forward of a
+        # training step, with or without dropout
+        offer = {"workspace": None, "overflow": overflow, "cold": dropout is not None, "train": train}
         if os.environ.get("AUDIOCAPTION_W1_SPLITK", "1") != "0":
             offer["workspace"] = lambda n: self._buf("w1_splitk", n, dev)
         fuse1 = os.environ.get("AUDIOCAPTION_FUSE_BLOCK1", "1") != "0"

@@ -49,6 +49,9 @@ namespace {
 #ifndef W4_RING     // weight fragment ring: a group's pair is requested W4_RING - 1 groups ahead (18 % W4_RING == 0)
 #define W4_RING 9
 #endif
+#ifndef W6_RING     // the same for row sextets (24 groups per K step)
+#define W6_RING 8
+#endif
 #ifndef W4_PRO2     // prologue: request the rows of the first two steps together
 #define W4_PRO2 1
 #endif
@@ -68,10 +71,11 @@ __device__ unsigned long long w4_clk[8];
 
 constexpr int KS = 16;   // input channels per K step = one MFMA k-step
 constexpr int W4_OUT_TILE = 4 * 32 * 144;   // epilogue: a wave's LDS tile of 4 rows x 32 pixels x (128 + 16) bytes
+constexpr int W6_OUT_TILE = 3 * 32 * 144;   // row sextets drain as two halves of 3 rows
 
 struct W4Params {
   const float* in;
-  const void* wpk;    // [Cin/16][18 = 3 kx x 6 p][Cout/32][2 (hi, lo)][64 lanes][8] bf16
+  const void* wpk;    // [Cin/16][18 = 3 kx x 6 p][Cout/32][2 (hi, lo)][64 lanes][8] bf16 (sextets: 24 = 3 kx x 8 p)
   const float* scale;
   const float* shift;
   float* out;
@@ -121,10 +125,16 @@ __device__ __forceinline__ bool w4_block_map(const W4Params& p, int& m_tile, int
   return true;
 }
 
-template <int TC, int MW>
+// R: output rows of a tile along time = 4 (row QUADS, F(4,3): 6 positions) or 6 (row SEXTETS, F(6,3): 8 positions, 24
+// products per sextet = 11 % fewer MFMAs per output row, and 1.5 x the rows per workgroup: fewer rounds of workgroups, each
+// of which pays its prologue and epilogue once).  "quad" below reads "tile of R rows".
+template <int TC, int MW, int R = 4>
 struct W4Geom {
   static_assert(TC == 32 || TC == 16 || TC == 8 || TC == 4 || TC == 2, "full-width blocks of 32, 16, 8, 4 or 2 mel columns");
   static_assert(MW == 1 || MW == 2, "one or two MFMA tiles per wave");
+  static_assert(R == 4 || (R == 6 && TC >= 8), "row quads, or row sextets in conv blocks 2-4");
+  static constexpr int NP = R + 2;                 // transformed positions
+  static constexpr int NG = 3 * NP;                // (kx, position) MFMA groups of a K step
   // TC = 2 (conv block 6): COLUMN tiles - tile m is column m of 32 quads, so the taps that read the zero padding beside the
   // image (kx = 0 of column 0, kx = 2 of column 1: a third of the products) are skipped at compile time, and no halo
   // column is staged
@@ -139,21 +149,22 @@ struct W4Geom {
   static constexpr int COLP = COLT ? 32 : TC == 32 ? (PQ | 1) : TC == 16 ? (PQ % 4 == 2 ? PQ : PQ + 2) : (PQ % 8 == 4 ? PQ : PQ + 4);
   static constexpr int HALF = ((LCOLS * COLP * 16 + 127) / 128) * 128 + 64;   // bytes of one k-half of a plane (= 64 mod 128:
   static constexpr int PLANE = 2 * HALF;      //   the 8-byte stores of channels 0-7 / 8-15 of four items hit different banks)
-  static constexpr int VBUF = 12 * PLANE;     // 6 positions x (hi, lo)
+  static constexpr int VBUF = 2 * NP * PLANE; // positions x (hi, lo)
   static constexpr int NITEM = PQ * TC * 4;   // staging items (quad, column, channel quad) of a step: 256 (MW 2) or 128
   static_assert(NITEM == 256 || NITEM == 128, "one item per thread (MW = 1: per thread of waves 0 and 1)");
-  static constexpr int NPIECE = 6;
+  static constexpr int NPIECE = NP;
+  static constexpr int OUT_TILE = R == 4 ? W4_OUT_TILE : W6_OUT_TILE;
 };
 
 // MW = 1: HALF-SIZE workgroups - 96 accumulators and <= 256 registers per wave, so TWO workgroups share a CU and one's
 // prologue / epilogue (8 k + 6-14 k cycles: as long as the 4-step K loop of conv1 of block 2) runs under the other's K loop.
 // A weight fragment pair then feeds 3 MFMAs instead of 6: twice the weight bytes through the L1 per product, which is why
 // the long-K layers keep MW = 2 (see w4_dispatch).
-template <int MODE, int TC, int MW>
+template <int MODE, int TC, int MW, int R = 4>
 __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Params p) {
-  using G = W4Geom<TC, MW>;
+  using G = W4Geom<TC, MW, R>;
   constexpr int QT = G::QT, PQ = G::PQ, COLP = G::COLP, HALF = G::HALF, PLANE = G::PLANE, VBUF = G::VBUF;
-  constexpr int NPIECE = G::NPIECE;
+  constexpr int NPIECE = G::NPIECE, NP = G::NP, NG = G::NG;
   extern __shared__ __attribute__((aligned(128))) unsigned char dsm_raw[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -181,24 +192,24 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
                       : (unsigned)(half * HALF + ((i % TC) * COLP + m * QT + i / TC) * 16);
   }
 
-  f32x16 acc[6][MW];
+  f32x16 acc[NP][MW];
 #pragma unroll
-  for (int q = 0; q < 6; ++q)
+  for (int q = 0; q < NP; ++q)
 #pragma unroll
     for (int m = 0; m < MW; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[q][m][r] = 0.f;
 
-  const int row0 = 4 * quad0;
-  const bool live = w4_rows_live(row0, 4 * PQ, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add);
+  const int row0 = R * quad0;
+  const bool live = w4_rows_live(row0, R * PQ, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add);
   const bool all_pad = !live;
   const int nstep = p.Cin / KS;
   if (!all_pad) {
-    // Input window of this block: rows 4 quad0 - 1 .. 4 (quad0 + PQ), through a buffer descriptor REBASED to the block's
+    // Input window of this block: rows R quad0 - 1 .. R (quad0 + PQ), through a buffer descriptor REBASED to the block's
     // first row (offsets stay small whatever the batch; bytes beyond the tensor, the row above the batch and lanes
     // parked on 0x80000000 read as zero)
     const int R0 = row0 > 0 ? row0 - 1 : 0;
-    const int first = row0 > 0 ? 0 : 1;   // rows to subtract: relative row of (quad, r) = 4 quad + r - first
+    const int first = row0 > 0 ? 0 : 1;   // rows to subtract: relative row of (quad, r) = R quad + r - first
     const size_t row_elems = (size_t)p.W * p.Cin;
     const size_t left = ((size_t)p.rows_total - R0) * row_elems * 4;
     const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
@@ -206,11 +217,11 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
     const int NT32 = p.Cout >> 5;
     const unsigned g_bytes = (unsigned)NT32 * 2048u;   // one (step, kx, p) group: NT32 x (hi, lo) x 1 KiB
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.wpk, 0, (int)((unsigned)nstep * 18u * g_bytes), 0x00020000);
+        (void*)p.wpk, 0, (int)((unsigned)nstep * (unsigned)NG * g_bytes), 0x00020000);
     const unsigned wvoff = (unsigned)((n_tile * 4 + wave) * 2048 + lane * 16);
     auto w_load = [&](int s, int gi, bf16x8 (&w)[2]) {
       if (W4_KO & 1) { if (s | gi) return; }
-      const unsigned soff = (unsigned)(s * 18 + gi) * g_bytes;
+      const unsigned soff = (unsigned)(s * NG + gi) * g_bytes;
       w[0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, soff, 0));
       w[1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff + 1024u, soff, 0));
     };
@@ -223,7 +234,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
     {
       auto item = [&](int it, unsigned& vb, unsigned& lofs) {
         const int cq = it & 3, rest = it >> 2, quad = rest % PQ, c = rest / PQ;
-        vb = (unsigned)(((4 * quad - first) * p.W + c) * p.Cin * 4 + cq * 16);
+        vb = (unsigned)(((R * quad - first) * p.W + c) * p.Cin * 4 + cq * 16);
         lofs = (unsigned)((cq >> 1) * HALF + ((c + (G::COLT ? 0 : 1)) * COLP + quad) * 16 + (cq & 1) * 8);
       };
       item(stager ? tid : 0, vbA, lofsA);
@@ -237,12 +248,12 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
       // every even step s, into two register sets: the rows of step r live in set r & 1 (`rwp`).
       constexpr bool PAIR = W4_ROWPAIR && MW == 2;
       static_assert(!PAIR || W4_PRO2, "the paired form starts from the two-step prologue");
-      f32x4 preA[6], rwp[PAIR ? 6 : 1];   // preA = set 0, rwp = set 1
+      f32x4 preA[NP], rwp[PAIR ? NP : 1];   // preA = set 0, rwp = set 1
       auto rows_request_pair = [&](int s) {   // rows of steps s (set 0) and s + 1 (set 1): the two halves of a line back to back
         if (W4_KO & 8) { if (s > 1) return; }
         const unsigned cs = (unsigned)(s * KS * 4);
 #pragma unroll
-        for (int r = 0; r < 6; ++r) {
+        for (int r = 0; r < NP; ++r) {
           preA[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, vbA + cs + (unsigned)r * row_bytes, 0, 0));
           rwp[PAIR ? r : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, vbA + cs + (unsigned)(KS * 4) + (unsigned)r * row_bytes, 0, 0));
         }
@@ -252,7 +263,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
         if (!stager) return;
         const unsigned cs = (unsigned)(s * KS * 4);
 #pragma unroll
-        for (int r = 0; r < 6; ++r)
+        for (int r = 0; r < NP; ++r)
           preA[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, vbA + cs + (unsigned)r * row_bytes, 0, 0));
       };
       auto store_piece = [&](unsigned char* buf, unsigned lofs, int pos, const f32x4 v) {
@@ -263,21 +274,28 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
         *(u32x2*)(dst + PLANE) = lo;
       };
       // piece k of a step: position k of the thread's item
+      auto transform = [](int k, const f32x4* d, auto PRESENT_) {   // rows d[0 .. NP - 1] (!PRESENT: a one-element dummy set)
+        constexpr bool PRESENT = decltype(PRESENT_)::value;
+        if constexpr (R == 4)
+          return w4_transform(k, d[0], d[PRESENT ? 1 : 0], d[PRESENT ? 2 : 0], d[PRESENT ? 3 : 0], d[PRESENT ? 4 : 0], d[PRESENT ? 5 : 0]);
+        else
+          return w6_transform(k, d[0], d[PRESENT ? 1 : 0], d[PRESENT ? 2 : 0], d[PRESENT ? 3 : 0], d[PRESENT ? 4 : 0], d[PRESENT ? 5 : 0],
+                              d[PRESENT ? 6 : 0], d[PRESENT ? 7 : 0]);
+      };
       auto commit_piece_set1 = [&](unsigned char* buf, int k) {   // PAIR: piece k of the rows in set 1
         if (W4_KO & 4) return;
-        store_piece(buf, lofsA, k, w4_transform(k, rwp[0], rwp[PAIR ? 1 : 0], rwp[PAIR ? 2 : 0], rwp[PAIR ? 3 : 0],
-                                                rwp[PAIR ? 4 : 0], rwp[PAIR ? 5 : 0]));
+        store_piece(buf, lofsA, k, transform(k, rwp, std::integral_constant<bool, PAIR>{}));
       };
       auto commit_piece = [&](unsigned char* buf, int k) {
         if (W4_KO & 4) return;
         if (!stager) return;
-        store_piece(buf, lofsA, k, w4_transform(k, preA[0], preA[1], preA[2], preA[3], preA[4], preA[5]));
+        store_piece(buf, lofsA, k, transform(k, preA, std::true_type{}));
       };
       // column tiles: tap kx of tile (= column) m reads column m + kx - 1, which exists for (m, kx) in {(0,1), (0,2), (1,0), (1,1)}
       auto tap_valid = [](int m, int kx) { return !G::COLT || (m + kx - 1 >= 0 && m + kx - 1 <= 1); };
       auto a_load = [&](const unsigned char* buf, int gi, bf16x8 (&a)[MW][2]) {
         if (W4_KO & 2) { if (gi) return; }
-        const int kx = gi / 6, q = gi % 6;
+        const int kx = gi / NP, q = gi % NP;
         const unsigned char* vh = buf + (2 * q) * PLANE;
         const int koff = (G::COLT ? kx - 1 : kx) * COLP * 16;
 #pragma unroll
@@ -290,27 +308,28 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
 
       // ---- prologue: zero halo columns of both buffers, step 0 into buffer 0, rows of step 1 requested ----
       {
-        constexpr int NZ = G::COLT ? 0 : 2 * 12 * 2 * 2 * COLP;   // 16-byte slots: buffers x planes x k-halves x 2 columns x COLP
+        constexpr int PH = 4 * NP;   // (plane, k-half) pairs of a buffer
+        constexpr int NZ = G::COLT ? 0 : 2 * PH * 2 * COLP;   // 16-byte slots: buffers x planes x k-halves x 2 columns x COLP
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         for (int i = tid; i < NZ; i += 256) {
-          const int slot = i % COLP, col = (i / COLP) & 1, hh = (i / (2 * COLP)) % 24, b = i / (48 * COLP);
+          const int slot = i % COLP, col = (i / COLP) & 1, hh = (i / (2 * COLP)) % PH, b = i / (2 * PH * COLP);
           *(f32x4*)(sV + b * VBUF + hh * HALF + ((col ? TC + 1 : 0) * COLP + slot) * 16) = z;
         }
       }
-      constexpr int RING = MW == 1 ? 6 : W4_RING, AH = RING - 1, NA = W4_ADEPTH + 1, LASTG = 17 - W4_ADEPTH;   // MW = 1: 256 registers
-      static_assert(18 % RING == 0 && 18 % NA == 0 && NPIECE <= LASTG, "ring positions are static; staging ends before the barrier");
+      constexpr int RING = MW == 1 ? 6 : R == 4 ? W4_RING : W6_RING, AH = RING - 1, NA = W4_ADEPTH + 1, LASTG = NG - 1 - W4_ADEPTH;   // MW = 1: 256 registers
+      static_assert(NG % RING == 0 && NG % NA == 0 && NPIECE <= LASTG, "ring positions are static; staging ends before the barrier");
       bf16x8 wr[RING][2];   // ring of weight fragments: group gi lives in wr[gi % RING], requested RING - 1 groups ahead
 #if W4_PRO2
       // the rows of steps 0 AND 1 are requested back to back before anything else (one exposed HBM round trip instead of
       // two: step 0's staging below waits for the first set, step 0 of the K loop finds the second one landed), the
       // weight fragments behind them (L2 hits, and the vector-memory counter retires in order)
-      f32x4 pre2[6];
+      f32x4 pre2[NP];
       if (PAIR) rows_request_pair(0);
       else rows_request(0);
       if (MW == 2 && !PAIR) {
         const unsigned cs = (unsigned)(KS * 4);
 #pragma unroll
-        for (int r = 0; r < 6; ++r)
+        for (int r = 0; r < NP; ++r)
           pre2[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, vbA + cs + (unsigned)r * row_bytes, 0, 0));
       }
 #pragma unroll
@@ -321,7 +340,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
         // step 0 stages set 1 (rows of step 1) and requests the rows of steps 2 and 3
       } else if (MW == 2) {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) preA[r] = pre2[r];
+        for (int r = 0; r < NP; ++r) preA[r] = pre2[r];
       } else {
         rows_request(1);
       }
@@ -345,16 +364,16 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
         const unsigned char* cur = sV + (s & 1) * VBUF;
         unsigned char* nxt = sV + ((s + 1) & 1) * VBUF;
 #pragma unroll
-        for (int gi = 0; gi < 18; ++gi) {
-          const int q = gi % 6;
-          if (gi + W4_ADEPTH < 18) a_load(cur, gi + W4_ADEPTH, af[(gi + W4_ADEPTH) % NA]);
-          else if (MORE) a_load(nxt, gi + W4_ADEPTH - 18, af[(gi + W4_ADEPTH) % NA]);   // behind the barrier of group LASTG
-          if (gi + AH < 18) w_load(s, gi + AH, wr[(gi + AH) % RING]);
-          else if (MORE) w_load(s + 1, gi + AH - 18, wr[(gi + AH) % RING]);
+        for (int gi = 0; gi < NG; ++gi) {
+          const int q = gi % NP;
+          if (gi + W4_ADEPTH < NG) a_load(cur, gi + W4_ADEPTH, af[(gi + W4_ADEPTH) % NA]);
+          else if (MORE) a_load(nxt, gi + W4_ADEPTH - NG, af[(gi + W4_ADEPTH) % NA]);   // behind the barrier of group LASTG
+          if (gi + AH < NG) w_load(s, gi + AH, wr[(gi + AH) % RING]);
+          else if (MORE) w_load(s + 1, gi + AH - NG, wr[(gi + AH) % RING]);
           if (!(W4_KO & 32)) {
             // operand order (weights, pixels): D rows = channels, columns = pixels, so that a lane ends up with four
             // CONSECUTIVE channels of one pixel per register quad (16-byte stores in the epilogue)
-            const int kxg = gi / 6;
+            const int kxg = gi / NP;
 #pragma unroll
             for (int m = 0; m < MW; ++m)
               if (tap_valid(m, kxg))
@@ -370,7 +389,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
           } else {
 #pragma unroll
             for (int m = 0; m < MW; ++m)
-              if (tap_valid(m, gi / 6))
+              if (tap_valid(m, gi / NP))
                 asm volatile("" :: "v"(af[gi % NA][m][0]), "v"(af[gi % NA][m][1]), "v"(wr[gi % RING][0]), "v"(wr[gi % RING][1]));
           }
           if (MORE) {
@@ -449,51 +468,69 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
   for (int m = 0; m < MW; ++m) {
     const int col = G::COLT ? m : pi % TC;
     const int qg = quad0 + (G::COLT ? pi : m * QT + pi / TC);
-    const int gr = 4 * qg;
-    f32x4 y[4][4];   // y[g][j][e]: channel quad g, output row j, channel chw + 8 g + e
+    const int gr = R * qg;
+    f32x4 y[4][R];   // y[g][j][e]: channel quad g, output row j, channel chw + 8 g + e
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * g + e;
-        float yy[4];
-        w4_outputs(acc[0][m][r], acc[1][m][r], acc[2][m][r], acc[3][m][r], acc[4][m][r], acc[5][m][r], sc4[g][e], sh4[g][e], yy);
+        float yy[R];
+        if constexpr (R == 4)
+          w4_outputs(acc[0][m][r], acc[1][m][r], acc[2][m][r], acc[3][m][r], acc[4][m][r], acc[5][m][r], sc4[g][e], sh4[g][e], yy);
+        else
+          w6_outputs(acc[0][m][r], acc[1][m][r], acc[2][m][r], acc[3][m][r], acc[4][m][r], acc[5][m][r], acc[NP - 2][m][r],
+                     acc[NP - 1][m][r], sc4[g][e], sh4[g][e], yy);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) y[g][j][e] = yy[j];
+        for (int j = 0; j < R; ++j) y[g][j][e] = yy[j];
       }
     // The values go to memory through a wave-private LDS tile ([row][pixel], 144-byte pixel pitch): lane (pixel, half)
     // writes its channel quads, lane (P = l / 8, q = l % 8) reads quad q of pixel 8 k + P back, so that a store instruction
     // writes the wave's 128 contiguous bytes of 8 pixels.  Straight from the accumulator layout every lane's 16 bytes were
     // a memory request of their own (a lane's neighbour in memory sits 32 lanes away): 64 requests per instruction, and a
     // conv1 layer's 128 KB per workgroup took 9 k cycles to drain (tools/w4_variants.py, EXPERIMENTS.md).
-    unsigned char* wt = dsm_raw + wave * W4_OUT_TILE;
+    unsigned char* wt = dsm_raw + wave * G::OUT_TILE;
     constexpr int PITCH = 144;
     const int P8 = lane >> 3, q8 = lane & 7;
     if (MODE == MODE_FULL) {
-      const int h = by_hp.mod(gr);   // Hp % 4 == 0: the four rows of a quad belong to one clip
+      // Quads: Hp % 4 == 0, the four rows of a quad belong to one clip and the tile drains in one pass.  Sextets straddle
+      // clips: every row looks up its own h, and the tile drains as two halves of three rows (a smaller LDS tile)
+      constexpr int RH = R == 4 ? 4 : 3;
+      const int h = by_hp.mod(gr);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j0 = 0; j0 < R; j0 += RH) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *(f32x4*)(wt + (j * 32 + pi) * PITCH + (2 * g + half) * 16) = h + j < p.H ? y[g][j] : zero4;
+        for (int j = 0; j < RH; ++j) {
+          const bool inside = (R == 4 ? h + j : by_hp.mod(gr + j0 + j)) < p.H;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int px = 8 * k + P8;
-        const int pcol = G::COLT ? m : px % TC;
-        const int pgr = 4 * (quad0 + (G::COLT ? px : m * QT + px / TC));
+          for (int g = 0; g < 4; ++g)
+            *(f32x4*)(wt + (j * 32 + pi) * PITCH + (2 * g + half) * 16) = inside ? y[g][j0 + j] : zero4;
+        }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f32x4 v = *(const f32x4*)(wt + (j * 32 + px) * PITCH + q8 * 16);
-          const size_t oi = ((size_t)(pgr + j) * p.W + pcol) * p.Cout + n_tile * 128 + wave * 32 + 4 * q8;
-          if (p.drop.thresh != 0) {
+        for (int k = 0; k < 4; ++k) {
+          const int px = 8 * k + P8;
+          const int pcol = G::COLT ? m : px % TC;
+          const int pgr = R * (quad0 + (G::COLT ? px : m * QT + px / TC));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= p.drop.mask(oi + e);
+          for (int j = 0; j < RH; ++j) {
+            f32x4 v = *(const f32x4*)(wt + (j * 32 + px) * PITCH + q8 * 16);
+            const size_t oi = ((size_t)(pgr + j0 + j) * p.W + pcol) * p.Cout + n_tile * 128 + wave * 32 + 4 * q8;
+            if (p.drop.thresh != 0) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] *= p.drop.mask(oi + e);
+            }
+            // (rows_total % 4 == 0: a quad is inside the batch or beyond it; the last sextet may be cut)
+            if ((R == 4 ? pgr : pgr + j0 + j) < p.rows_total && !(W4_KO & 64)) *(f32x4*)(p.out + oi) = v;
           }
-          if (pgr < p.rows_total && !(W4_KO & 64)) *(f32x4*)(p.out + oi) = v;
         }
       }
-    } else {   // a row quad is two pooled rows: the even lane of a column pair holds the first, the odd lane the second
-      const bool valid = by_hp_out.mod(2 * qg) + (col & 1) < p.H_out;
+    } else {
+      // A row quad is two pooled rows: the even lane of a column pair holds the first, the odd lane the second.  A sextet is
+      // three (rows_total and Hp are even, so a pooling pair never straddles clips): the third goes out in a second pass
+      // from the even lanes, 16 pooled pixels
+      constexpr int PR = R / 2;   // pooled rows of a tile
+      const int prow = PR * qg + (col & 1);
+      const bool valid = R == 4 ? by_hp_out.mod(2 * qg) + (col & 1) < p.H_out : by_hp_out.mod(prow) < p.H_out;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 t0 = y[g][0] + y[g][1], t1 = y[g][2] + y[g][3];
@@ -510,12 +547,37 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
         const int px = 8 * k + P8;
         const int pcol = px % TC, pqg = quad0 + m * QT + px / TC;
         f32x4 o = *(const f32x4*)(wt + px * PITCH + q8 * 16);
-        const size_t oi = ((size_t)(2 * pqg + (pcol & 1)) * p.W_out + (pcol >> 1)) * p.Cout + n_tile * 128 + wave * 32 + 4 * q8;
+        const int orow = PR * pqg + (pcol & 1);
+        const size_t oi = ((size_t)orow * p.W_out + (pcol >> 1)) * p.Cout + n_tile * 128 + wave * 32 + 4 * q8;
         if (p.drop.thresh != 0) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] *= p.drop.mask(oi + e);
         }
-        if (4 * pqg < p.rows_total && !(W4_KO & 64)) *(f32x4*)(p.out + oi) = o;
+        if ((R == 4 ? 4 * pqg : 2 * orow) < p.rows_total && !(W4_KO & 64)) *(f32x4*)(p.out + oi) = o;
+      }
+      if constexpr (R == 6) {
+        const bool valid2 = by_hp_out.mod(PR * qg + 2) < p.H_out;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 t2 = y[g][4] + y[g][5];
+          f32x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = 0.25f * (t2[e] + dpp_mov<DPP_QUAD_XOR1>(t2[e]));
+          if (!(col & 1)) *(f32x4*)(wt + (pi >> 1) * PITCH + (2 * g + half) * 16) = valid2 ? o : zero4;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int px = 2 * (8 * k + P8);   // the even lane's pixel
+          const int pcol = px % TC, pqg = quad0 + m * QT + px / TC;
+          f32x4 o = *(const f32x4*)(wt + (px >> 1) * PITCH + q8 * 16);
+          const int orow = PR * pqg + 2;
+          const size_t oi = ((size_t)orow * p.W_out + (pcol >> 1)) * p.Cout + n_tile * 128 + wave * 32 + 4 * q8;
+          if (p.drop.thresh != 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] *= p.drop.mask(oi + e);
+          }
+          if (2 * orow < p.rows_total && !(W4_KO & 64)) *(f32x4*)(p.out + oi) = o;
+        }
       }
     }
   }
@@ -533,27 +595,27 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
 #endif
 }
 
-template <int MODE, int TC, int MW>
+template <int MODE, int TC, int MW, int R = 4>
 int launch_w4(W4Params p, hipStream_t s) {
-  using G = W4Geom<TC, MW>;
-  const int quads = p.rows_total / 4;
+  using G = W4Geom<TC, MW, R>;
+  const int quads = (p.rows_total + R - 1) / R;   // tiles of R rows; the last sextet may be cut
   p.MT = (quads + G::PQ - 1) / G::PQ;
   unsigned grid;
   if (p.map_mode == 2) grid = (unsigned)(((p.MT + 7) / 8) * 8 * p.NT);
   else if (p.map_mode == 3 || p.map_mode == 4) grid = (unsigned)(((p.MT + 8 / p.NT - 1) / (8 / p.NT)) * 8);
   else grid = (unsigned)(p.MT * p.NT);
-  constexpr size_t lds = (size_t)2 * G::VBUF > (size_t)4 * W4_OUT_TILE ? (size_t)2 * G::VBUF : (size_t)4 * W4_OUT_TILE;
-  static_assert(lds <= 160 * 1024, "V planes exceed the LDS");
+  constexpr size_t lds = (size_t)2 * G::VBUF > (size_t)4 * G::OUT_TILE ? (size_t)2 * G::VBUF : (size_t)4 * G::OUT_TILE;
+  static_assert(lds <= 160 * 1024 && (MW == 2 || lds <= 80 * 1024), "V planes exceed the LDS (half-size form: of two workgroups)");
   static AcLdsAttr lds_attr;   // per device
-  if (ac_allow_lds((const void*)conv3x3_w4_kernel<MODE, TC, MW>, 160 * 1024, &lds_attr) != AC_OK) return AC_ERR_LAUNCH;
-  hipLaunchKernelGGL((conv3x3_w4_kernel<MODE, TC, MW>), dim3(grid), dim3(256), lds, s, p);
+  if (ac_allow_lds((const void*)conv3x3_w4_kernel<MODE, TC, MW, R>, 160 * 1024, &lds_attr) != AC_OK) return AC_ERR_LAUNCH;
+  hipLaunchKernelGGL((conv3x3_w4_kernel<MODE, TC, MW, R>), dim3(grid), dim3(256), lds, s, p);
   return ac_check_launch();
 }
 
-template <int MODE, int TC>
+template <int MODE, int TC, int R = 4>
 int launch_w4_mw(const W4Params& p, int mw, hipStream_t s) {
-  if (mw == 1) return launch_w4<MODE, TC, 1>(p, s);
-  return launch_w4<MODE, TC, 2>(p, s);
+  if (mw == 1) return launch_w4<MODE, TC, 1, R>(p, s);
+  return launch_w4<MODE, TC, 2, R>(p, s);
 }
 
 }  // namespace
@@ -564,16 +626,18 @@ static long w4_grid(int rows_total, int W, int Cout, int mw) {
   return (long)((rows_total / 4 + pq - 1) / pq) * (Cout / 128);
 }
 
+// rows: 4 = row quads (wfrag: the F(4,3) pack), 6 = row sextets (the F(6,3) pack; conv blocks 2-4: W = 32, 16, 8)
 static int w4_dispatch(const float* in, const void* wfrag, const float* scale, const float* shift, float* out, int B, int Hp,
                        int H, int W, int Cin, int Cout, int mode, int map_mode, int mw, const int* clip_frames, int need_mul,
-                       int need_add, void* stream, Drop drop) {
+                       int need_add, void* stream, Drop drop, int rows = 4) {
   if (!in || !wfrag || !scale || !shift || !out) return AC_ERR_ARG;
+  if (rows == 6 && !(W == 32 || W == 16 || W == 8)) return AC_ERR_ARG;
   if (B <= 0 || Hp <= H || (Hp & 3) || !(W == 32 || W == 16 || W == 8 || W == 4 || W == 2) || Cin % 32 || Cin < 32 || Cout % 128)
     return AC_ERR_ARG;   // (Cin % 32: the K loop walks its 16-channel steps in pairs)
   if (W == 2 ? (mode != MODE_FULL && mode != MODE_MEANW) : (mode != MODE_FULL && mode != MODE_POOL)) return AC_ERR_ARG;
   if (mode == MODE_MEANW && drop.thresh != 0) return AC_ERR_ARG;   // dropout sits BEFORE the mean over mel: use mode 0
   if ((unsigned long long)B * Hp >= (1ull << 23)) return AC_ERR_ARG;          // the epilogue finds a row's clip offset with FastDiv4::mod (float reciprocal: exact below 2^23 rows); callers chunk clips beyond it
-  if ((unsigned long long)(Cin / 16) * 18 * (Cout / 32) * 2048 >= (1ull << 31)) return AC_ERR_ARG;   // packed weights: one descriptor
+  if ((unsigned long long)(Cin / 16) * (3 * (rows + 2)) * (Cout / 32) * 2048 >= (1ull << 31)) return AC_ERR_ARG;   // packed weights: one descriptor
   W4Params p;
   p.in = in; p.wpk = wfrag; p.scale = scale; p.shift = shift; p.out = out;
   p.rows_total = B * Hp; p.Hp = Hp; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
@@ -600,6 +664,13 @@ static int w4_dispatch(const float* in, const void* wfrag, const float* scale, c
   }
   if (W == 2) mw = 2;   // column tiles
   hipStream_t s = (hipStream_t)stream;
+  if (rows == 6) {
+#define W6_CASE(TCV)                                                                     \
+  if (W == TCV) return mode == MODE_FULL ? launch_w4_mw<MODE_FULL, TCV, 6>(p, mw, s) : launch_w4_mw<MODE_POOL, TCV, 6>(p, mw, s);
+    W6_CASE(32) W6_CASE(16) W6_CASE(8)
+#undef W6_CASE
+    return AC_ERR_ARG;
+  }
 #define W4_CASE(TCV)                                                                     \
   if (W == TCV) return mode == MODE_FULL ? launch_w4_mw<MODE_FULL, TCV>(p, mw, s) : launch_w4_mw<MODE_POOL, TCV>(p, mw, s);
   W4_CASE(32) W4_CASE(16) W4_CASE(8) W4_CASE(4)
@@ -637,4 +708,22 @@ extern "C" int ac_conv3x3_bn_relu_wino43_drop(const float* in, const void* wfrag
 extern "C" long ac_conv3x3_wino43_workgroups(int B, int Hp, int W, int Cout) {
   if (B <= 0 || Hp <= 0 || (Hp & 3) || !(W == 32 || W == 16 || W == 8 || W == 4 || W == 2) || Cout % 128) return 0;
   return w4_grid(B * Hp, W, Cout, 2);
+}
+
+// The same layer on row SEXTETS (F(6,3) along time): see include/audiocaption_hip.h
+extern "C" int ac_conv3x3_bn_relu_wino63(const float* in, const void* wfrag, const float* scale, const float* shift,
+                                         float* out, int B, int Hp, int H, int W, int Cin, int Cout, int mode,
+                                         int map_mode, int tiles_per_wave, const int* clip_frames, int need_mul,
+                                         int need_add, void* stream) {
+  return w4_dispatch(in, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, tiles_per_wave, clip_frames,
+                     need_mul, need_add, stream, make_drop(0.f, 0, nullptr), 6);
+}
+
+extern "C" int ac_conv3x3_bn_relu_wino63_drop(const float* in, const void* wfrag, const float* scale, const float* shift,
+                                              float* out, int B, int Hp, int H, int W, int Cin, int Cout, int mode,
+                                              int map_mode, float drop_p, unsigned long long drop_seed,
+                                              const unsigned long long* seed_dev, void* stream) {
+  if (!(drop_p >= 0.f) || drop_p >= 1.f) return AC_ERR_ARG;
+  return w4_dispatch(in, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, 0, nullptr, 0, 0, stream,
+                     make_drop(drop_p, drop_seed, seed_dev), 6);
 }

@@ -269,6 +269,28 @@ def conv3x3_bn_relu_wino43(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, 
     return out
 
 
+def conv3x3_bn_relu_wino63(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1, need=None, dropout=None,
+                           tiles_per_wave=0):
+    """The row-SEXTET tile form of ``conv3x3_bn_relu_wino43``: F(6,3) along time, 8 positions per 6 output rows, the same
+    kernel source and the same contract (csrc/conv3x3_wino43.hip); ``wfrag`` from ``pack_conv_weight_wino63_frag``.
+    Covers W in (32, 16, 8) with modes 0 / 1; sextets run over the stacked ``B * Hp`` rows, so ``Hp % 4 == 0`` is all a
+    buffer has to keep.  Reported to observers as the "wino43" tier it is a tile form of."""
+    lib = _lib.load()
+    cf, mul, add = need if need is not None else (None, 0, 0)
+    if dropout is not None and cf is not None:
+        raise ValueError("conv3x3_bn_relu_wino63: dropout and dead-row skipping are not combined")
+    with _observed("wino43", B, Hp, H, W, Cin, Cout, mode):
+        if dropout is not None:
+            check(lib.ac_conv3x3_bn_relu_wino63_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
+                                                     Cout, mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2],
+                                                     stream()), "ac_conv3x3_bn_relu_wino63_drop")
+        else:
+            check(lib.ac_conv3x3_bn_relu_wino63(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                                mode, map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()),
+                  "ac_conv3x3_bn_relu_wino63")
+    return out
+
+
 def skinny_workspace_floats(B, Hp, W, Cin, Cout):
     """Floats of workspace ``conv3x3_bn_relu_skinny`` needs for this geometry; 0 = not a launch for that kernel (more than
     2048 pixels, W other than 2 / 4)."""
@@ -374,6 +396,30 @@ def pack_conv_weight_wino43_frag(w):
     def lay(t):
         t = t.permute(1, 2, 0).reshape(cin // 16, 2, 8, 18, cout // 32, 32)     # (step, k-half, j, tap, channel tile, n)
         return t.permute(0, 3, 4, 1, 5, 2).reshape(cin // 16, 18, cout // 32, 64, 8)
+
+    return torch.stack([lay(hi), lay(lo)], dim=3).contiguous()
+
+
+# F(6,3), points 0, +-1, +-2, +-1/2, inf: the filter transform G (rows = positions)
+WINO63_G = ((1, 0, 0), (-2 / 9, -2 / 9, -2 / 9), (-2 / 9, 2 / 9, -2 / 9), (1 / 90, 1 / 45, 2 / 45), (1 / 90, -1 / 45, 2 / 45),
+            (32 / 45, 16 / 45, 8 / 45), (32 / 45, -16 / 45, 8 / 45), (0, 0, 1))
+
+
+def pack_conv_weight_wino63_frag(w):
+    """OIHW f32 -> U = G g (F(6,3) filter transform over the time taps ky, evaluated in float64), split into bf16
+    hi + lo, in MFMA fragment order [Cin/16][24 = 3 kx x 8 positions][Cout/32][2 (hi, lo)][64 lanes][8]: the layout of
+    ``pack_conv_weight_wino43_frag`` with eight positions (csrc/conv3x3_wino43.hip, row sextets).  Elementwise torch ops only."""
+    cout, cin = w.shape[0], w.shape[1]
+    g = w.double()                                                   # (o, c, ky, kx)
+    G = WINO63_G
+    u = torch.stack([G[p][0] * g[:, :, 0] + G[p][1] * g[:, :, 1] + G[p][2] * g[:, :, 2] for p in range(8)], dim=3)   # (o, c, kx, p)
+    u = u.reshape(cout, cin, 24)                                     # tap = kx * 8 + position
+    hi = u.to(torch.bfloat16)
+    lo = (u - hi.double()).to(torch.bfloat16)
+
+    def lay(t):
+        t = t.permute(1, 2, 0).reshape(cin // 16, 2, 8, 24, cout // 32, 32)     # (step, k-half, j, tap, channel tile, n)
+        return t.permute(0, 3, 4, 1, 5, 2).reshape(cin // 16, 24, cout // 32, 64, 8)
 
     return torch.stack([lay(hi), lay(lo)], dim=3).contiguous()
 

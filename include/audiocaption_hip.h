@@ -155,6 +155,24 @@ int ac_conv3x3_bn_relu_wino43_drop(const float* in, const void* wfrag, const flo
  * launches of a few workgroups (single clips) to the K-sliced F(2,3) form instead. */
 long ac_conv3x3_wino43_workgroups(int B, int Hp, int W, int Cout);
 
+/* The row-SEXTET tile form of ac_conv3x3_bn_relu_wino43: F(6,3) along time (points 0, +-1, +-2, +-1/2, inf), 8 transformed
+ * positions per 6 output rows = 24 instead of 27 products per (cin, cout) and sextet, 11 % fewer MFMAs per output row,
+ * and 1.5 x the rows per workgroup (fewer rounds of workgroups, each paying its prologue and epilogue once).  Same kernel
+ * source, arguments, layouts, epilogue modes, tiles_per_wave and ragged-batch arguments as the quad form; the stacked
+ * B * Hp rows are one signal with zero rows between clips, so a sextet may straddle two clips and the last one may be
+ * cut (Hp % 4 == 0 stays the contract of every buffer; every output row is masked by its own h < H).  Covers W = 32, 16, 8
+ * (conv blocks 2-4; modes 0, 1), Cin % 32 == 0, Cout % 128 == 0; wfrag [Cin/16][3 kx x 8 positions][Cout/32][hi, lo]
+ * [64 lanes][8] bf16 (U = G g in f64, then split).  The input transform is evaluated in f32 before the split as in the
+ * quad form; the larger constants of F(6,3) cost nothing against the 2^-16 operand error (tests/test_wino63_ref_cpu.py).
+ * AC_ERR_ARG for shapes outside this list. */
+int ac_conv3x3_bn_relu_wino63(const float* in, const void* wfrag, const float* scale, const float* shift, float* out,
+                              int B, int Hp, int H, int W, int Cin, int Cout, int mode, int map_mode, int tiles_per_wave,
+                              const int* clip_frames, int need_mul, int need_add, void* stream);
+/* ... followed by F.dropout in the epilogue (see ac_conv3x3_bn_relu_wino1d_drop). */
+int ac_conv3x3_bn_relu_wino63_drop(const float* in, const void* wfrag, const float* scale, const float* shift, float* out,
+                                   int B, int Hp, int H, int W, int Cin, int Cout, int mode, int map_mode, float drop_p,
+                                   unsigned long long drop_seed, const unsigned long long* seed_dev, void* stream);
+
 /* Conv block 1 at f32 grade in ONE kernel (csrc/conv3x3_block1_w4.hip): conv1 (Cin = 1) + BN + ReLU is computed straight
  * into the staging of conv2, conv2 + BN + ReLU + 2x2 average pool runs as F(4,3) on split-bf16 operands; persistent
  * workgroups (one per CU) walk tiles of 8 rows x 64 columns.  The 64-channel intermediate never exists in HBM.

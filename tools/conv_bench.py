@@ -71,6 +71,13 @@ def main():
                 tiles = int(algo[7:]) if len(algo) > 6 else 0          # "wino43", "wino43x2", "wino43x3"
                 fn = lambda: K.conv3x3_bn_relu_wino43(x, wp, sc, sh, out, B, Hp, H, W, Cin, Cout, mode, args.map_mode,
                                                       tiles_per_wave=tiles)
+            elif algo.startswith("wino63"):                            # row sextets: "wino63", "wino63x1", "wino63x2"
+                if W not in (32, 16, 8) or Cout % 128:
+                    continue
+                wp = K.pack_conv_weight_wino63_frag(w)
+                tiles = int(algo[7:]) if len(algo) > 6 else 0
+                fn = lambda: K.conv3x3_bn_relu_wino63(x, wp, sc, sh, out, B, Hp, H, W, Cin, Cout, mode, args.map_mode,
+                                                      tiles_per_wave=tiles)
             elif algo == "f16x2":
                 wp, inv = K.pack_conv_weight_f16x2_frag(w)
                 sc2 = (sc * inv).contiguous()

@@ -2,6 +2,7 @@
 
     python tools/w4_variants.py --build [name=flags ...]   # here (no GPU): tools/bin/libw4_<name>.so
     python tools/w4_variants.py [--layers ...] [--tiles N]  # on the GPU box: microseconds per launch, variants interleaved
+    python tools/w4_variants.py --entry wino63 ...          # the same through the row-sextet entry (F(6,3); W6_RING)
 
 Knockout bits (W4_KO): 1 weight loads, 2 A-fragment reads, 4 plane stores, 8 row loads, 16 barrier, 32 MFMAs (results
 are then wrong).  W4_RING / W4_ADEPTH: prefetch depths."""
@@ -66,6 +67,7 @@ def main():
     ap.add_argument("--tiles", type=int, default=2)
     ap.add_argument("--layers", default="b2c1,b2c2,b3c1,b3c2,b4c1,b4c2,b5c1,b5c2")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (default: all built ones)")
+    ap.add_argument("--entry", default="wino43", choices=["wino43", "wino63"], help="row quads | row sextets")
     args = ap.parse_args()
     if args.build:
         specs = {s.split("=", 1)[0]: [f for f in s.split("=", 1)[1].split(",") if f] for s in args.specs} if args.specs else DEFAULT
@@ -81,8 +83,8 @@ def main():
     libs = {}
     for v in names:
         lib = ctypes.CDLL(os.path.join(BIN, f"libw4_{v}.so"))
-        lib.ac_conv3x3_bn_relu_wino43.restype = I
-        lib.ac_conv3x3_bn_relu_wino43.argtypes = [P] * 5 + [I] * 9 + [P, I, I, P]
+        getattr(lib, "ac_conv3x3_bn_relu_" + args.entry).restype = I
+        getattr(lib, "ac_conv3x3_bn_relu_" + args.entry).argtypes = [P] * 5 + [I] * 9 + [P, I, I, P]
         libs[v] = lib
         if v.startswith("clk"):
             lib.ac_w4_clk_read.restype = I
@@ -91,19 +93,19 @@ def main():
     print("layer   " + " ".join(f"{v:>9s}" for v in names), flush=True)
     tot = {v: 0.0 for v in names}
     for name, H, Hp, W, Cin, Cout, mode in LAYERS:
-        if name not in args.layers.split(",") or Cout % 128 or W not in (32, 16, 8, 4):
+        if name not in args.layers.split(",") or Cout % 128 or W not in ((32, 16, 8, 4) if args.entry == "wino43" else (32, 16, 8)):
             continue
         x = torch.randn(B * Hp, W, Cin, device=dev)
         x.view(B, Hp, W, Cin)[:, H:] = 0
         w = torch.randn(Cout, Cin, 3, 3, device=dev) * (2.0 / (9 * Cin)) ** 0.5
         sc, sh = torch.rand(Cout, device=dev) + 0.5, torch.randn(Cout, device=dev) * 0.1
         out = torch.empty({0: (B * Hp, W, Cout), 1: (B * Hp // 2, W // 2, Cout)}[mode], device=dev)
-        wp = K.pack_conv_weight_wino43_frag(w)
+        wp = (K.pack_conv_weight_wino43_frag if args.entry == "wino43" else K.pack_conv_weight_wino63_frag)(w)
         best = {v: 1e9 for v in names}
         for _ in range(args.rounds):
             for v in names:
                 def fn():
-                    rc = libs[v].ac_conv3x3_bn_relu_wino43(x.data_ptr(), wp.data_ptr(), sc.data_ptr(), sh.data_ptr(), out.data_ptr(),
+                    rc = getattr(libs[v], "ac_conv3x3_bn_relu_" + args.entry)(x.data_ptr(), wp.data_ptr(), sc.data_ptr(), sh.data_ptr(), out.data_ptr(),
                                                            B, Hp, H, W, Cin, Cout, mode, -1, args.tiles, None, 0, 0,
                                                            torch.cuda.current_stream().cuda_stream)
                     assert rc == 0, rc
