@@ -247,6 +247,7 @@ SIGNATURES = {
     "ac_htsat_token_mean": (_I, [_P, _P, _I, _I, _I, _P]),
     "ac_gelu": (_I, [_P, _P, _L, _P]),
     "ac_mfma_bf16_probe": (_I, [_P, _I, _I, _P]),
+    "ac_split_bf16_probe": (_I, [_P, _L, _P, _P, _P]),
     "ac_placement_probe": (_I, [_P, _I, _I, _I, _P]),
     "ac_stream_create_cu_mask": (_I, [_I, _I, _P]),
     "ac_stream_destroy": (_I, [_P]),

@@ -21,6 +21,8 @@
 // i = 4*window + 2*dy + dx, so the four pixels of a pooling window sit in four consecutive
 // accumulator registers of one lane and pooling costs three adds in the epilogue.
 #include "ac_common.h"
+#include "ac_conv_tile.h"
+#include "ac_split_bf16.h"
 
 namespace {
 
@@ -60,7 +62,7 @@ struct F16Guard {
   }
 };
 
-enum { MODE_FULL = 0, MODE_POOL = 1, MODE_MEANW = 2, MODE_LINEAR = 3 };  // LINEAR: FULL without the ReLU (1-tap GEMM use)
+enum { MODE_LINEAR = 3 };  // beside the MODE_* of ac_conv_tile.h: FULL without the ReLU (1-tap GEMM use)
 
 // ---- block -> (m_tile, n_tile); block b runs on XCD b % 8 (speed only, never correctness) ----
 __device__ __forceinline__ bool conv_block_map(const ConvParams& p, int& m_tile, int& n_tile) {
@@ -92,23 +94,6 @@ __device__ __forceinline__ bool conv_block_map(const ConvParams& p, int& m_tile,
 // Mapping those to window POSITIONS 0-3 / 4-7 makes each hardware group read one compact half of the tile
 // (2x8, 4x4 or 8x2 pixels), which a suitable patch row pitch then spreads over all 16 bank slots.
 __device__ __forceinline__ int window_pos(int q) { return (0x73261540 >> (4 * q)) & 7; }  // [0,4,5,1,6,2,3,7]
-
-// x mod d (and x / d) for 0 <= x < 2^23 with a reciprocal computed once per wave: the epilogues need the row inside the
-// clip of 16-64 output rows per wave, and an integer division by the run-time Hp costs ~25 instructions each.
-struct FastDiv {
-  int d;
-  float inv;
-  __device__ __forceinline__ explicit FastDiv(int d_) : d(d_), inv(1.0f / (float)d_) {}
-  __device__ __forceinline__ int div(int x, int& rem) const {
-    int q = (int)((float)x * inv);
-    int r = x - q * d;
-    if (r < 0) { r += d; --q; }
-    if (r >= d) { r -= d; ++q; }
-    rem = r;
-    return q;
-  }
-  __device__ __forceinline__ int mod(int x) const { int r; div(x, r); return r; }
-};
 
 // ---- epilogue: BN scale/shift, ReLU, pooling, zero rows; lanes 0..31 store 32 consecutive channels ----
 // acc[m][n] = 32x32 tile (m-th pixel tile, n-th channel tile of this wave), MFMA row i = 4*window + 2*dy + dx
@@ -309,11 +294,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(ConvParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Split-bf16 ("bf16x3") variant of the same implicit GEMM for the 1e-3-logit precision tier:
-// every f32 operand is split into two bf16 numbers, x = hi + lo (hi = RNE(x), lo = RNE(x - hi), 16
-// significant bits together), and the product is accumulated in f32 as hi*hi + hi*lo + lo*hi on
-// v_mfma_f32_32x32x16_bf16.  Three bf16 MFMAs replace eight f32 MFMAs (K = 16): 5.3x the matrix rate of
-// the exact-f32 path at ~2^-16 relative operand error.  Activations stay f32 in HBM: the halo patch is
+// Split-bf16 ("bf16x3") variant of the same implicit GEMM for the 1e-3-logit precision tier, on the
+// operand arithmetic of csrc/ac_split_bf16.h.  Three bf16 MFMAs replace eight f32 MFMAs (K = 16): 5.3x
+// the matrix rate of the exact-f32 path.  Activations stay f32 in HBM: the halo patch is
 // split once when it is staged (and then re-used by 9 taps x all channel tiles), weights are split
 // offline.  LDS holds a hi and a lo plane of bf16 rows: 32 channels = 64 bytes + 16 pad (80-byte rows keep
 // the 16-byte fragment reads aligned and spread over the banks).
@@ -329,26 +312,7 @@ __host__ __device__ __forceinline__ int patch_row_pad_slots(int TC) {
   return TC >= 8 ? ((8 - base) & 15) : (TC == 4 ? ((4 - base) & 7) : ((2 - base) & 3));
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int BROW = 40;  // bf16 elements per LDS row (32 + 8 pad)
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// x (4 floats) -> packed hi (2 dwords) and lo (2 dwords) bf16 quadruples
-__device__ __forceinline__ void split_bf16x4(const f32x4 x, u32x2& hi, u32x2& lo) {
-  hi.x = cvt_pk_bf16(x[0], x[1]);
-  hi.y = cvt_pk_bf16(x[2], x[3]);
-  const float h0 = __builtin_bit_cast(float, hi.x << 16), h1 = __builtin_bit_cast(float, hi.x & 0xffff0000u);
-  const float h2 = __builtin_bit_cast(float, hi.y << 16), h3 = __builtin_bit_cast(float, hi.y & 0xffff0000u);
-  lo.x = cvt_pk_bf16(x[0] - h0, x[1] - h1);
-  lo.y = cvt_pk_bf16(x[2] - h2, x[3] - h3);
-}
 
 template <int BN, int MODE>
 __global__ __launch_bounds__(256, 1) void conv3x3_bf16x3_kernel(ConvParams p) {
@@ -487,11 +451,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_bf16x3_kernel(ConvParams p) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int n = 0; n < NTW; ++n) {
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[m], wh[n], acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], wl[n], acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], wh[n], acc[m][n], 0, 0, 0);
-          }
+          for (int n = 0; n < NTW; ++n) acc[m][n] = mfma_bf16x3(ah[m], al[m], wh[n], wl[n], acc[m][n]);
       }
 #ifndef AC_ABL_NORING
       w_store((it + 1) & 1, breg);
@@ -882,9 +842,7 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 2) void conv3x3_gw_kernel(Conv
 #pragma unroll
           for (int n = 0; n < NTW; ++n) {
             if (PREC == 0) {
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[m], wc[ks][n][0], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], wc[ks][n][1], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], wc[ks][n][0], acc[m][n], 0, 0, 0);
+              acc[m][n] = mfma_bf16x3(ah[m], al[m], wc[ks][n][0], wc[ks][n][1], acc[m][n]);
             } else {
               const f16x8 a = __builtin_bit_cast(f16x8, ah[m]);
               acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, wc[ks][n][1]), acc[m][n], 0, 0, 0);

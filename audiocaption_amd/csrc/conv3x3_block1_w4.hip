@@ -59,8 +59,6 @@ namespace {
 __device__ unsigned long long b1_clk[8];
 #endif
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct B1Params {
   const float* in;       // FORM 1, 2: [B*Hp][64] log-mel after bn0; FORM 0: [B*Hp][64][64] conv1 output
   const float* w1;       // [64][9]
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256, 1) void block1_w4_kernel(B1Params p) {
   const int cg = wave & 1, wq = wave >> 1;   // channel tile, quad of this wave's two MFMA tiles (columns 0-31, 32-63)
   const int nblk = (int)gridDim.x;
 
-  auto tile_live = [&](int t) { return w4_rows_live(8 * t, 8, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add); };
+  auto tile_live = [&](int t) { return rows_live(8 * t, 8, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add); };
   auto zero_tile = [&](int t) {   // 4 pooled rows x 32 columns x 64 channels
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     float* o = p.out + (size_t)t * 4 * 32 * 64;
@@ -429,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void block1_w4_kernel(B1Params p) {
 
   const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)p.scale, 0, 256, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsh = __builtin_amdgcn_make_buffer_rsrc((void*)p.shift, 0, 256, 0x00020000);
-  const FastDiv4 by_hp_out(p.Hp / 2);
+  const FastDiv by_hp_out(p.Hp / 2);
   const int chw = cg * 32 + 4 * half;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 

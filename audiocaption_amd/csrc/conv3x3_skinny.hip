@@ -13,13 +13,12 @@
 // to eight 32-pixel MFMA tiles x one slice of the (input channel) loop; a wave streams its 32 channels' fragments
 // (1 KiB per instruction, straight from the fragment-ordered pack of ac_conv3x3_bn_relu_bf16x3_gw) through a register ring
 // EIGHT groups deep - 16 KB in flight per wave, 64 KB per CU - while each fragment pair feeds 3 x (pixel tiles) MFMAs
-// (hi*lo + lo*hi + hi*hi on v_mfma_f32_32x32x16_bf16, f32 accumulate: the "bf16x3" tier's arithmetic, 2^-16 operand
-// error).  The input patch of a 32-channel chunk (all pixels + halo, split into bf16 hi | lo once) is double-buffered in
-// LDS.  Every slice stores its raw sums to workspace[slice][pixel][Cout]; skinny_finish_kernel adds the slices IN ORDER
-// (deterministic) and applies BN / ReLU / pool / mean / dropout.
+// (the "bf16x3" tier's arithmetic: csrc/ac_split_bf16.h).  The input patch of a 32-channel chunk (all pixels + halo, split
+// into bf16 hi | lo once) is double-buffered in LDS.  Every slice stores its raw sums to workspace[slice][pixel][Cout];
+// skinny_finish_kernel adds the slices IN ORDER (deterministic) and applies BN / ReLU / pool / mean / dropout.
 #include "ac_common.h"
 #include "ac_drop.h"
-#include "ac_wino43.h"   // bf16x8, split_bf16x4
+#include "ac_split_bf16.h"
 #include <type_traits>
 
 namespace {

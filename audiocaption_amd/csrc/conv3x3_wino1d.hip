@@ -10,10 +10,10 @@
 //     M_p[pair, w, cout] = sum_kx sum_cin V_p[pair, w + kx - 1, cin] U_p,kx[cout, cin]    (4 positions x 3 mel taps)
 //     y(2j) = M0 + M1 + M2        y(2j+1) = M1 - M2 - M3                                  (output transform, epilogue)
 // i.e. 12 products per (cin, cout) and row pair instead of 18: 1.5x fewer multiplications than the direct form.  Every
-// product runs on split-bf16 operands like the "bf16x3" tier (x = hi + lo, hi*hi + hi*lo + lo*hi on
-// v_mfma_f32_32x32x16_bf16, f32 accumulation: 2^-16 relative operand error), so a f32 product costs 3 / 1.5 = TWO bf16
-// MFMA products - what the fp16-activation tier pays - while the activations stay f32 in HBM and the result stays
-// f32-grade (greedy logits within 3e-5 of the fp32 CPU reference: tests/wino_split_emulation.py, tests/test_gpu_model.py).
+// product runs on split-bf16 operands like the "bf16x3" tier (csrc/ac_split_bf16.h), so a f32 product costs 3 / 1.5 =
+// TWO bf16 MFMA products - what the fp16-activation tier pays - while the activations stay f32 in HBM and the result
+// stays f32-grade (greedy logits within 3e-5 of the fp32 CPU reference: tests/wino_split_emulation.py,
+// tests/test_gpu_model.py).
 // The 2-D form F(2x2,3x3) (1.33 products) was priced and dropped: its 16 accumulator sets per output tile cap a CU at
 // 64 x 64 (tile, channel) outputs in flight, and at that size the transformed operands (4 KB of fresh fragments per
 // three MFMAs) exceed what LDS and the L1 can deliver to the matrix cores.
@@ -38,12 +38,11 @@
 #include <type_traits>
 
 #include "ac_common.h"
+#include "ac_conv_tile.h"
 #include "ac_drop.h"
+#include "ac_split_bf16.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // Development only (tools/w1_knockout.py): -DW1_KO=<bits> removes one ingredient of the K loop at a time to price it
 // (results are then wrong).  1 weight loads, 2 A-fragment reads, 4 plane stores, 8 patch loads, 16 barrier, 32 MFMAs.
@@ -101,41 +100,6 @@ struct W1Params {
   Drop drop;
 };
 
-enum { MODE_FULL = 0, MODE_POOL = 1, MODE_MEANW = 2 };
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// x (4 floats) -> packed hi (2 dwords) and lo (2 dwords) bf16 quadruples: hi = RNE(x), lo = RNE(x - hi)
-__device__ __forceinline__ void split_bf16x4(const f32x4 x, u32x2& hi, u32x2& lo) {
-  hi.x = cvt_pk_bf16(x[0], x[1]);
-  hi.y = cvt_pk_bf16(x[2], x[3]);
-  const float h0 = __builtin_bit_cast(float, hi.x << 16), h1 = __builtin_bit_cast(float, hi.x & 0xffff0000u);
-  const float h2 = __builtin_bit_cast(float, hi.y << 16), h3 = __builtin_bit_cast(float, hi.y & 0xffff0000u);
-  lo.x = cvt_pk_bf16(x[0] - h0, x[1] - h1);
-  lo.y = cvt_pk_bf16(x[2] - h2, x[3] - h3);
-}
-
-// x mod d / x div d for 0 <= x < 2^23 with one reciprocal per wave (an integer division by a run-time value is ~25
-// instructions; the epilogue needs the row inside the clip for every stored row)
-struct FastDiv {
-  int d;
-  float inv;
-  __device__ __forceinline__ explicit FastDiv(int d_) : d(d_), inv(1.0f / (float)d_) {}
-  __device__ __forceinline__ int div(int x, int& rem) const {
-    int q = (int)((float)x * inv);
-    int r = x - q * d;
-    if (r < 0) { r += d; --q; }
-    if (r >= d) { r -= d; ++q; }
-    rem = r;
-    return q;
-  }
-  __device__ __forceinline__ int mod(int x) const { int r; div(x, r); return r; }
-};
-
 // block -> (m_tile, n_tile); block b runs on XCD b % 8 (speed only).  map_mode 1: one XCD streams one weight column
 // slab (weight-heavy layers, NT % 8 == 0); 2: the channel tiles of a pixel tile share an L2; 3: NT in {1, 2, 4}: every
 // XCD owns one weight slab; 4: row blocks (below)
@@ -169,25 +133,8 @@ __device__ __forceinline__ bool block_map(const W1Params& p, int& m_tile, int& n
   return true;
 }
 
-// Dead block: every one of its `nrows` rows from `row0` lies in the padding of its clip(s) - beyond the geometry's H valid
-// rows, or (ragged batches) beyond the rows the clip's own length can bring to an output frame.  Such a block convolves
-// nothing and stores zeros.
 __device__ __forceinline__ bool w1_block_live(const W1Params& p, int row0, int nrows) {
-  bool live = false;
-  if (row0 < p.rows_total) {
-    const int r_end = row0 + nrows < p.rows_total ? row0 + nrows : p.rows_total;
-    int b = row0 / p.Hp;
-    for (int base = b * p.Hp; base < r_end; base += p.Hp, ++b) {
-      const int lo = (row0 > base ? row0 : base) - base;
-      int lim = p.H;
-      if (p.clip_frames) {
-        const int need = p.need_mul * p.clip_frames[b] + p.need_add;
-        lim = need < lim ? need : lim;
-      }
-      live = live || lo < lim;
-    }
-  }
-  return live;
+  return rows_live(row0, nrows, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add);
 }
 
 // TC: columns of the block (4, or 2 for the 2-column layers).  FULLW: the block spans the whole image width (W == TC):
@@ -432,9 +379,7 @@ __global__ __launch_bounds__((W1Geom<TC, FULLW, WIDE, CW>::THREADS), 2) void con
               asm volatile("" :: "v"(ah), "v"(al), "v"(wr[gi % RING][0]), "v"(wr[gi % RING][1]));
               continue;
             }
-            acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wr[gi % RING][0], acc[q][m], 0, 0, 0);
-            acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wr[gi % RING][1], acc[q][m], 0, 0, 0);
-            acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wr[gi % RING][0], acc[q][m], 0, 0, 0);
+            acc[q][m] = mfma_bf16x3(ah, al, wr[gi % RING][0], wr[gi % RING][1], acc[q][m]);
           }
           if (W1_PRIO) __builtin_amdgcn_s_setprio(0);
           // the next step's planes, a piece per group

@@ -12,10 +12,10 @@
 //     M_p[quad, w, cout] = sum_kx sum_cin V_p[quad, w + kx - 1, cin] U_p,kx[cout, cin]            (6 positions x 3 mel taps)
 //     y0 = M0+M1+M2+M3+M4   y1 = (M1-M2) + 2 (M3-M4)   y2 = (M1+M2) + 4 (M3+M4)   y3 = (M1-M2) + 8 (M3-M4) + M5
 // i.e. 18 products per (cin, cout) and row quad instead of 36: HALF the multiplications of the direct form (F(2,3): 2/3).
-// Every product runs on split-bf16 operands (x = hi + lo, hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16, f32
-// accumulation), so a f32 product costs 3 / 2 = 1.5 bf16 MFMA products.  V is transformed in f32 BEFORE the split and U in
-// f64 before the split, so the larger transform constants of F(4,3) do not amplify the 2^-17 operand error: greedy logits
-// within 3e-5 of the fp32 CPU reference, the same as F(2,3) and the direct split form (tests/wino_split_emulation.py).
+// Every product runs on split-bf16 operands (csrc/ac_split_bf16.h), so a f32 product costs 3 / 2 = 1.5 bf16 MFMA
+// products.  V is transformed in f32 BEFORE the split and U in f64 before the split, so the larger transform constants of
+// F(4,3) do not amplify the 2^-17 operand error: greedy logits within 3e-5 of the fp32 CPU reference, the same as F(2,3)
+// and the direct split form (tests/wino_split_emulation.py).
 //
 // Work decomposition.  Six accumulator sets per (pixel tile, channel tile) do not fit two waves per SIMD, so a workgroup is
 // FOUR waves, one per SIMD, each with up to 512 registers: a wave owns 32 output channels x MW = 2 MFMA tiles of 32
@@ -87,8 +87,6 @@ struct W4Params {
   int need_mul, need_add;
   Drop drop;
 };
-
-enum { MODE_FULL = 0, MODE_POOL = 1, MODE_MEANW = 2 };   // MEANW: mean over the two mel columns of block 6 (column tiles)
 
 // block -> (row block, channel tile); block b runs on XCD b % 8 (speed only).  1: an XCD streams one weight column slab
 // (NT % 8 == 0); 3: NT in {1, 2, 4, 8}: the channel tiles of a row block sit on 8 / NT ... XCDs each owning one slab, row
@@ -201,7 +199,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
       for (int r = 0; r < 16; ++r) acc[q][m][r] = 0.f;
 
   const int row0 = R * quad0;
-  const bool live = w4_rows_live(row0, R * PQ, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add);
+  const bool live = rows_live(row0, R * PQ, p.rows_total, p.Hp, p.H, p.clip_frames, p.need_mul, p.need_add);
   const bool all_pad = !live;
   const int nstep = p.Cin / KS;
   if (!all_pad) {
@@ -430,7 +428,7 @@ __global__ __launch_bounds__(256, MW == 1 ? 2 : 1) void conv3x3_w4_kernel(W4Para
   // quad i / TC) and, in register quad g, the four consecutive channels 8 g + 4 (l / 32) .. + 3 of the wave's 32: one
   // 16-byte store per (tile, g, row).  The two columns of a pooling window sit in lanes l, l ^ 1. ----
   const int chw = n_tile * 128 + wave * 32 + 4 * half;
-  const FastDiv4 by_hp(p.Hp), by_hp_out(MODE == MODE_POOL ? p.Hp_out : 1);
+  const FastDiv by_hp(p.Hp), by_hp_out(MODE == MODE_POOL ? p.Hp_out : 1);
   const int pi = lane & 31;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 sc4[4], sh4[4];
@@ -636,7 +634,7 @@ static int w4_dispatch(const float* in, const void* wfrag, const float* scale, c
     return AC_ERR_ARG;   // (Cin % 32: the K loop walks its 16-channel steps in pairs)
   if (W == 2 ? (mode != MODE_FULL && mode != MODE_MEANW) : (mode != MODE_FULL && mode != MODE_POOL)) return AC_ERR_ARG;
   if (mode == MODE_MEANW && drop.thresh != 0) return AC_ERR_ARG;   // dropout sits BEFORE the mean over mel: use mode 0
-  if ((unsigned long long)B * Hp >= (1ull << 23)) return AC_ERR_ARG;          // the epilogue finds a row's clip offset with FastDiv4::mod (float reciprocal: exact below 2^23 rows); callers chunk clips beyond it
+  if ((unsigned long long)B * Hp >= (1ull << 23)) return AC_ERR_ARG;          // the epilogue finds a row's clip offset with FastDiv::mod (float reciprocal: exact below 2^23 rows); callers chunk clips beyond it
   if ((unsigned long long)(Cin / 16) * (3 * (rows + 2)) * (Cout / 32) * 2048 >= (1ull << 31)) return AC_ERR_ARG;   // packed weights: one descriptor
   W4Params p;
   p.in = in; p.wpk = wfrag; p.scale = scale; p.shift = shift; p.out = out;

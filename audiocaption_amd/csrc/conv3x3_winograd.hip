@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "ac_common.h"
+#include "ac_conv_tile.h"
 
 // Development builds only (-DAC_WINO_ABLATE=mask): bit0 no weight ring, bit1 no barriers, bit2 no transform, bit3 no patch
 // reload, bit4 no epilogue - isolates what each phase of the kernel costs.  0 in the product library.
@@ -50,8 +51,6 @@ struct WinoParams {
   int Hp_out, H_out, W_out;
   int map_mode;
 };
-
-enum { MODE_FULL = 0, MODE_POOL = 1, MODE_MEANW = 2 };
 
 // Input transform B^T d B, per index x in 0..3 (rows and columns alike):
 //   x=0: d0 - d2   x=1: d1 + d2   x=2: d2 - d1   x=3: d1 - d3

@@ -11,46 +11,21 @@
 //
 //   ac_conv5x5_first            Cin = 1, 25 taps, Cout = 64: f32 FMAs, BN + ReLU + the 2x2 pool fused - the full-resolution
 //                               64-channel map never reaches HBM.
-//   ac_conv5x5_bn_relu_bf16x3   implicit GEMM, M = pixels, N = Cout, K = 25 * Cin, on split-bf16 operands (x = hi + lo, RNE
-//                               both, lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, f32 accumulation): the arithmetic of
-//                               the "bf16x3" 3x3 tier.  A 256-thread block owns 128 pixels (TR rows x TC columns, TC =
-//                               min(W, 16)) by 128 channels; per 32-channel K chunk it stages the (TR+4) x (TC+4) halo patch in
-//                               LDS once, already split, and all 25 taps read it.  Weights come straight from L2 in MFMA
-//                               fragment order, one tap ahead in registers.
+//   ac_conv5x5_bn_relu_bf16x3   implicit GEMM, M = pixels, N = Cout, K = 25 * Cin, on split-bf16 operands
+//                               (csrc/ac_split_bf16.h): the arithmetic of the "bf16x3" 3x3 tier.  A 256-thread block owns
+//                               128 pixels (TR rows x TC columns, TC = min(W, 16)) by 128 channels; per 32-channel K chunk it
+//                               stages the (TR+4) x (TC+4) halo patch in LDS once, already split, and all 25 taps read it.
+//                               Weights come straight from L2 in MFMA fragment order, one tap ahead in registers.
 //   ac_pack_conv5x5_weight_bf16x3   OIHW f32 -> that fragment order, on the device.
 #include "ac_common.h"
+#include "ac_split_bf16.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TAPS = 25;
 constexpr int BROW = 40;            // bf16 elements per staged pixel: 32 channels + 8 pad (80 bytes = 5 slots of 16 bytes)
 constexpr int BM = 128, BN = 128;   // pixels and channels per block
 constexpr int PLANE_BYTES = 23040;  // largest patch plane: TC = 8 -> 20 rows of 72 slots
-
-// round-to-nearest-even bf16 of a finite f32, as the upper half of a dword
-__device__ __forceinline__ unsigned bf16_rne(float x) {
-  const unsigned u = __builtin_bit_cast(unsigned, x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_up(unsigned h) { return __builtin_bit_cast(float, h << 16); }
-
-// x (4 floats) -> packed hi (2 dwords) and lo (2 dwords): hi = RNE(x), lo = RNE(x - hi)
-__device__ __forceinline__ void split4(const f32x4 x, u32x2& hi, u32x2& lo) {
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    h[e] = bf16_rne(x[e]);
-    l[e] = bf16_rne(x[e] - bf16_up(h[e]));
-  }
-  hi.x = h[0] | (h[1] << 16);
-  hi.y = h[2] | (h[3] << 16);
-  lo.x = l[0] | (l[1] << 16);
-  lo.y = l[2] | (l[3] << 16);
-}
 
 struct Conv5Params {
   const float* in;
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void conv5x5_bf16x3_kernel(Conv5Params p) {
         if (gr >= 0 && gr < p.rows_total && gc >= 0 && gc < p.W && (gr % p.Hp) < p.H)
           v = *(const f32x4*)(p.in + ((size_t)gr * p.W + gc) * p.Cin + c * 32 + c4 * 4);
         u32x2 hi, lo;
-        split4(v, hi, lo);
+        split_bf16x4(v, hi, lo);
         *(u32x2*)(sAh + pr * PITCH + pc * BROW + c4 * 4) = hi;
         *(u32x2*)(sAl + pr * PITCH + pc * BROW + c4 * 4) = lo;
       }
@@ -161,11 +136,7 @@ __global__ __launch_bounds__(256, 2) void conv5x5_bf16x3_kernel(Conv5Params p) {
 #pragma unroll
           for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int n = 0; n < 2; ++n) {
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[m], bcur[ks][n][0], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bcur[ks][n][1], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bcur[ks][n][0], acc[m][n], 0, 0, 0);
-            }
+            for (int n = 0; n < 2; ++n) acc[m][n] = mfma_bf16x3(ah[m], al[m], bcur[ks][n][0], bcur[ks][n][1], acc[m][n]);
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -288,19 +259,12 @@ __global__ __launch_bounds__(256) void pack5x5_kernel(const float* w, u32x4* out
   const int c = (int)(q / TAPS);
   const int co = nt * 32 + (lane & 31);
   const int ci0 = c * 32 + ks * 16 + (lane >> 5) * 8;
-  unsigned h[8];
+  float x[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float x = w[((size_t)co * Cin + ci0 + e) * TAPS + tap];
-    const unsigned hi = bf16_rne(x);
-    h[e] = plane == 0 ? hi : bf16_rne(x - bf16_up(hi));
-  }
-  u32x4 r;
-  r.x = h[0] | (h[1] << 16);
-  r.y = h[2] | (h[3] << 16);
-  r.z = h[4] | (h[5] << 16);
-  r.w = h[6] | (h[7] << 16);
-  out[u] = r;
+  for (int e = 0; e < 8; ++e) x[e] = w[((size_t)co * Cin + ci0 + e) * TAPS + tap];
+  u32x4 hi, lo;
+  split_bf16_pairs<4>(x, hi, lo);
+  out[u] = plane == 0 ? hi : lo;
 }
 
 }  // namespace

@@ -32,7 +32,7 @@
 // ds_read_b128 group hit 16 different 16-byte bank slots); every load of the 32 rows is requested before the first LayerNorm
 // reduction.  The four waves split the tile's columns (halves) and K (halves / quarters); the K parts meet in LDS.
 #include "ac_common.h"
-#include "ac_wino43.h"   // bf16x8, u32x2, cvt_pk_bf16
+#include "ac_split_bf16.h"
 #include "../../include/audiocaption_hip.h"
 
 namespace {
@@ -54,20 +54,6 @@ struct WideParams {
   int M, N, K, relu, ntb, vec;
 };
 
-__device__ __forceinline__ float bf_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
-
-// four floats -> three packed bf16 quadruples (2 dwords each)
-__device__ __forceinline__ void split3_bf16x4(const f32x4 x, u32x2& p0, u32x2& p1, u32x2& p2) {
-  p0.x = cvt_pk_bf16(x[0], x[1]);
-  p0.y = cvt_pk_bf16(x[2], x[3]);
-  const float r0 = x[0] - bf_lo(p0.x), r1 = x[1] - bf_hi(p0.x), r2 = x[2] - bf_lo(p0.y), r3 = x[3] - bf_hi(p0.y);
-  p1.x = cvt_pk_bf16(r0, r1);
-  p1.y = cvt_pk_bf16(r2, r3);
-  p2.x = cvt_pk_bf16(r0 - bf_lo(p1.x), r1 - bf_hi(p1.x));
-  p2.y = cvt_pk_bf16(r2 - bf_lo(p1.y), r3 - bf_hi(p1.y));
-}
-
 // W [N][K] f32 (row pitch ldw) -> fragment pack.  One thread per (tile, k step, lane): 8 values, three 16-byte stores.
 __global__ void wide_pack_kernel(const float* W, long ldw, int N, int K, unsigned char* out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,7 +72,6 @@ __global__ void wide_pack_kernel(const float* W, long ldw, int N, int K, unsigne
   u32x2 a0, a1, a2, b0, b1, b2;
   split3_bf16x4(a, a0, a1, a2);
   split3_bf16x4(b, b0, b1, b2);
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   unsigned char* dst = out + (g * 3) * 1024 + (size_t)lane * 16;
   *(u32x4*)(dst) = (u32x4){a0.x, a0.y, b0.x, b0.y};
   *(u32x4*)(dst + 1024) = (u32x4){a1.x, a1.y, b1.x, b1.y};

@@ -3,10 +3,9 @@
 // bench.py runs it next to the timed region so that `roofline` can say how much of the gap to the nominal 2.5 PFLOP/s is
 // the clock the part holds while its matrix pipes are busy (~1.7 of 2.4 GHz) and how much is the kernel.
 #include "ac_common.h"
+#include "ac_split_bf16.h"
 
 namespace {
-
-typedef __bf16 pb_bf16x8 __attribute__((ext_vector_type(8)));
 
 __global__ __launch_bounds__(256, 2) void mfma_bf16_probe_kernel(float* out, int iters) {
   f32x16 acc[8];
@@ -14,7 +13,7 @@ __global__ __launch_bounds__(256, 2) void mfma_bf16_probe_kernel(float* out, int
   for (int m = 0; m < 8; ++m)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-  pb_bf16x8 a[8], b;
+  bf16x8 a[8], b;
 #pragma unroll
   for (int e = 0; e < 8; ++e) b[e] = (__bf16)(0.001f * (float)((threadIdx.x + e) & 31));
 #pragma unroll
@@ -46,12 +45,32 @@ __global__ void placement_probe_kernel(int* out, int spin) {
   while (clock64() - t0 < spin) __builtin_amdgcn_s_sleep(8);   // keep the workgroup resident so that the grid spreads
 }
 
+// the device's operand split as the kernels apply it (csrc/ac_split_bf16.h), for tests/test_gpu_split_bf16.py: thread t
+// splits x[4 t .. 4 t + 3] into dwords 2 t, 2 t + 1 of hi and of lo
+__global__ void split_bf16_probe_kernel(const float* x, long quads, unsigned* hi, unsigned* lo) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= quads) return;
+  u32x2 h, l;
+  split_bf16x4(*(const f32x4*)(x + 4 * t), h, l);
+  *(u32x2*)(hi + 2 * t) = h;
+  *(u32x2*)(lo + 2 * t) = l;
+}
+
 }  // namespace
 
 // C ABI: see include/audiocaption_hip.h
 extern "C" int ac_mfma_bf16_probe(float* out, int blocks, int iters, void* stream) {
   if (!out || blocks <= 0 || iters <= 0) return AC_ERR_ARG;
   hipLaunchKernelGGL(mfma_bf16_probe_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out, iters);
+  return ac_check_launch();
+}
+
+extern "C" int ac_split_bf16_probe(const float* x, long n, unsigned* hi, unsigned* lo, void* stream) {
+  if (!x || !hi || !lo || n <= 0 || n % 4 != 0 || n / 4 > 0x7fffffffL * 256) return AC_ERR_ARG;
+  if (((uintptr_t)x & 15) || ((uintptr_t)hi & 7) || ((uintptr_t)lo & 7)) return AC_ERR_ARG;   // 16-byte loads, 8-byte stores
+  const long quads = n / 4;
+  hipLaunchKernelGGL(split_bf16_probe_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                     quads, hi, lo);
   return ac_check_launch();
 }
 

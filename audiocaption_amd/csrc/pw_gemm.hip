@@ -17,41 +17,23 @@
 //     k-steps): at 12-24 MFMAs per wave and step a single step does not cover the L2 latency;
 //   * the accumulator is the TRANSPOSED tile (weights as the MFMA row operand): a lane ends up with 4 consecutive
 //     channels of one row, so bias / swish / residual work on 16-byte words and the stores are 16 bytes wide.
-// Arithmetic: x = hi + lo (bf16, RNE), products lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, f32 accumulation -
-// 2^-16 relative operand error, the same as the split-bf16 conv tier and ac_gemm_bf16x3.
+// Arithmetic: the split-bf16 operands of csrc/ac_split_bf16.h, the same as the split-bf16 conv tier and ac_gemm_bf16x3.
 #include "ac_common.h"
 #include "ac_drop.h"
+#include "ac_split_bf16.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 pg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned pg_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int PG_ROW = 40;   // bf16 per LDS row: 32 k + 8 pad (80 B: a lane's 16-byte fragment reads stay conflict-light)
 
 struct PwgP {
-  const float* x; const pg_bf16x8* wf; const float* bias; float* y; const float* gate;
+  const float* x; const bf16x8* wf; const float* bias; float* y; const float* gate;
   long ldx, ldy, row0;                                     // row strides in floats; row0: dropout index of row 0
   int M, N, K, KC, NT32, act, gate_rows;
   float beta;
   Drop drop;                                               // inverted dropout on the output (training forward), off: thresh 0
 };
-
-__device__ __forceinline__ unsigned pg_cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-// 4 floats -> 4 bf16 hi (2 dwords) + 4 bf16 lo
-__device__ __forceinline__ void pg_split4(const f32x4 x, pg_u32x2& hi, pg_u32x2& lo) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const unsigned h = pg_cvt_pk_bf16(x[2 * i], x[2 * i + 1]);
-    const float h0 = __builtin_bit_cast(float, h << 16), h1 = __builtin_bit_cast(float, h & 0xffff0000u);
-    hi[i] = h;
-    lo[i] = pg_cvt_pk_bf16(x[2 * i] - h0, x[2 * i + 1] - h1);
-  }
-}
 
 // ---- epilogue: lane = row m0 + 32 a + (lane & 31), registers 4 g .. 4 g + 3 = channels 8 g + 4 (lane >> 5) + 0..3 ----
 template <int MW>
@@ -133,20 +115,20 @@ __global__ __launch_bounds__(256, 2) void pw_bf16x3_kernel(PwgP p) {
   auto commit = [&](int buf, const f32x4 (&pre)[NI], const f32x4 (&pg)[NI]) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      pg_u32x2 hi, lo;
-      pg_split4(pre[j] * pg[j], hi, lo);
-      *(pg_u32x2*)(sA[buf][0] + sdst[j]) = hi;
-      *(pg_u32x2*)(sA[buf][1] + sdst[j]) = lo;
+      u32x2 hi, lo;
+      split_bf16_pairs<2>(pre[j] * pg[j], hi, lo);
+      *(u32x2*)(sA[buf][0] + sdst[j]) = hi;
+      *(u32x2*)(sA[buf][1] + sdst[j]) = lo;
     }
   };
   // ---- weight fragments: (k-step kk, tile nt, plane) = 64 lanes x 16 B at ((kk * NT32 + nt) * 2 + plane) * 64; a ring
   // of four k-steps in registers, k-step kk + 3 requested while kk runs ----
-  const pg_bf16x8* wbase = p.wf + (size_t)min(nt0, p.NT32 - 1) * 2 * 64 + lane;
+  const bf16x8* wbase = p.wf + (size_t)min(nt0, p.NT32 - 1) * 2 * 64 + lane;
   const size_t w_kstep = (size_t)p.NT32 * 2 * 64;
   const int w_t1 = on1 ? 2 * 64 : 0;
   const int nks = p.KC * 2;
-  auto w_load = [&](int kk, pg_bf16x8 (&w)[2][2]) {
-    const pg_bf16x8* q = wbase + (size_t)min(kk, nks - 1) * w_kstep;
+  auto w_load = [&](int kk, bf16x8 (&w)[2][2]) {
+    const bf16x8* q = wbase + (size_t)min(kk, nks - 1) * w_kstep;
     w[0][0] = q[0];
     w[0][1] = q[64];
     w[1][0] = q[w_t1];
@@ -161,13 +143,13 @@ __global__ __launch_bounds__(256, 2) void pw_bf16x3_kernel(PwgP p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   const int frag = (lane & 31) * PG_ROW + 8 * (lane >> 5);
-  pg_bf16x8 w0[2][2], w1[2][2], w2[2][2], w3[2][2];
-  auto kstep = [&](int buf, int ks, const pg_bf16x8 (&wc)[2][2]) {
-    pg_bf16x8 ah[MW], al[MW];
+  bf16x8 w0[2][2], w1[2][2], w2[2][2], w3[2][2];
+  auto kstep = [&](int buf, int ks, const bf16x8 (&wc)[2][2]) {
+    bf16x8 ah[MW], al[MW];
 #pragma unroll
     for (int a = 0; a < MW; ++a) {
-      ah[a] = *(const pg_bf16x8*)(sA[buf][0] + a * 32 * PG_ROW + frag + ks * 16);
-      al[a] = *(const pg_bf16x8*)(sA[buf][1] + a * 32 * PG_ROW + frag + ks * 16);
+      ah[a] = *(const bf16x8*)(sA[buf][0] + a * 32 * PG_ROW + frag + ks * 16);
+      al[a] = *(const bf16x8*)(sA[buf][1] + a * 32 * PG_ROW + frag + ks * 16);
     }
 #pragma unroll
     for (int a = 0; a < MW; ++a)
@@ -254,18 +236,18 @@ __global__ __launch_bounds__(256, 2) void pw_bf16x3_longk_kernel(PwgP p) {
   auto commit = [&](int buf, const f32x4 (&pre)[NI], const f32x4 (&pg)[NI]) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      pg_u32x2 hi, lo;
-      pg_split4(pre[j] * pg[j], hi, lo);
-      *(pg_u32x2*)(sA[buf][0] + sdst + j * 32) = hi;
-      *(pg_u32x2*)(sA[buf][1] + sdst + j * 32) = lo;
+      u32x2 hi, lo;
+      split_bf16_pairs<2>(pre[j] * pg[j], hi, lo);
+      *(u32x2*)(sA[buf][0] + sdst + j * 32) = hi;
+      *(u32x2*)(sA[buf][1] + sdst + j * 32) = lo;
     }
   };
-  const pg_bf16x8* wbase = p.wf + (size_t)min(nt0, p.NT32 - 1) * 2 * 64 + lane;
+  const bf16x8* wbase = p.wf + (size_t)min(nt0, p.NT32 - 1) * 2 * 64 + lane;
   const size_t w_kstep = (size_t)p.NT32 * 2 * 64;
   const int w_t1 = on1 ? 2 * 64 : 0;
   const int nks = p.KC * 2;                        // k-steps the packed weights hold (K rounded up to 32)
-  auto w_load = [&](int kk, pg_bf16x8 (&w)[2][2]) {
-    const pg_bf16x8* q = wbase + (size_t)min(kk, nks - 1) * w_kstep;
+  auto w_load = [&](int kk, bf16x8 (&w)[2][2]) {
+    const bf16x8* q = wbase + (size_t)min(kk, nks - 1) * w_kstep;
     w[0][0] = q[0];
     w[0][1] = q[64];
     w[1][0] = q[w_t1];
@@ -277,11 +259,11 @@ __global__ __launch_bounds__(256, 2) void pw_bf16x3_longk_kernel(PwgP p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][b][r] = 0.f;
   const int frag = (lane & 31) * PG_ROWL + 8 * (lane >> 5);
-  pg_bf16x8 w0[2][2], w1[2][2], w2[2][2], w3[2][2];
-  auto kstep = [&](int buf, int ks, int kk, const pg_bf16x8 (&wc)[2][2]) {
+  bf16x8 w0[2][2], w1[2][2], w2[2][2], w3[2][2];
+  auto kstep = [&](int buf, int ks, int kk, const bf16x8 (&wc)[2][2]) {
     if (kk >= nks) return;                          // beyond the packed k-steps (K % 128 != 0): zeros anyway
-    const pg_bf16x8 ah = *(const pg_bf16x8*)(sA[buf][0] + frag + ks * 16);
-    const pg_bf16x8 al = *(const pg_bf16x8*)(sA[buf][1] + frag + ks * 16);
+    const bf16x8 ah = *(const bf16x8*)(sA[buf][0] + frag + ks * 16);
+    const bf16x8 al = *(const bf16x8*)(sA[buf][1] + frag + ks * 16);
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[b][0], al, acc[0][b], 0, 0, 0);
@@ -340,7 +322,6 @@ struct PwPackDesc {
 // One thread = one lane's fragment of one (k-group, column tile): 8 consecutive k of one column -> 16 bytes of the hi plane
 // and 16 of the lo plane (the first form wrote one bf16 per thread: 454 us per training step for the 10.7 M parameters).
 __device__ __forceinline__ void pw_pack_items(const PwPackDesc& d, long first, long stride) {
-  typedef __bf16 pk_bf16x8 __attribute__((ext_vector_type(8)));
   const int NT32 = (d.N + 31) / 32, KS = (d.K + 31) / 32 * 2;
   const long items = (long)KS * NT32 * 64;
   for (long it = first; it < items; it += stride) {
@@ -357,15 +338,15 @@ __device__ __forceinline__ void pw_pack_items(const PwPackDesc& d, long first, l
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (n < d.N && k0 + e < d.K) ? d.w[(long)n * d.s_n + (long)(k0 + e) * d.s_k] : 0.f;
     }
-    pk_bf16x8 hi, lo;
+    bf16x8 hi, lo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const __bf16 h = (__bf16)v[e];
       hi[e] = h;
       lo[e] = (__bf16)(v[e] - (float)h);
     }
-    *(pk_bf16x8*)(d.out + ((t * 2) * 64 + lane) * 8) = hi;
-    *(pk_bf16x8*)(d.out + ((t * 2 + 1) * 64 + lane) * 8) = lo;
+    *(bf16x8*)(d.out + ((t * 2) * 64 + lane) * 8) = hi;
+    *(bf16x8*)(d.out + ((t * 2 + 1) * 64 + lane) * 8) = lo;
   }
 }
 __global__ void pw_pack_kernel(const PwPackDesc* table) {
@@ -418,7 +399,7 @@ int ac_pw_gemm_bf16x3_ex(const float* x, long ldx, const void* wfrag, const floa
       (bias && ((uintptr_t)bias & 15)) || (gate && ((uintptr_t)gate & 15)))
     return AC_ERR_ARG;
   PwgP p;
-  p.x = x; p.wf = (const pg_bf16x8*)wfrag; p.bias = bias; p.y = y; p.gate = gate;
+  p.x = x; p.wf = (const bf16x8*)wfrag; p.bias = bias; p.y = y; p.gate = gate;
   p.ldx = ldx; p.ldy = ldy; p.row0 = row0; p.drop = make_drop(drop_p, drop_seed, seed_dev);
   p.M = (int)M; p.N = N; p.K = K; p.KC = (K + 31) / 32; p.NT32 = (N + 31) / 32; p.act = act; p.gate_rows = gate ? gate_rows : 1;
   p.beta = beta;

@@ -11,6 +11,7 @@
 // stored, and the CPU oracle reproduces them bit for bit (oracle/train_path.py).
 #include "ac_common.h"
 #include "ac_drop.h"
+#include "ac_split_bf16.h"
 
 namespace {
 
@@ -324,8 +325,7 @@ __global__ __launch_bounds__(256) void gemm_kk_kernel(GemmP p) {
 // =========================================================================================================
 // Split-bf16 GEMM ("bf16x3"): the same contract as gemm_general_kernel - C = epilogue(sum_k A(m,k) B(k,n)), each operand
 // contiguous along k OR along its row dimension - at 5x the f32 matrix rate.  Every f32 operand is split when it is
-// staged into LDS, x = hi + lo (bf16 each, RNE; 16 significant bits together), and a product is three bf16 MFMAs
-// (lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, f32 accumulation): 2^-16 relative operand error instead of exact
+// staged into LDS and a product is three bf16 MFMAs (csrc/ac_split_bf16.h): 2^-16 relative operand error instead of exact
 // f32, the arithmetic of the split-bf16 conv tier.  It serves the backward GEMMs of the training step (dY W, dY^T X
 // with split-K atomics; 7 392 rows) and the teacher-forced forward GEMMs, which is where the decoder's matrix work is.
 //
@@ -337,25 +337,7 @@ __global__ __launch_bounds__(256) void gemm_kk_kernel(GemmP p) {
 //   operand contiguous along rows  : item = (4 rows, 8-k group): eight 16-byte loads (4 rows at one k each), transposed
 //                                    in registers, one 16-byte LDS store per row and plane
 // =========================================================================================================
-typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned gb_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int GB_ROW = 40;   // bf16 elements per LDS row
-
-__device__ __forceinline__ unsigned gb_cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-// 8 floats -> 8 bf16 hi (4 dwords) + 8 bf16 lo
-__device__ __forceinline__ void gb_split8(const float (&x)[8], gb_u32x4& hi, gb_u32x4& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned h = gb_cvt_pk_bf16(x[2 * i], x[2 * i + 1]);
-    const float h0 = __builtin_bit_cast(float, h << 16), h1 = __builtin_bit_cast(float, h & 0xffff0000u);
-    hi[i] = h;
-    lo[i] = gb_cvt_pk_bf16(x[2 * i] - h0, x[2 * i + 1] - h1);
-  }
-}
 
 template <int TM, int TN>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmP p) {
@@ -435,10 +417,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmP p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { x[e] *= gate[2 * j][e]; x[4 + e] *= gate[2 * j + 1][e]; }
         }
-        gb_u32x4 hi, lo;
-        gb_split8(x, hi, lo);
-        *(gb_u32x4*)(dst_hi + row * GB_ROW + kg * 8) = hi;
-        *(gb_u32x4*)(dst_lo + row * GB_ROW + kg * 8) = lo;
+        u32x4 hi, lo;
+        split_bf16_pairs<4>(x, hi, lo);
+        *(u32x4*)(dst_hi + row * GB_ROW + kg * 8) = hi;
+        *(u32x4*)(dst_lo + row * GB_ROW + kg * 8) = lo;
       }
     } else {
       const int rgs = rows >> 2;
@@ -447,10 +429,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float x[8] = {pre[0][i], pre[1][i], pre[2][i], pre[3][i], pre[4][i], pre[5][i], pre[6][i], pre[7][i]};
-          gb_u32x4 hi, lo;
-          gb_split8(x, hi, lo);
-          *(gb_u32x4*)(dst_hi + (rg * 4 + i) * GB_ROW + kg * 8) = hi;
-          *(gb_u32x4*)(dst_lo + (rg * 4 + i) * GB_ROW + kg * 8) = lo;
+          u32x4 hi, lo;
+          split_bf16_pairs<4>(x, hi, lo);
+          *(u32x4*)(dst_hi + (rg * 4 + i) * GB_ROW + kg * 8) = hi;
+          *(u32x4*)(dst_lo + (rg * 4 + i) * GB_ROW + kg * 8) = lo;
         }
       }
     }
@@ -472,25 +454,21 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmP p) {
     if (c + 1 < nchunks) request(kbeg + (c + 1) * 32);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      gb_bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
       for (int a = 0; a < TM; ++a) {
-        ah[a] = *(const gb_bf16x8*)(sA[0] + ((wm * TM + a) * 32) * GB_ROW + frag + ks * 16);
-        al[a] = *(const gb_bf16x8*)(sA[1] + ((wm * TM + a) * 32) * GB_ROW + frag + ks * 16);
+        ah[a] = *(const bf16x8*)(sA[0] + ((wm * TM + a) * 32) * GB_ROW + frag + ks * 16);
+        al[a] = *(const bf16x8*)(sA[1] + ((wm * TM + a) * 32) * GB_ROW + frag + ks * 16);
       }
 #pragma unroll
       for (int b = 0; b < TN; ++b) {
-        bh[b] = *(const gb_bf16x8*)(sB[0] + ((wn * TN + b) * 32) * GB_ROW + frag + ks * 16);
-        bl[b] = *(const gb_bf16x8*)(sB[1] + ((wn * TN + b) * 32) * GB_ROW + frag + ks * 16);
+        bh[b] = *(const bf16x8*)(sB[0] + ((wn * TN + b) * 32) * GB_ROW + frag + ks * 16);
+        bl[b] = *(const bf16x8*)(sB[1] + ((wn * TN + b) * 32) * GB_ROW + frag + ks * 16);
       }
 #pragma unroll
       for (int a = 0; a < TM; ++a)
 #pragma unroll
-        for (int b = 0; b < TN; ++b) {
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[b], acc[a][b], 0, 0, 0);
-        }
+        for (int b = 0; b < TN; ++b) acc[a][b] = mfma_bf16x3(ah[a], al[a], bh[b], bl[b], acc[a][b]);
     }
   }
   // ---- epilogue: the same as gemm_general_kernel's ----

@@ -109,49 +109,81 @@ def _observed(algo, B, Hp, H, W, Cin, Cout, mode, **more):
     return _Observed(hook, dict(B=B, H=H, Hp=Hp, W=W, Cin=Cin, Cout=Cout, mode=mode, algo=algo, **more))
 
 
-def conv3x3_bn_relu(x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
+def _plain_conv(symbol, tier_name, x, w, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode):
+    """The body of the conv3x3 + BN + ReLU entry points that take the common argument list: the library's ``symbol``,
+    reported to observers as ``tier_name``."""
     lib = _lib.load()
-    with _observed("direct", B, Hp, H, W, Cin, Cout, mode):
-        check(lib.ac_conv3x3_bn_relu(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                     mode, map_mode, stream()), "ac_conv3x3_bn_relu")
+    with _observed(tier_name, B, Hp, H, W, Cin, Cout, mode):
+        check(getattr(lib, symbol)(ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout, mode, map_mode,
+                                   stream()), symbol)
     return out
+
+
+def conv3x3_bn_relu(x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
+    return _plain_conv("ac_conv3x3_bn_relu", "direct", x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode)
 
 
 def conv3x3_bn_relu_winograd(x, upk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
-    lib = _lib.load()
-    with _observed("winograd", B, Hp, H, W, Cin, Cout, mode):
-        check(lib.ac_conv3x3_bn_relu_winograd(ptr(x), ptr(upk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                              mode, map_mode, stream()), "ac_conv3x3_bn_relu_winograd")
-    return out
+    return _plain_conv("ac_conv3x3_bn_relu_winograd", "winograd", x, upk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode)
 
 
 def conv3x3_bn_relu_bf16x3(x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
-    lib = _lib.load()
-    with _observed("bf16x3", B, Hp, H, W, Cin, Cout, mode):
-        check(lib.ac_conv3x3_bn_relu_bf16x3(ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                            mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3")
-    return out
+    return _plain_conv("ac_conv3x3_bn_relu_bf16x3", "bf16x3", x, wpk, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode)
+
+
+def conv3x3_bn_relu_bf16x3_gw(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
+    return _plain_conv("ac_conv3x3_bn_relu_bf16x3_gw", "bf16x3", x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode)
+
+
+def _split(u, dtype):
+    hi = u.to(dtype)
+    return hi, (u - hi.to(u.dtype)).to(dtype)
+
+
+def split_bf16(u):
+    """u (float32 or float64) -> (hi, lo) bfloat16 with hi = RNE_bf16(u), lo = RNE_bf16(u - hi), the subtraction in u's own
+    precision: u = hi + lo to 2^-16 |u|.  THE host-side definition of the split-bf16 operand convention - every weight
+    packer below pre-splits with it; the kernels split the other operand the same way (csrc/ac_split_bf16.h,
+    ``split_bf16_device``) and tests/_split_ref.py derives the conv error bars from it."""
+    return _split(u, torch.bfloat16)
+
+
+def split_bf16_device(x):
+    """The split as the kernels apply it (tests): x f32 on the device, numel % 4 == 0 -> (hi, lo) bfloat16 of x's shape."""
+    x = f32c(_dev(x))
+    hi, lo = torch.empty_like(x, dtype=torch.bfloat16), torch.empty_like(x, dtype=torch.bfloat16)
+    check(_lib.load().ac_split_bf16_probe(ptr(x), x.numel(), ptr(hi), ptr(lo), stream()), "ac_split_bf16_probe")
+    return hi, lo
+
+
+def _frag_order(t, taps, k_step):
+    """(Cout, Cin, taps...) -> MFMA fragment order, lane = (cout % 32) + 32 * ((cin % 16) // 8), element = cin % 8:
+    ``k_step`` 32: [Cin/32][taps][2 ks][Cout/32][64 lanes][8] (two 16-channel k-steps per 32-channel chunk);
+    ``k_step`` 16: [Cin/16][taps][Cout/32][64 lanes][8]."""
+    cout, cin = t.shape[0], t.shape[1]
+    t = t.reshape(cout, cin, taps).permute(1, 2, 0)                              # (cin, tap, cout)
+    if k_step == 32:
+        t = t.reshape(cin // 32, 2, 2, 8, taps, cout // 32, 32)                  # [c][ks][h][e][tap][nt][r]
+        return t.permute(0, 4, 1, 5, 2, 6, 3).reshape(cin // 32, taps, 2, cout // 32, 64, 8)
+    t = t.reshape(cin // 16, 2, 8, taps, cout // 32, 32)                         # [step][h][e][tap][nt][r]
+    return t.permute(0, 3, 4, 1, 5, 2).reshape(cin // 16, taps, cout // 32, 64, 8)
+
+
+def _split_frags(hi, lo, taps, k_step):
+    """The (hi, lo) planes of a split, each in fragment order, interleaved per channel tile: [...][2 (hi, lo)][64][8]."""
+    return torch.stack([_frag_order(hi, taps, k_step), _frag_order(lo, taps, k_step)], dim=-3).contiguous()
 
 
 def pack_conv_weight_bf16x3(w):
     """OIHW f32 -> split bf16 planes [Cin/32][9][2 (hi, lo)][Cout][32] (csrc/conv3x3.hip, bf16x3 kernel).
     hi = RNE_bf16(w), lo = RNE_bf16(w - hi)."""
     cout, cin = w.shape[0], w.shape[1]
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
 
     def lay(t):
         return t.permute(1, 2, 3, 0).reshape(cin // 32, 32, 9, cout).permute(0, 2, 3, 1)
 
+    hi, lo = split_bf16(w)
     return torch.stack([lay(hi), lay(lo)], dim=2).contiguous()
-
-
-def conv3x3_bn_relu_bf16x3_gw(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1):
-    lib = _lib.load()
-    with _observed("bf16x3", B, Hp, H, W, Cin, Cout, mode):
-        check(lib.ac_conv3x3_bn_relu_bf16x3_gw(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                               mode, map_mode, stream()), "ac_conv3x3_bn_relu_bf16x3_gw")
-    return out
 
 
 def conv5x5_first(x, w, scale, shift, out, B, Hp, H):
@@ -248,25 +280,31 @@ def wino43_workgroups(B, Hp, W, Cout):
     return int(_lib.load().ac_conv3x3_wino43_workgroups(B, Hp, W, Cout))
 
 
+def _conv3x3_bn_relu_w4(stem, x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need, dropout, tiles_per_wave):
+    """The body of the two tile forms of csrc/conv3x3_wino43.hip; ``stem``: "wino43" (row quads) or "wino63" (row sextets)."""
+    lib = _lib.load()
+    cf, mul, add = need if need is not None else (None, 0, 0)
+    if dropout is not None and cf is not None:
+        raise ValueError(f"conv3x3_bn_relu_{stem}: dropout and dead-row skipping are not combined")
+    name = f"ac_conv3x3_bn_relu_{stem}"
+    with _observed("wino43", B, Hp, H, W, Cin, Cout, mode):
+        if dropout is not None:
+            check(getattr(lib, name + "_drop")(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
+                                               mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2], stream()),
+                  name + "_drop")
+        else:
+            check(getattr(lib, name)(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout, mode,
+                                     map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()), name)
+    return out
+
+
 def conv3x3_bn_relu_wino43(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1, need=None, dropout=None,
                            tiles_per_wave=0):
     """F(4,3) Winograd along time on split-bf16 operands, one wave per SIMD (csrc/conv3x3_wino43.hip); ``wfrag`` from
     ``pack_conv_weight_wino43_frag``.  Covers W in (32, 16, 8, 4) with modes 0 / 1 and W = 2 with modes 0 / 2 (mean over
     mel), Cout % 128 == 0, Hp % 4 == 0; ``need`` and ``dropout`` as for ``conv3x3_bn_relu_wino1d``."""
-    lib = _lib.load()
-    cf, mul, add = need if need is not None else (None, 0, 0)
-    if dropout is not None and cf is not None:
-        raise ValueError("conv3x3_bn_relu_wino43: dropout and dead-row skipping are not combined")
-    with _observed("wino43", B, Hp, H, W, Cin, Cout, mode):
-        if dropout is not None:
-            check(lib.ac_conv3x3_bn_relu_wino43_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                                     Cout, mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2],
-                                                     stream()), "ac_conv3x3_bn_relu_wino43_drop")
-        else:
-            check(lib.ac_conv3x3_bn_relu_wino43(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                                mode, map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()),
-                  "ac_conv3x3_bn_relu_wino43")
-    return out
+    return _conv3x3_bn_relu_w4("wino43", x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need, dropout,
+                               tiles_per_wave)
 
 
 def conv3x3_bn_relu_wino63(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode=-1, need=None, dropout=None,
@@ -275,20 +313,8 @@ def conv3x3_bn_relu_wino63(x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, 
     kernel source and the same contract (csrc/conv3x3_wino43.hip); ``wfrag`` from ``pack_conv_weight_wino63_frag``.
     Covers W in (32, 16, 8) with modes 0 / 1; sextets run over the stacked ``B * Hp`` rows, so ``Hp % 4 == 0`` is all a
     buffer has to keep.  Reported to observers as the "wino43" tier it is a tile form of."""
-    lib = _lib.load()
-    cf, mul, add = need if need is not None else (None, 0, 0)
-    if dropout is not None and cf is not None:
-        raise ValueError("conv3x3_bn_relu_wino63: dropout and dead-row skipping are not combined")
-    with _observed("wino43", B, Hp, H, W, Cin, Cout, mode):
-        if dropout is not None:
-            check(lib.ac_conv3x3_bn_relu_wino63_drop(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin,
-                                                     Cout, mode, map_mode, float(dropout[0]), int(dropout[1]), dropout[2],
-                                                     stream()), "ac_conv3x3_bn_relu_wino63_drop")
-        else:
-            check(lib.ac_conv3x3_bn_relu_wino63(ptr(x), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), B, Hp, H, W, Cin, Cout,
-                                                mode, map_mode, int(tiles_per_wave), ptr(cf), int(mul), int(add), stream()),
-                  "ac_conv3x3_bn_relu_wino63")
-    return out
+    return _conv3x3_bn_relu_w4("wino63", x, wfrag, scale, shift, out, B, Hp, H, W, Cin, Cout, mode, map_mode, need, dropout,
+                               tiles_per_wave)
 
 
 def skinny_workspace_floats(B, Hp, W, Cin, Cout):
@@ -330,98 +356,57 @@ def pack_conv_weight_f16x2_frag(w):
     Every output channel is first multiplied by the power of two that brings its largest |w| into [2^13, 2^14): the
     lo parts (~2^-12 of the hi parts) are then normal fp16 numbers for every weight above 2^-15 of the channel maximum;
     ``inv_scale`` (exact powers of two) goes into the BN scale of the epilogue."""
-    cout, cin = w.shape[0], w.shape[1]
     amax = w.abs().amax(dim=(1, 2, 3)).clamp_min(1e-30)
     e = 13 - torch.floor(torch.log2(amax))
-    ws = w * torch.exp2(e).view(-1, 1, 1, 1)
-    hi = ws.to(torch.float16)
-    lo = (ws - hi.float()).to(torch.float16)
-
-    def lay(t):
-        t = t.permute(1, 2, 3, 0).reshape(cin // 32, 2, 2, 8, 9, cout // 32, 32)
-        return t.permute(0, 4, 1, 5, 2, 6, 3).reshape(cin // 32, 9, 2, cout // 32, 64, 8)
-
-    return torch.stack([lay(hi), lay(lo)], dim=4).contiguous(), torch.exp2(-e).contiguous()
+    hi, lo = _split(w * torch.exp2(e).view(-1, 1, 1, 1), torch.float16)
+    return _split_frags(hi, lo, 9, 32), torch.exp2(-e).contiguous()
 
 
 def pack_conv_weight_bf16x3_frag(w):
     """OIHW f32 -> split bf16 in MFMA fragment order [Cin/32][9][2 ks][Cout/32][2 (hi, lo)][64 lanes][8]:
     lane = (cout % 32) + 32 * ((cin % 16) // 8), element = cin % 8 (csrc/conv3x3.hip, "gw" kernel)."""
-    cout, cin = w.shape[0], w.shape[1]
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
-
-    taps = w.shape[2] * w.shape[3]   # 9, or 1 for the linear layers
-
-    def lay(t):
-        # (cout, cin, 3, 3) -> (cin, tap, cout) -> [c][ks][h][e][tap][nt][r] -> [c][tap][ks][nt][h][r][e]
-        t = t.permute(1, 2, 3, 0).reshape(cin // 32, 2, 2, 8, taps, cout // 32, 32)
-        return t.permute(0, 4, 1, 5, 2, 6, 3).reshape(cin // 32, taps, 2, cout // 32, 64, 8)
-
-    return torch.stack([lay(hi), lay(lo)], dim=4).contiguous()
+    hi, lo = split_bf16(w)
+    return _split_frags(hi, lo, w.shape[2] * w.shape[3], 32)   # 9 taps, or 1 for the linear layers
 
 
 def pack_conv_weight_wino1d_frag(w):
     """OIHW f32 -> U = G g (F(2,3) filter transform over the time taps ky, evaluated in float64), split into bf16
     hi + lo, in MFMA fragment order [Cin/32][12 = 3 kx x 4 positions][2 ks][Cout/32][2 (hi, lo)][64 lanes][8]
     (csrc/conv3x3_wino1d.hip).  Pure elementwise / small-matrix torch ops: no library GEMM."""
-    cout, cin = w.shape[0], w.shape[1]
     g = w.double()                                                   # (o, c, ky, kx)
     u = torch.stack([g[:, :, 0], 0.5 * (g[:, :, 0] + g[:, :, 1] + g[:, :, 2]),
                      0.5 * (g[:, :, 0] - g[:, :, 1] + g[:, :, 2]), g[:, :, 2]], dim=3)   # (o, c, kx, position)
-    u = u.reshape(cout, cin, 12, 1)                                  # "tap" = kx * 4 + position
-    hi = u.to(torch.bfloat16)
-    lo = (u - hi.double()).to(torch.bfloat16)
+    hi, lo = split_bf16(u)
+    return _split_frags(hi, lo, 12, 32)                              # "tap" = kx * 4 + position
 
-    def lay(t):
-        t = t.permute(1, 2, 3, 0).reshape(cin // 32, 2, 2, 8, 12, cout // 32, 32)
-        return t.permute(0, 4, 1, 5, 2, 6, 3).reshape(cin // 32, 12, 2, cout // 32, 64, 8)
 
-    return torch.stack([lay(hi), lay(lo)], dim=4).contiguous()
+# The filter transforms G (rows = positions) of F(4,3), points 0, +-1, +-2, inf, and F(6,3), points 0, +-1, +-2, +-1/2, inf
+WINO43_G = ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6),
+            (0, 0, 1))
+WINO63_G = ((1, 0, 0), (-2 / 9, -2 / 9, -2 / 9), (-2 / 9, 2 / 9, -2 / 9), (1 / 90, 1 / 45, 2 / 45), (1 / 90, -1 / 45, 2 / 45),
+            (32 / 45, 16 / 45, 8 / 45), (32 / 45, -16 / 45, 8 / 45), (0, 0, 1))
+
+
+def _pack_wino_time_frag(w, G):
+    """OIHW f32 -> U = G g over the time taps ky in float64, split, [Cin/16][3 kx x len(G) positions][Cout/32][2][64][8]."""
+    g = w.double()                                                   # (o, c, ky, kx)
+    u = torch.stack([Gp[0] * g[:, :, 0] + Gp[1] * g[:, :, 1] + Gp[2] * g[:, :, 2] for Gp in G], dim=3)   # (o, c, kx, p)
+    hi, lo = split_bf16(u)
+    return _split_frags(hi, lo, 3 * len(G), 16)                      # tap = kx * len(G) + position
 
 
 def pack_conv_weight_wino43_frag(w):
     """OIHW f32 -> U = G g (F(4,3) filter transform over the time taps ky, evaluated in float64), split into bf16
     hi + lo, in MFMA fragment order [Cin/16][18 = 3 kx x 6 positions][Cout/32][2 (hi, lo)][64 lanes][8]: lane
     (cout % 32) + 32 * ((cin % 16) // 8), element cin % 8 (csrc/conv3x3_wino43.hip).  Elementwise torch ops only."""
-    cout, cin = w.shape[0], w.shape[1]
-    g = w.double()                                                   # (o, c, ky, kx)
-    G = ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6),
-         (0, 0, 1))
-    u = torch.stack([G[p][0] * g[:, :, 0] + G[p][1] * g[:, :, 1] + G[p][2] * g[:, :, 2] for p in range(6)], dim=3)   # (o, c, kx, p)
-    u = u.reshape(cout, cin, 18)                                     # tap = kx * 6 + position
-    hi = u.to(torch.bfloat16)
-    lo = (u - hi.double()).to(torch.bfloat16)
-
-    def lay(t):
-        t = t.permute(1, 2, 0).reshape(cin // 16, 2, 8, 18, cout // 32, 32)     # (step, k-half, j, tap, channel tile, n)
-        return t.permute(0, 3, 4, 1, 5, 2).reshape(cin // 16, 18, cout // 32, 64, 8)
-
-    return torch.stack([lay(hi), lay(lo)], dim=3).contiguous()
-
-
-# F(6,3), points 0, +-1, +-2, +-1/2, inf: the filter transform G (rows = positions)
-WINO63_G = ((1, 0, 0), (-2 / 9, -2 / 9, -2 / 9), (-2 / 9, 2 / 9, -2 / 9), (1 / 90, 1 / 45, 2 / 45), (1 / 90, -1 / 45, 2 / 45),
-            (32 / 45, 16 / 45, 8 / 45), (32 / 45, -16 / 45, 8 / 45), (0, 0, 1))
+    return _pack_wino_time_frag(w, WINO43_G)
 
 
 def pack_conv_weight_wino63_frag(w):
     """OIHW f32 -> U = G g (F(6,3) filter transform over the time taps ky, evaluated in float64), split into bf16
     hi + lo, in MFMA fragment order [Cin/16][24 = 3 kx x 8 positions][Cout/32][2 (hi, lo)][64 lanes][8]: the layout of
     ``pack_conv_weight_wino43_frag`` with eight positions (csrc/conv3x3_wino43.hip, row sextets).  Elementwise torch ops only."""
-    cout, cin = w.shape[0], w.shape[1]
-    g = w.double()                                                   # (o, c, ky, kx)
-    G = WINO63_G
-    u = torch.stack([G[p][0] * g[:, :, 0] + G[p][1] * g[:, :, 1] + G[p][2] * g[:, :, 2] for p in range(8)], dim=3)   # (o, c, kx, p)
-    u = u.reshape(cout, cin, 24)                                     # tap = kx * 8 + position
-    hi = u.to(torch.bfloat16)
-    lo = (u - hi.double()).to(torch.bfloat16)
-
-    def lay(t):
-        t = t.permute(1, 2, 0).reshape(cin // 16, 2, 8, 24, cout // 32, 32)     # (step, k-half, j, tap, channel tile, n)
-        return t.permute(0, 3, 4, 1, 5, 2).reshape(cin // 16, 24, cout // 32, 64, 8)
-
-    return torch.stack([lay(hi), lay(lo)], dim=3).contiguous()
+    return _pack_wino_time_frag(w, WINO63_G)
 
 
 def pack_conv_weight_winograd(w):

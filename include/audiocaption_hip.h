@@ -1275,6 +1275,11 @@ int ac_gelu(const float* x, float* y, long n, void* stream);
  * holds under matrix load - the context of `roofline.frac`, whose denominator is the NOMINAL dense peak. */
 int ac_mfma_bf16_probe(float* out, int blocks, int iters, void* stream);
 
+/* Diagnostic (tests): the split-bf16 operand split exactly as the kernels apply it (csrc/ac_split_bf16.h).  x [n] f32,
+ * n % 4 == 0 -> hi [n / 2], lo [n / 2] dwords of two bf16 each (element 2 i in the low half): hi = RNE_bf16(x),
+ * lo = RNE_bf16(x - hi).  One thread per four floats. */
+int ac_split_bf16_probe(const float* x, long n, unsigned* hi, unsigned* lo, void* stream);
+
 /* Diagnostic: `blocks` workgroups of `threads` threads record where they ran - out[2 b] = XCC_ID register, out[2 b + 1] =
  * HW_ID register (cu_id bits 11:8, sh_id bit 12, se_id bits 15:13) - and stay resident for spin_ticks of the 100 MHz clock. */
 int ac_placement_probe(int* out, int blocks, int threads, int spin_ticks, void* stream);

@@ -95,7 +95,7 @@ def test_wino63_half_size_form_is_the_default_for_short_k(K, mode):
 
 def _dead_rows(B, Hp, H, rows_blk, need):
     """Stacked rows of the row blocks (``rows_blk`` rows each, from row 0) in which every row lies at or beyond
-    min(H, need[b]) of its clip: the blocks the kernel does not convolve (csrc/ac_wino43.h w4_rows_live)."""
+    min(H, need[b]) of its clip: the blocks the kernel does not convolve (csrc/ac_conv_tile.h rows_live)."""
     dead = torch.zeros(B * Hp, dtype=torch.bool)
     for r0 in range(0, B * Hp, rows_blk):
         r1 = min(r0 + rows_blk, B * Hp)
